@@ -343,6 +343,27 @@ def test_bench_line_is_compact():
     assert len(json.dumps(di)) < bench.MAX_LINE_BYTES and di["dtype"] == "bf16" and di["roofline"]["deconv_mask_frac"] > 0
 
 
+def test_bench_dump_outputs_writes_float_arrays_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per array, float32 / float64 only (integers exact in float64), small arrays whole, an array over
+    DUMP_MAX_ELEMS elements as the same seeded sample in every call, everything within DUMP_MAX_BYTES."""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 12345, dtype=torch.float32)
+    arrays = {"terms": torch.tensor([1.5, 2.5]), "ids": torch.tensor([[3, -1], [0, 7]], dtype=torch.int32), "weights": (1.0, 0.25), "big": big, "none": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["big.npy", "ids.npy", "terms.npy", "weights.npy"]
+    assert got["terms"].dtype == np.float32 and np.array_equal(got["terms"], [1.5, 2.5])
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], [[3, -1], [0, 7]])
+    assert got["weights"].dtype == np.float64 and np.array_equal(got["weights"], [1.0, 0.25])
+    s = got["big"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(s) > 0)    # distinct positions, in order
+    assert np.array_equal(s, np.load(str(tmp_path / "b" / "big.npy")))
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES == 64 << 20
+
+
 def test_bench_algorithmic_work_matches_survey():
     import importlib
     bench = importlib.import_module("bench")
