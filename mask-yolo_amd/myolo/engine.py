@@ -12,6 +12,7 @@ yolo_branch_graph :249-278; feature_map :848; DecodeYOLOLayer :1442-1473; Detect
 :605-661; build_mask_graph :668-715; yolo_custom_loss :86-242; myolo_mask_loss_graph :718-754;
 compile :1062-1094 (loss sum + Adam).
 """
+import contextlib
 import os
 import threading
 import time
@@ -140,6 +141,14 @@ class Workspace(object):
         return self.buf.numel()
 
 
+class _Side(object):
+    """A side stream of the training step (or of an inference forward), the scratch buffer every launch issued on it uses (None: launches
+    there may use none), and whether work queued on it has not been joined into another stream yet (Net._on / Net._join)."""
+
+    def __init__(self, stream, ws):
+        self.stream, self.ws, self.pending = stream, ws, False
+
+
 def _ensure_hw_queues(want=2):
     """HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues.  A side stream that lands on the COMPUTE stream's queue
     serialises against it in submission order (measured: +4 ... +8 ms per training step, profiles/r3_notes.md "hardware queues"; an extra
@@ -211,10 +220,11 @@ class Net(object):
         self._fork_now = None             # the effective value while predict_graphed captures / runs a forward for a given number of lanes
         # a captured graph bakes in pointers to the scratch buffer: growing it (a bigger launch on the same Net) drops the graphs
         self._ws_main = Workspace(self.dev, on_realloc=lambda: self._drop_graphs(0))
-        self._ws_side = Workspace(self.dev)    # scratch of the YOLO-head backward running on the side stream
-        self._ws_active = self._ws_main
+        self._side = None                 # the side a block runs on (Net._on): its scratch is what self.ws gives; None = the compute stream's
+        # the YOLO loss and the YOLO head's backward, under the mask head (training step); later the backbone's weight gradients (the last part of
+        # the step), the stream being idle by then, instead of queueing behind conv1's weight gradient on the weight-gradient stream
         self._yolo_stream = _shared_stream(self.dev, "yolo_head_bwd")
-        self.overlap_yolo_bwd = True      # YOLO-head backward on a side stream, under the mask head (training step)
+        self._yolo_side = _Side(self._yolo_stream, Workspace(self.dev))
         # When the YOLO head's backward is launched: 1 = right behind the YOLO loss, under the mask head's FORWARD; 0 = at the start of the mask head's
         # backward (rounds 3-5); -1 (default) = early exactly when a gradient exchange is active (GradReducer.attach sets exchange_active).  Same step
         # time on one GPU either way (19.40 against 19.41 ms, round 6).  Early, its 12.9 MB gradient bucket is complete 9.3 ms before the step ends
@@ -223,39 +233,20 @@ class Net(object):
         # kernel's launches: 1.36 against 1.19 ms) and give it back in the backward, so the late form stays there.
         self.yolo_bwd_early = -1
         self.exchange_active = False      # set by myolo.dist.GradReducer.attach: collectives are really issued (world > 1, or a 1-rank probe)
-        # conv1's weight gradient (MFMA-bound, 2.7 ms, nothing downstream but the optimiser) on a third stream with its own
-        # scratch, underneath conv1's data gradient -> ROIAlign backward -> backbone backward (launch- / HBM-bound small kernels)
+        # ONE weight-gradient stream with its own scratch, its launches strictly in order: conv1's weight gradient (MFMA-bound, 2.7 ms, nothing
+        # downstream but the optimiser), queued behind the weight / bias gradients of the compacted conv2-4 / deconv backward, underneath conv1's
+        # data gradient -> ROIAlign backward -> backbone backward (launch- / HBM-bound small kernels); and the weight gradients of the YOLO blocks
+        # and feature_map, beside the BatchNorm-backward -> data-gradient chain that is the critical path of the trunk backward.  Measured
+        # (profiles/r3_notes.md, "hardware queues"): a second, really concurrent weight-gradient stream made the step 1.6 ms SLOWER
         self._wgrad_stream = _shared_stream(self.dev, "weight_gradients")
-        self._ws_wgrad = Workspace(self.dev)
-        self.overlap_conv1_wgrad = True
-        self.overlap_compact_wgrad = True  # ... and the weight / bias gradients of the compacted conv2-4 / deconv backward in front of it on that stream
-        # the trunk's weight-gradient kernels (no consumer but the optimiser) on their own stream and scratch, beside the
-        # BatchNorm-backward -> data-gradient chain that is the critical path of the trunk backward
-        self._twg_stream_own_ = None           # (created on demand: the two-stream ablation only)
-        self._ws_twg_own = Workspace(self.dev)
-        # 1 (default): they share conv1's weight-gradient stream and scratch -- ONE weight-gradient stream, its launches strictly in order.
-        # Measured (profiles/r3_notes.md, "hardware queues"): with the two streams really concurrent the step is 1.6 ms SLOWER; HIP's default
-        # of four hardware queues happened to alias them, a mapping that depends on stream creation order -- so the order is made explicit
-        self.single_wgrad_stream = 1
-        self.overlap_trunk_wgrad = True
-        self._twg_pending = False
-        self._twg_used = set()
-        self._twg_override = None              # (stream, scratch) the trunk's weight gradients go to instead, see backbone_wgrad_on_yolo_stream
-        self.backbone_wgrad_on_yolo_stream = 1 # 1 = the backbone's weight gradients (the last part of the step) run on the YOLO-head stream, idle by then, instead of queueing behind conv1's weight gradient on the weight-gradient stream
-        # ... and started only when conv1's data gradient (the other matrix-pipe-bound kernel of that window) has been issued: two MFMA-bound
-        # kernels sharing the chip each run at half speed, an MFMA-bound one beside the small HBM- / latency-bound kernels of the trunk
-        # backward costs neither much (0 = start it together with the data gradient, as in round 2)
-        self.conv1_wgrad_after_dgrad = 0
-        self._wgrad_pending = False
-        self.mask_keep_pre = True         # F(6,3) chain in training: the positive ROIs' PRE-BatchNorm conv outputs are kept (exact bn2-4 backward); False: post-activation + (a - beta) / gamma
+        self._wgrad_side = _Side(self._wgrad_stream, Workspace(self.dev))
+        self._twg_stream = self._wgrad_stream     # the trunk's weight gradients (YOLO blocks, feature_map) go to that same stream
         self.lazy_bn1_bwd = True          # conv1's gradients read bn1's input gradient lazily (never materialised)
-        self.fused_frozen_bn = True       # bn_act_fwd on moving statistics: one launch instead of coefficients + apply
         self.fold_frozen_bn = True        # train=False forwards: that BatchNorm + ReLU6 in the epilogue of the depthwise / pointwise conv
         # training forwards of the trunk: every BatchNorm's batch statistics come out of the producing conv's epilogue and its apply +
         # ReLU6 happen on the consumer's load -- the normalised activations are never written (dw_block_fwd / dw_block_bwd)
         self.fuse_trunk_bn = bool(getattr(cfg, "FUSE_TRUNK_BN", True))
         self._fz_table = None
-        self.merge_conv1_bwd_transforms = True    # conv1's backward: the V and Q transforms of the lazily formed gradient from one pass over y_pre
         self.anchors = torch.tensor(np.asarray(cfg.ANCHORS, np.float32), device=self.dev)
         self.class_weights = torch.tensor(np.asarray(cfg.CLASS_WEIGHTS, np.float32), device=self.dev)
         self.adam_t = 0
@@ -284,28 +275,18 @@ class Net(object):
         self._copy_stream = _shared_stream(self.dev, "n_pos_copy")
         self._npos_ready = torch.cuda.Event()
         self._npos_pinned = None
-        self.fuse_bn_bwd_sums = 1         # trunk backward: the depthwise data gradient leaves the sums of the BatchNorm its output reaches (conv_pw_{b-1}_bn / conv1_bn) in its epilogue -- that BatchNorm's backward is finish + dx, its pass over (dy, x) is gone (round 5); 0 = three launches per BatchNorm
         self._bn_sums = {}                # BatchNorm name -> (partials, rows) left by the producer of its output gradient
         self._np_seen = None              # positives of the last step whose counts the host has read (sizes the next step's kept-rows buffer)
         self._keep_cap_hw = 0
-        self.fused_bn_bwd = 0             # 1 = training-mode BatchNorm backward in one launch (sums, grid-wide barrier, dx: myolo_bn_act_bwd_fused).  Measured: 28.7 against 20.9 ms per step -- the barrier needs all its workgroups resident, and this step runs its chains BESIDE chip-filling kernels of other streams on purpose (profiles/r4_notes.md section 6)
-        self._bn_sync = {}                # stream -> the barrier's counters
-        self._bn_fused_bytes = {}
         self.weight_prep = 1              # training step: weight-only re-layouts (transposes, bf16x6 splits, Winograd filter transforms) re-run on a side stream at the step's start instead of inside the chain (X.WeightPrep); 0 = in place (round 3)
         self._wprep = None
         self._wprep_calls, self._wprep_misses, self._wprep_cap = 0, None, 0      # (_wprep_begin: one warning if the arena turns out too small)
-        self.wprep_wait_late = 1          # 0: wait for the trunk's prepared weights right behind conv1 (A/B)
         self._wprep_ntrunk = None         # registry entries recorded before the mask head (their consumers are the trunk's first layers)
         self._wprep_ev = None
         self.seen = 0                     # evaluations of the YOLO loss so far (the reference's `seen`, see _yolo_warm)
-        self.keep_rows_compact = 1        # the rows the training forward keeps for the sparse backward (pre-BatchNorm outputs of conv2-4, bn1's activation) are written in compact order by the layer boundaries: no gathers in the backward chain; 0 = dense positions + gathers (round 3)
         self.keep_deconv_rows = 48        # training forward keeps the ReLU'd deconv output of up to this many positives PER IMAGE (batch total) for the sparse backward; 0 = re-run the deconv there (round 3); beyond the cap the backward re-runs it
-        self.fuse_compact_gather = 1      # compacted mask-head backward: gather + BatchNorm apply in one kernel, each pre-BN tensor gathered once (0: round 3's sequence)
-        self.bucket1_on_wgrad_stream = 1  # data-parallel: bucket 1 released on the weight-gradient stream (0: round 3's join of that stream into the compute stream)
-        self.pinned_upload = 1            # to_device_batch through pinned staging + the upload stream (0: synchronous torch.as_tensor copies, rounds 1-3)
-        self.upload_own_stream = 0        # EXPERIMENT
         self._stage_lock = threading.Lock()
-        self._stage = None                # to_device_batch: ring of pinned staging sets + upload stream (created on first use)
+        self._stage = None                # to_device_batch: ring of pinned staging sets (created on first use); uploads go on _copy_stream
         self._bind_cache = {}
         self.timed_tags = set()           # bench.py: kernel tags to bracket with HIP events
         self.timings = {}                 # tag -> [(start_event, end_event), ...]
@@ -392,10 +373,49 @@ class Net(object):
 
     @property
     def ws(self):
-        return self._ws_active
+        """the scratch buffer of the stream launches are issued on: the side's inside Net._on, else the compute stream's"""
+        if self._side is None:
+            return self._ws_main
+        if self._side.ws is None:
+            raise RuntimeError("myolo: a launch on a side stream without scratch asked for one")
+        return self._side.ws
 
     def _wsargs(self):
         return self.ws.ptr, self.ws.size
+
+    @contextlib.contextmanager
+    def _on(self, side, *tensors):
+        """run the block on `side`: behind everything queued so far on the current stream, with the side's scratch as self.ws (the previous
+        scratch is back on exit); `tensors` (or lazy references to them) are kept from the allocator until the side is done with them, and the
+        side is pending until a _join.  No host synchronisation."""
+        side.stream.wait_stream(torch.cuda.current_stream())
+        prev, self._side = self._side, side
+        try:
+            with torch.cuda.stream(side.stream):
+                yield
+        finally:
+            self._side = prev
+        for t in tensors:
+            t = t[1] if self._is_lazy(t) else t
+            t.record_stream(side.stream)
+        side.pending = True
+
+    def _join(self, side):
+        """make the current stream wait for a pending side"""
+        if side is not None and side.pending:
+            torch.cuda.current_stream().wait_stream(side.stream)
+            side.pending = False
+
+    def _release(self, bucket, side):
+        """hand `bucket` to the all-reduce hook: on `side` behind the current stream when the side is pending (its weight gradients may still be
+        running there; the current stream does not wait), else now"""
+        if not self.on_bucket_ready:
+            return
+        if side.pending:
+            with self._on(side):
+                self.on_bucket_ready(bucket)
+        else:
+            self.on_bucket_ready(bucket)
 
     def _call_timed(self, tag, name, *args):
         """X.call bracketed by HIP events on the launch stream when `tag` is being measured."""
@@ -433,7 +453,7 @@ class Net(object):
                    X.ptr(mean), X.ptr(var), X.ptr(scale), X.ptr(shift),
                    X.ptr(self.s[name + "/moving_mean"]), X.ptr(self.s[name + "/moving_variance"]),
                    M, C, *self._wsargs(), X.stream())
-        elif self.fused_frozen_bn and C % 4 == 0 and 256 % (C // 4) == 0:       # frozen BN: coefficients + apply + activation in one launch
+        elif C % 4 == 0 and 256 % (C // 4) == 0:       # frozen BN: coefficients + apply + activation in one launch
             a = self._new(M, C)
             X.call("myolo_bn_frozen_apply_act", X.ptr(y), X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]),
                    X.ptr(self.s[name + "/moving_mean"]), X.ptr(self.s[name + "/moving_variance"]), X.ptr(scale), X.ptr(shift), X.ptr(a),
@@ -467,19 +487,6 @@ class Net(object):
             X.call("myolo_bn_act_bwd_from_partials", X.ptr(da), X.ptr(y), X.ptr(mean), X.ptr(var), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(dx),
                    X.ptr(self.g[name + "/gamma"]), X.ptr(self.g[name + "/beta"]), M, C, act, X.ptr(part), rows, *self._wsargs(), X.stream())
             return dx
-        if batch_stats and self.fused_bn_bwd:
-            need = self._bn_fused_bytes.get((M, C))
-            if need is None:
-                need = self._bn_fused_bytes[(M, C)] = int(X.load().myolo_bn_act_bwd_fused_ws_bytes(M, C))
-            if need:
-                # one launch (sums, grid-wide barrier, dx) instead of three; the barrier's counters are private to the stream this runs on
-                sid = torch.cuda.current_stream().cuda_stream
-                sync = self._bn_sync.get(sid)
-                if sync is None:
-                    sync = self._bn_sync[sid] = torch.zeros(64, dtype=torch.int32, device=self.dev)
-                X.call("myolo_bn_act_bwd_fused", X.ptr(da), X.ptr(y), X.ptr(mean), X.ptr(var), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(dx),
-                       X.ptr(self.g[name + "/gamma"]), X.ptr(self.g[name + "/beta"]), M, C, act, X.ptr(sync), *self._wsargs(), X.stream())
-                return dx
         X.call("myolo_bn_act_bwd", X.ptr(da), X.ptr(y), X.ptr(self.p[name + "/gamma"]), X.ptr(mean), X.ptr(var),
                X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(dx), X.ptr(self.g[name + "/gamma"]), X.ptr(self.g[name + "/beta"]),
                M, C, act, 1 if batch_stats else 0, *self._wsargs(), X.stream())
@@ -679,52 +686,16 @@ class Net(object):
         self.tape["blk%d" % bid] = (a, shape, stride, ad)
         return ap, (N, Ho, Wo, Co)
 
-    @property
-    def _twg_stream(self):
-        if self._twg_override is not None:
-            return self._twg_override[0]
-        if self.single_wgrad_stream:
-            return self._wgrad_stream
-        if self._twg_stream_own_ is None:
-            self._twg_stream_own_ = _shared_stream(self.dev, "trunk_weight_gradients")
-        return self._twg_stream_own_
-
-    @property
-    def _ws_twg(self):
-        if self._twg_override is not None:
-            return self._twg_override[1]
-        return self._ws_wgrad if self.single_wgrad_stream else self._ws_twg_own
-
-    def _on_wgrad_stream(self, fn, tensors):
-        """run fn(ws_ptr, ws_size) -- a weight-gradient launch sequence whose inputs are complete on the current stream -- on the trunk's
-        weight-gradient stream (own scratch); `tensors` are kept from the allocator until that stream is done with them"""
-        if not self.overlap_trunk_wgrad:
-            return fn(*self._wsargs())
-        cur = torch.cuda.current_stream()
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        self._twg_stream.wait_event(ev)
-        with torch.cuda.stream(self._twg_stream):
-            fn(self._ws_twg.ptr, self._ws_twg.size)
-        for t in tensors:
-            if isinstance(t, tuple) and len(t) == 3 and t[0] == "lazy":       # ("lazy", pre-BN tensor, bn): the tensor inside is what the kernels read
-                t = t[1]
-            if torch.is_tensor(t):
-                t.record_stream(self._twg_stream)
-        self._twg_pending = True
-        self._twg_used.add(self._twg_stream)
-
     def join_trunk_wgrad(self):
-        """make the current stream wait for the trunk's weight-gradient stream"""
-        if self._twg_pending:
-            for st in self._twg_used:
-                torch.cuda.current_stream().wait_stream(st)
-            self._twg_used.clear()
-            self._twg_pending = False
+        """make the current stream wait for the trunk's weight gradients (the weight-gradient stream, and the YOLO-head stream that takes the
+        backbone's)"""
+        self._join(self._wgrad_side)
+        self._join(self._yolo_side)
 
-    def dw_block_bwd(self, bid, da, next_bn=None):
-        """next_bn: the training-mode BatchNorm this block's input gradient reaches next (conv_pw_{bid-1}_bn / conv1_bn); with
-        fuse_bn_bwd_sums the depthwise data gradient leaves that BatchNorm's backward sums in its epilogue (bn_act_bwd then finishes them)."""
+    def dw_block_bwd(self, bid, da, next_bn=None, wside=None):
+        """next_bn: the training-mode BatchNorm this block's input gradient reaches next (conv_pw_{bid-1}_bn / conv1_bn): the depthwise data
+        gradient leaves that BatchNorm's backward sums in its epilogue (bn_act_bwd then finishes them).  The weight gradients (no consumer but the
+        optimiser) run on `wside` (default: the weight-gradient stream), beside the data-gradient chain."""
         a, shape, stride, ad = self.tape["blk%d" % bid]
         N, H, W, C = shape
         Ho, Wo = H // stride, W // stride
@@ -732,28 +703,24 @@ class Net(object):
         Co = self.p[pwn + "/kernel"].shape[3]
         M = N * Ho * Wo
         dy2 = self.bn_act_bwd(pwn + "_bn", da)
-        # the scratch the weight gradients will really run on (their own stream's, or the main one without the overlap), sized for both of them
-        (self._ws_twg if self.overlap_trunk_wgrad else self.ws).ensure(max(X.workspace_bytes(M, C, Co), X.dw_bwd_weight_ws_bytes(N, H, W, C, stride)))
-
-        def pw_wgrad(wsp, wsz):
+        wside = wside or self._wgrad_side
+        wside.ws.ensure(max(X.workspace_bytes(M, C, Co), X.dw_bwd_weight_ws_bytes(N, H, W, C, stride)))      # sized for both weight gradients
+        with self._on(wside, dy2, ad):
             if self._is_lazy(ad):       # the forward normalised the depthwise output on load: so does the weight gradient
-                X.call("myolo_pwconv1x1_bwd_weight_affine_in", *self._in_args(ad), X.ptr(dy2), X.ptr(self.g[pwn + "/kernel"]), M, C, Co, wsp, wsz, X.stream())
+                X.call("myolo_pwconv1x1_bwd_weight_affine_in", *self._in_args(ad), X.ptr(dy2), X.ptr(self.g[pwn + "/kernel"]), M, C, Co, *self._wsargs(), X.stream())
             else:
-                X.call("myolo_pwconv1x1_bwd_weight", X.ptr(ad), X.ptr(dy2), X.ptr(self.g[pwn + "/kernel"]), M, C, Co, wsp, wsz, X.stream())
-        self._on_wgrad_stream(pw_wgrad, (dy2, ad))
+                X.call("myolo_pwconv1x1_bwd_weight", X.ptr(ad), X.ptr(dy2), X.ptr(self.g[pwn + "/kernel"]), M, C, Co, *self._wsargs(), X.stream())
         dad = self._new(M, C)
         X.call("myolo_pwconv1x1_bwd_data", X.ptr(dy2), X.ptr(self.p[pwn + "/kernel"]), X.ptr(dad), M, C, Co, *self._wsargs(), X.stream())
         dy = self.bn_act_bwd(dwn + "_bn", dad)
-
-        def dw_wgrad(wsp, wsz):
+        with self._on(wside, dy, a):
             if self._is_lazy(a):
-                X.call("myolo_dwconv3x3_bwd_weight_affine_in", *self._in_args(a), X.ptr(dy), X.ptr(self.g[dwn + "/depthwise_kernel"]), N, H, W, C, stride, wsp, wsz, X.stream())
+                X.call("myolo_dwconv3x3_bwd_weight_affine_in", *self._in_args(a), X.ptr(dy), X.ptr(self.g[dwn + "/depthwise_kernel"]), N, H, W, C, stride, *self._wsargs(), X.stream())
             else:
-                X.call("myolo_dwconv3x3_bwd_weight", X.ptr(a), X.ptr(dy), X.ptr(self.g[dwn + "/depthwise_kernel"]), N, H, W, C, stride, wsp, wsz, X.stream())
-        self._on_wgrad_stream(dw_wgrad, (dy, a))
+                X.call("myolo_dwconv3x3_bwd_weight", X.ptr(a), X.ptr(dy), X.ptr(self.g[dwn + "/depthwise_kernel"]), N, H, W, C, stride, *self._wsargs(), X.stream())
         dx = self._new(N * H * W, C)
         rows = 0
-        if next_bn is not None and self.fuse_bn_bwd_sums and next_bn in self.tape and self.tape[next_bn][2] and not self.fused_bn_bwd:
+        if next_bn is not None and next_bn in self.tape and self.tape[next_bn][2]:
             rows = X.dw_bwd_data_bnsums_rows(N, H, W, C, stride)
         if rows:
             yb, actb, _ = self.tape[next_bn]
@@ -798,7 +765,7 @@ class Net(object):
         waited = not train
         bid = 1
         for f, s in BACKBONE_BLOCKS:
-            if not waited and (shape[3] >= 128 or not self.wprep_wait_late):
+            if not waited and shape[3] >= 128:
                 self._wprep_wait(0)
                 waited = True
             a, shape = self.dw_block_fwd(bid, a, shape, s, train)
@@ -816,12 +783,15 @@ class Net(object):
         # 21.55 / 21.67 ms, nothing -- at batch 32 both branches fill the chip.  An inference forward at batch 4 is a chain of ~45 small launches:
         # there the conv's three kernels run beside the YOLO head's sixteen, infer_fork_feature_map.)
         fork = (not train) and (self.infer_fork_feature_map if self._fork_now is None else self._fork_now) and self._wino_ok(n, h, w, c, Cf)
+        fm = None
         if fork:
-            cur = torch.cuda.current_stream()
             if self._fm_stream is None:
                 self._fm_stream = _shared_stream(self.dev, "infer_feature_map")
-            self._fm_stream.wait_stream(cur)          # (inside a capture this pulls the side stream into the graph: the fork is a graph edge)
-            with torch.cuda.stream(self._fm_stream):  # the planes it allocates live and die in this stream's pool; Fm and C4 belong to `cur`
+            # no scratch: the Winograd forward uses none, and a launch that asks for one there raises instead of sharing the compute stream's.
+            # (inside a capture the fork and the join pull the side stream into the graph as edges; the planes the conv allocates live and die
+            # in the side stream's pool, Fm and C4 belong to the current stream)
+            fm = _Side(self._fm_stream, None)
+            with self._on(fm):
                 self.conv3x3_fwd(C4, "feature_map", Fm, n, h, w, c, Cf)
         else:
             self.conv3x3_fwd(C4, "feature_map", Fm, n, h, w, c, Cf)
@@ -835,8 +805,7 @@ class Net(object):
         X.call("myolo_pwconv1x1_fwd", X.ptr(a), X.ptr(self.p["conv_23/kernel"]), X.ptr(self.p["conv_23/bias"]), X.ptr(yo),
                n2 * h2 * w2, c2, D, *self._wsargs(), X.stream())
         self.tape["trunk"] = (C4, c4shape, a, shape)
-        if fork:
-            cur.wait_stream(self._fm_stream)         # Fm is complete for whatever the caller does next (detections, ROIAlign)
+        self._join(fm)                    # Fm is complete for whatever the caller does next (detections, ROIAlign)
         if train:
             self._wprep_mark_trunk()
             self._wprep_wait(1)           # everything else that was prepared (before any stream forks off this one)
@@ -864,36 +833,16 @@ class Net(object):
         """Launch yolo_head_bwd on the side stream (its own scratch buffer).  It depends only on the trunk forward and the YOLO
         loss, so it runs underneath the mask head's forward and backward; its small 7x7 / 14x14 kernels fill a fraction of the
         chip on their own.  trunk_bwd joins it before adding the two gradients of C4.  Same kernels, same results."""
-        cur = torch.cuda.current_stream()
-        self._yolo_stream.wait_stream(cur)
-        self._ws_active = self._ws_side
-        try:
-            with torch.cuda.stream(self._yolo_stream):
-                da = self.yolo_head_bwd(dyolo)
-                self._release_yolo_bucket()
-        finally:
-            self._ws_active = self._ws_main
+        with self._on(self._yolo_side):
+            da = self.yolo_head_bwd(dyolo)
+            self._release_yolo_bucket()
         self.tape["yolo_bwd"] = da
-
-    def _release_on_wgrad_stream(self, bucket, stream, pending):
-        """hand `bucket` to the all-reduce hook once the current stream AND `stream` (the one its weight gradients were queued on) have produced it:
-        on `stream`, behind an event of the current stream -- the current stream does not wait"""
-        if not self.on_bucket_ready:
-            return
-        if not pending:
-            self.on_bucket_ready(bucket)
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        stream.wait_event(ev)
-        with torch.cuda.stream(stream):
-            self.on_bucket_ready(bucket)
 
     def _release_yolo_bucket(self):
         """bucket 1 = YOLO blocks + conv_23: complete when the YOLO head's backward retires -- about half a step before the step ends when that
         backward runs on its side stream under the mask head (start_yolo_head_bwd).  Its data gradients and BatchNorm / conv_23 gradients are on the
-        current stream, the blocks' weight gradients on the trunk's weight-gradient stream."""
-        self._release_on_wgrad_stream(BUCKET_YOLO, self._twg_stream, self.overlap_trunk_wgrad and self._twg_pending)
+        current stream, the blocks' weight gradients on the weight-gradient stream."""
+        self._release(BUCKET_YOLO, self._wgrad_side)
 
     def trunk_bwd(self, dF, dyolo):
         C4, c4shape, a14, s14 = self.tape["trunk"]
@@ -905,9 +854,8 @@ class Net(object):
 
         def join():
             if started:
-                cur = torch.cuda.current_stream()
-                cur.wait_stream(self._yolo_stream)
-                da.record_stream(cur)
+                self._join(self._yolo_side)
+                da.record_stream(torch.cuda.current_stream())
         bid = len(BACKBONE_BLOCKS)
         n, h, w, c = c4shape
         if dF is None:
@@ -918,37 +866,22 @@ class Net(object):
             dC4 = da
         else:
             Cf = dF.shape[1]
-            def fm_wgrad(wsp, wsz):           # feature_map's weight and bias gradients: beside its data gradient and the backbone chain
-                prev, self._ws_active = self._ws_active, (self._ws_twg if self.overlap_trunk_wgrad else self._ws_active)
-                try:
-                    self.conv3x3_bwd_weight(C4, None, dF, "feature_map", n, h, w, c, Cf)
-                    self.colsum(dF, self.g["feature_map/bias"])
-                finally:
-                    self._ws_active = prev
-            self._on_wgrad_stream(fm_wgrad, (dF, C4))
+            with self._on(self._wgrad_side, dF, C4):     # feature_map's weight and bias gradients: beside its data gradient and the backbone chain
+                self.conv3x3_bwd_weight(C4, None, dF, "feature_map", n, h, w, c, Cf)
+                self.colsum(dF, self.g["feature_map/bias"])
             dC4 = self._new(n * h * w, c)
             self.conv3x3_bwd_data(dF, "feature_map", dC4, n, h, w, c, Cf)
             join()
             X.call("myolo_add_inplace", X.ptr(dC4), X.ptr(da), dC4.numel(), X.stream())
-        if self.on_bucket_ready:
-            # bucket 2 = feature_map: its weight gradient sits on the weight-gradient stream (or was zeroed on this one).  Released ON that
-            # stream, behind an event of the compute stream -- the compute stream itself does not wait (round 3 joined the whole
-            # weight-gradient stream here, conv1's 2.7 ms weight gradient included, in front of the backbone backward: +3 ms per step whenever
-            # a reducer was attached).
-            if self.bucket1_on_wgrad_stream and self.overlap_trunk_wgrad and self._twg_pending:
-                self._release_on_wgrad_stream(BUCKET_FEATURE_MAP, self._twg_stream, True)
-            else:
-                self.join_trunk_wgrad()
-                self.on_bucket_ready(BUCKET_FEATURE_MAP)
+        # bucket 2 = feature_map: its weight gradient sits on the weight-gradient stream (or was zeroed on this one).  Released ON that
+        # stream, behind an event of the compute stream -- the compute stream itself does not wait (round 3 joined the whole
+        # weight-gradient stream here, conv1's 2.7 ms weight gradient included, in front of the backbone backward: +3 ms per step whenever
+        # a reducer was attached).
+        self._release(BUCKET_FEATURE_MAP, self._wgrad_side)
         da = dC4
-        if self.backbone_wgrad_on_yolo_stream and self.overlap_trunk_wgrad and self.overlap_yolo_bwd:
-            self._twg_override = (self._yolo_stream, self._ws_side)
-        try:
-            for _ in BACKBONE_BLOCKS:
-                da = self.dw_block_bwd(bid, da, next_bn=("conv_pw_%d_bn" % (bid - 1)) if bid > 1 else "conv1_bn")
-                bid -= 1
-        finally:
-            self._twg_override = None
+        for _ in BACKBONE_BLOCKS:
+            da = self.dw_block_bwd(bid, da, next_bn=("conv_pw_%d_bn" % (bid - 1)) if bid > 1 else "conv1_bn", wside=self._yolo_side)
+            bid -= 1
         dy = self.bn_act_bwd("conv1_bn", da)
         images = self.tape["images"]
         N, H, W, _ = images.shape
@@ -994,7 +927,7 @@ class Net(object):
         if chain:
             # ROIAlign is fused into conv1's input transform: the [NR,14,14,256] crops are never written
             x = self._mask_convs_winograd_chain(None, convs, NR, ps, cf, train, pos_flags, roi=(Fm, boxes, bind, n, h, w),
-                                                slots=keep[0] if (keep is not None and self.keep_rows_compact) else None)
+                                                slots=keep[0] if keep is not None else None)
         else:
             x = self._new(NR * ps * ps, cf)
             self._call_timed("roialign_fwd", "myolo_crop_and_resize_fwd", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(x),
@@ -1089,7 +1022,7 @@ class Net(object):
                 self.tape[bn] = (None, ACT_RELU, False)       # pre-BN tensor never materialised
             if fold and i < 4 and use63 == next63:
                 ykeep = self._new(NR * q, MASK_FILTERS) if train else None
-                keep_pre = bool(train and self.mask_keep_pre)     # what is kept for the positive ROIs is the conv's PRE-BatchNorm output (exact backward, any gamma)
+                keep_pre = bool(train)            # what is kept for the positive ROIs is the conv's PRE-BatchNorm output (exact backward, any gamma)
                 if use63:
                     Vn = self._new(X.wino63_plane_elems(NR, MASK_FILTERS))
                     if keep_pre and slots is not None:
@@ -1118,7 +1051,7 @@ class Net(object):
             else:
                 y = self._new(NR * q, MASK_FILTERS)
                 if fold:
-                    if use63 and train and pos_flags is not None and self.mask_keep_pre:
+                    if use63 and train and pos_flags is not None:
                         ypre = self._new(NR * q, MASK_FILTERS)
                         if slots is not None:
                             X.call("myolo_wino63_output_transform_keep_pre_slots", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), X.ptr(ypre),
@@ -1134,7 +1067,7 @@ class Net(object):
                     else:
                         X.call("myolo_wino_output_transform", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), NR, ps, ps,
                                MASK_FILTERS, ACT_RELU, X.stream())
-                        if train and self.mask_keep_pre and self.sparse_mask_bwd:
+                        if train and self.sparse_mask_bwd:
                             # (the F(4,3)-tiling output transform has no flagged second output: a second pass writes the pre-BatchNorm rows of every ROI.
                             #  Non-default tiling; the F(6,3) boundary above writes the flagged ROIs' rows in the same pass)
                             ypre = self._new(NR * q, MASK_FILTERS)
@@ -1476,36 +1409,14 @@ class Net(object):
         # The compacted part is a chain of data gradients (deconv -> conv4 -> conv3 -> conv2 -> bn1's coefficients) that conv1's dense backward
         # waits for; the weight / bias gradients hanging off it have no consumer before the bucket's all-reduce.  They go to the stream (and
         # scratch) conv1's weight gradient uses later: queued in front of it, finished before the bucket is released there.
-        side_wg = bool(self.overlap_compact_wgrad and self.overlap_conv1_wgrad)
-
-        def off_chain(fn, tensors):
-            if not side_wg:
-                return fn()
-            cur = torch.cuda.current_stream()
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._wgrad_stream.wait_event(ev)
-            saved = self._ws_active
-            self._ws_active = self._ws_wgrad
-            try:
-                with torch.cuda.stream(self._wgrad_stream):
-                    fn()
-            finally:
-                self._ws_active = saved
-            for t in tensors:
-                t.record_stream(self._wgrad_stream)
-            self._wgrad_pending = True
-
         a4_w = self._new(NP * q, MASK_FILTERS) if a4_lazy else a4_p
-
-        def deconv_wgrad():
+        with self._on(self._wgrad_side, a4_w, dd, *((pre4,) if a4_lazy else ())):
             if a4_lazy:
                 b4 = self.bnbuf["myolo_mask_bn4"]
                 X.call("myolo_bn_apply_act", X.ptr(pre4), X.ptr(b4[2]), X.ptr(b4[3]), X.ptr(a4_w), NP * q, MASK_FILTERS, ACT_RELU, X.stream())
             X.call("myolo_deconv2x2s2_bwd_weight", X.ptr(a4_w), X.ptr(dd), X.ptr(self.g["myolo_mask_deconv/kernel"]), NP, ps, ps,
                    MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
             self.colsum(dd, self.g["myolo_mask_deconv/bias"])
-        off_chain(deconv_wgrad, (a4_w, dd) + ((pre4,) if a4_lazy else ()))
         da = self._new(NP * q, MASK_FILTERS)
         X.call("myolo_deconv2x2s2_bwd_data", X.ptr(dd), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(da), NP, ps, ps,
                MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
@@ -1513,23 +1424,21 @@ class Net(object):
         for i in range(4, 1, -1):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
             src = convs[i - 1]
-            lazy_xin = None
+            lazy_xin = False
             if isinstance(src, tuple) and not compact and id(src[1]) in kept:
                 # the forward kept this conv's input rows compact, as pre-BatchNorm values: the BatchNorm backward below reads them as they are, and the
                 # normalised form -- only this conv's WEIGHT gradient needs it -- is formed where that runs
                 _, ypre, bsrc = src
                 yp = ypre[:NP * q]
                 xin = self._new(NP * q, MASK_FILTERS)
-                def lazy_xin(xin=xin, yp=yp, bsrc=bsrc):
-                    X.call("myolo_bn_apply_act", X.ptr(yp), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), X.ptr(xin), NP * q, MASK_FILTERS,
-                           ACT_RELU, X.stream())
+                lazy_xin = True
                 pre_rows[id(ypre)] = yp
             elif isinstance(src, tuple) and not compact and src[2] == "myolo_mask_bn1" and "conv2_in_rows" in self.tape:
                 xin = self.tape["conv2_in_rows"][:NP * q]          # bn1's activation of the positives, written compact by conv2's input transform
             elif isinstance(src, tuple):      # ("lazy_bn", pre-BN tensor, bn layer): the forward normalised on load
                 _, ypre, bsrc = src
                 xin = self._new(NP * q, MASK_FILTERS)
-                if compact or not self.fuse_compact_gather:
+                if compact:
                     yp = gather(ypre, q)
                     X.call("myolo_bn_apply_act", X.ptr(yp), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), X.ptr(xin), NP * q,
                            MASK_FILTERS, ACT_RELU, X.stream())
@@ -1551,24 +1460,23 @@ class Net(object):
                        X.ptr(buf[2]), X.ptr(dy), X.ptr(self.g[bn + "/gamma"]), X.ptr(self.g[bn + "/beta"]), NP * q, MASK_FILTERS,
                        self.tape[bn][1], *self._wsargs(), X.stream())
             else:
-                c_p = pre_rows.get(id(self.tape[bn][0])) if self.fuse_compact_gather else None
+                c_p = pre_rows.get(id(self.tape[bn][0]))
                 if c_p is None:
                     c_p = gather(self.tape[bn][0], q)          # (a view when the forward kept these rows compact)
                 dy = self.bn_act_bwd(bn, da, y_override=c_p)
             a_next = xin                  # conv_i's input = post-activation of layer i-1
-            def conv_wgrad(xin=xin, dy=dy, cn=cn, lazy_xin=lazy_xin):
-                if lazy_xin is not None:
-                    lazy_xin()
+            with self._on(self._wgrad_side, xin, dy, *((src[1],) if lazy_xin else ())):
+                if lazy_xin:
+                    X.call("myolo_bn_apply_act", X.ptr(yp), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), X.ptr(xin), NP * q, MASK_FILTERS,
+                           ACT_RELU, X.stream())
                 self.conv3x3_bwd_weight(xin, None, dy, cn, NP, ps, ps, MASK_FILTERS, MASK_FILTERS)
                 self.colsum(dy, self.g[cn + "/bias"])
-            off_chain(conv_wgrad, (xin, dy) + ((src[1],) if lazy_xin is not None else ()))
             da = self._new(NP * q, MASK_FILTERS)
             self.conv3x3_bwd_data(dy, cn, da, NP, ps, ps, MASK_FILTERS, MASK_FILTERS)
         # bucket 4 (conv2-4, bn2-4, deconv, myolo_mask) is complete: its data-path gradients on this stream, the weight gradients hanging off the
         # compact chain on the side stream -- in FRONT of conv1's dense weight gradient, i.e. several milliseconds before the step ends
-        self._release_on_wgrad_stream(BUCKET_MASK_REST, self._wgrad_stream, side_wg and self._wgrad_pending)
+        self._release(BUCKET_MASK_REST, self._wgrad_side)
         # bn1: batch statistics -> dense dx from the row-sparse upstream gradient
-        released = [False]                      # conv1's bucket handed to the all-reduce hook on the side stream (fork_wgrad)
         c1, act, _ = self.tape["myolo_mask_bn1"]
         buf = self.bnbuf["myolo_mask_bn1"]
         M1 = NR * q
@@ -1576,7 +1484,8 @@ class Net(object):
         cin = cf
         v1 = self.tape.pop("conv1_V", None)
         dp0 = self._new(M1, cin)
-        if self.lazy_bn1_bwd and v1 is not None and self._wino_ok(NR, ps, ps, MASK_FILTERS, cin):
+        lazy1 = self.lazy_bn1_bwd and v1 is not None and self._wino_ok(NR, ps, ps, MASK_FILTERS, cin)
+        if lazy1:
             # dc1 = d loss / d conv1-output is dense (batch statistics spread the gradient over every ROI) but it is an affine
             # function of conv1's output outside the positive ROIs: conv1's two gradients form it while loading that output
             # (Winograd transforms with a lazy operand) and it is never written.  Its column sums -- conv1's bias gradient --
@@ -1589,52 +1498,34 @@ class Net(object):
             self.g["myolo_mask_conv1/bias"].zero_()
             v63 = self.tape.pop("conv1_V_fmt", "f43") == "f63"      # the layout the forward left conv1's V planes in
             d63 = self.wino_tiles == "f63" and X.wino63_ok(ps, ps, MASK_FILTERS, cin)
-            merged = v63 and d63 and self.merge_conv1_bwd_transforms
+            # (the forward takes the F(6,3) layout for conv1 only where the data gradient has its F(6,3) kernels too: v63 implies d63)
+            merged = v63 and d63
             if merged:
                 # ONE pass over conv1's output forms the lazily built gradient tile and sends it out both ways: V (data gradient) and Q
                 # (weight gradient); the two gradients then finish on their own streams
                 pe = X.wino63_plane_elems(NR, MASK_FILTERS)
                 Vd, Qd = self._new(pe), self._new(pe)
                 X.call("myolo_wino63_lazybn_transforms", *lazy, X.ptr(Vd), X.ptr(Qd), NR, MASK_FILTERS, X.stream())
-
-            def conv1_wgrad(wsp, wsz):
+            # conv1's weight gradient on the weight-gradient stream, behind the compacted chain's; bn1's gradients (this bucket's other members)
+            # are complete here, so the bucket is released there, behind that kernel
+            self._wgrad_side.ws.ensure(X.wino63_bwd_weight_from_q_ws_bytes(NR, cin, MASK_FILTERS) if merged else
+                                       X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 2))
+            with self._on(self._wgrad_side, v1, c1, da, inv_d, kab, *((Qd,) if merged else ())):
                 if merged:
                     X.call("myolo_wino63_bwd_weight_from_q", X.ptr(v1), X.ptr(Qd), X.ptr(self.g["myolo_mask_conv1/kernel"]), NR, cin, MASK_FILTERS,
-                           wsp, wsz, X.stream())
+                           *self._wsargs(), X.stream())
                 elif v63:
-                    X.call("myolo_wino63_bwd_weight_lazybn", X.ptr(v1), *lazy, X.ptr(self.g["myolo_mask_conv1/kernel"]), NR, cin, MASK_FILTERS,
-                           wsp, wsz, X.stream())
+                    raise AssertionError("conv1's V planes in the F(6,3) layout without the F(6,3) data-gradient kernels")
                 else:
                     X.call("myolo_conv3x3_wino_bwd_weight_lazybn", X.ptr(v1), *lazy, X.ptr(self.g["myolo_mask_conv1/kernel"]), NR, ps, ps,
-                           cin, MASK_FILTERS, wsp, wsz, X.stream())
-            wg_bytes = (X.wino63_bwd_weight_from_q_ws_bytes(NR, cin, MASK_FILTERS) if merged else
-                        X.wino63_bwd_weight_ws_bytes(NR, cin, MASK_FILTERS) if v63 else X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 2))
-            def fork_wgrad():
-                released[0] = bool(self.on_bucket_ready)
-                self._ws_wgrad.ensure(wg_bytes)
-                cur = torch.cuda.current_stream()
-                self._wgrad_stream.wait_stream(cur)
-                with torch.cuda.stream(self._wgrad_stream):
-                    conv1_wgrad(self._ws_wgrad.ptr, self._ws_wgrad.size)
-                    if self.on_bucket_ready:          # bn1's gradients (this bucket's other members) were complete at the fork
-                        self.on_bucket_ready(BUCKET_MASK_CONV1)
-                for t in (v1, c1, da, inv_d, kab) + ((Qd,) if merged else ()):
-                    t.record_stream(self._wgrad_stream)
-                self._wgrad_pending = True
-            late = bool(self.conv1_wgrad_after_dgrad) and merged
-            if self.overlap_conv1_wgrad:
-                if not late:
-                    fork_wgrad()
-                self.ws.ensure(X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 1))
-            else:
-                self.ws.ensure(max(X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 1), wg_bytes))
-                conv1_wgrad(*self._wsargs())
+                           cin, MASK_FILTERS, *self._wsargs(), X.stream())
+                if self.on_bucket_ready:
+                    self.on_bucket_ready(BUCKET_MASK_CONV1)
+            self.ws.ensure(X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 1))
             if merged:
                 self.ws.ensure(X.wino63_bwd_data_from_v_ws_bytes(NR, cin, MASK_FILTERS))
                 X.call("myolo_wino63_bwd_data_from_v", X.ptr(Vd), X.ptr(self.p["myolo_mask_conv1/kernel"]), X.ptr(dp0), NR, cin, MASK_FILTERS,
                        *self._wsargs(), X.stream())
-                if self.overlap_conv1_wgrad and late:
-                    fork_wgrad()          # behind the data gradient: runs beside ROIAlign's backward and the trunk's backward
             elif d63:
                 self.ws.ensure(X.wino63_bwd_data_ws_bytes(NR, cin, MASK_FILTERS))
                 X.call("myolo_wino63_bwd_data_lazybn", *lazy, X.ptr(self.p["myolo_mask_conv1/kernel"]), X.ptr(dp0), NR, cin, MASK_FILTERS,
@@ -1652,33 +1543,23 @@ class Net(object):
             self.conv3x3_bwd_data(dc1, "myolo_mask_conv1", dp0, NR, ps, ps, cin, MASK_FILTERS)
         dF = self._new(n * h * w, cf)
         X.call("myolo_roialign_bwd_grouped", X.ptr(dp0), X.ptr(boxes), X.ptr(dF), n, h, w, cf, NR // n, ps, ps, X.stream())
-        if self.on_bucket_ready and not released[0]:
-            self.join_conv1_wgrad()       # the compacted weight gradients on the side stream, if any
-            self.on_bucket_ready(BUCKET_MASK_CONV1)       # (otherwise the bucket was released on the weight gradient's stream, behind that kernel)
+        if self.on_bucket_ready and not lazy1:
+            self.join_conv1_wgrad()       # the compacted weight gradients on the side stream
+            self.on_bucket_ready(BUCKET_MASK_CONV1)       # (with lazy1 the bucket was released on the weight gradient's stream, behind that kernel)
         return dF
 
     def join_conv1_wgrad(self):
-        """make the current stream wait for conv1's weight gradient (side stream)."""
-        if self._wgrad_pending:
-            torch.cuda.current_stream().wait_stream(self._wgrad_stream)
-            self._wgrad_pending = False
+        """make the current stream wait for the weight-gradient stream (conv1's and the compacted chain's weight gradients)."""
+        self._join(self._wgrad_side)
 
     # ------------------------------------------------------------------ steps
     def to_device_batch(self, batch):
         """host batch (the six arrays of model.py:896-897, or the three of 'yolo' mode, myolo_utils.py:849-851) -> device
         tensors in C-ABI dtypes.  Upload path: each array is converted into a PINNED staging buffer (a ring of
         `_STAGE_SETS` sets, so a prefetching caller can stage batch i+1 while batch i's copies are in flight) and copied
-        with an asynchronous H2D on the engine's upload stream into FRESH device tensors; the dict carries the event
+        with an asynchronous H2D on the engine's copy stream into FRESH device tensors; the dict carries the event
         (`_ready`) that the consuming step makes its stream wait on (`_await_batch`).  Nothing here blocks the host except
         re-use of a staging set whose previous copy is still running."""
-        dev = self.dev
-        T = self.cfg.TRUE_BOX_BUFFER
-        if not self.pinned_upload:
-            keys = ("images", "true_boxes", "y_true", "gt_ids", "gt_boxes", "gt_masks")[:len(batch)]
-            dts = dict(images=np.float32, true_boxes=np.float32, y_true=np.float32, gt_ids=np.int32, gt_boxes=np.int32, gt_masks=np.uint8)
-            out = {k: torch.as_tensor(np.ascontiguousarray(np.asarray(a).reshape(-1, T, 4) if k == "true_boxes" else a, dts[k]), device=dev)
-                   for k, a in zip(keys, batch)}
-            return out
         n = int(np.asarray(batch[0]).shape[0])
 
         def fill(arrays):
@@ -1702,7 +1583,6 @@ class Net(object):
             if self._stage is None:
                 self._stage = [dict(bufs={}, ev=None, busy=threading.Lock()) for _ in range(self._STAGE_SETS)]
                 self._stage_i = 0
-                self._upload_stream = _shared_stream(dev, "batch_upload") if self.upload_own_stream else self._copy_stream
             # a staging set belongs to ONE caller from here until its upload has been queued and its event recorded (`busy`): MaskYOLO.train()'s
             # prefetch thread and the main thread's validation batches go through this ring at the same time.  First set in ring order
             # that nobody is filling; if every set is taken, queue for the next one in order.
@@ -1732,7 +1612,7 @@ class Net(object):
                 arrays.append(pin.numpy())
             fill(arrays)
             out = {}
-            with torch.cuda.stream(self._upload_stream):
+            with torch.cuda.stream(self._copy_stream):
                 for key, shape, dt in spec:
                     t = torch.empty(shape, dtype=dt, device=dev)
                     t.copy_(st["bufs"][(key, shape, dt)], non_blocking=True)
@@ -1743,7 +1623,7 @@ class Net(object):
                     X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(out["images"]), raw.numel(), X.stream())
                     out["_raw_images"] = raw              # (kept until the conversion has run)
                 ev = torch.cuda.Event()
-                ev.record(self._upload_stream)
+                ev.record(self._copy_stream)
                 st["ev"] = ev
             out["_ready"] = ev
         finally:
@@ -1793,15 +1673,13 @@ class Net(object):
         n = wp.count()
         if n:
             # every preparation recorded so far, in the order the step first asked for them, on the weight-gradient stream (idle here: the optimizer
-            # joined it), under the first layers of the forward.  Two marks: the trunk's entries, everything.
-            cur = torch.cuda.current_stream()
-            side = self._wgrad_stream
-            side.wait_stream(cur)                 # behind the optimizer's update of the weights
+            # joined it), under the first layers of the forward, behind the optimizer's update of the weights.  Two marks: the trunk's entries,
+            # everything.
             nt = min(self._wprep_ntrunk if self._wprep_ntrunk is not None else n, n)
             ev1 = torch.cuda.Event()
-            with torch.cuda.stream(side):
+            with self._on(self._wgrad_side):
                 wp.refresh(0, nt)
-                ev1.record(side)
+                ev1.record()
             self._wprep_ev = [ev1, None]
             self._wprep_rest = (nt, n)            # launched by _wprep_phase2, once the big early layers of the trunk are through
         wp.activate(True)
@@ -1829,15 +1707,10 @@ class Net(object):
         if rest is None or self._wprep_ev is None:
             return
         self._wprep_rest = None
-        cur = torch.cuda.current_stream()
-        side = self._wgrad_stream
-        evm = torch.cuda.Event()
-        evm.record(cur)
-        side.wait_event(evm)
         ev2 = torch.cuda.Event()
-        with torch.cuda.stream(side):
+        with self._on(self._wgrad_side):
             self._wprep.refresh(rest[0], rest[1])
-            ev2.record(side)
+            ev2.record()
         self._wprep_ev[1] = ev2
 
     def _wprep_wait(self, k):
@@ -1909,22 +1782,14 @@ class Net(object):
             X.call("myolo_yolo_loss_warmup", X.ptr(db["y_true"]), X.ptr(yo), X.ptr(db["true_boxes"]), X.ptr(self.anchors),
                    X.ptr(self.class_weights), float(cfg.OBJECT_SCALE), float(cfg.NO_OBJECT_SCALE), float(cfg.COORD_SCALE),
                    float(cfg.CLASS_SCALE), w1, warm, X.ptr(yterms), X.ptr(dyolo), B, G, A, C, T, *self._wsargs(), X.stream())
-        if self.overlap_yolo_bwd:
-            # the loss kernel (one workgroup row per image, ~0.17 ms) only feeds the YOLO head's backward, which runs on the side stream:
-            # launch it there too (side scratch buffer), under the mask head's forward, instead of in front of it
-            self._yolo_stream.wait_stream(torch.cuda.current_stream())
-            self._ws_active = self._ws_side
-            try:
-                with torch.cuda.stream(self._yolo_stream):
-                    yolo_loss()
-            finally:
-                self._ws_active = self._ws_main
-        else:
+        # the loss kernel (one workgroup row per image, ~0.17 ms) only feeds the YOLO head's backward, which runs on the side stream:
+        # launch it there too (side scratch buffer), under the mask head's forward, instead of in front of it
+        with self._on(self._yolo_side):
             yolo_loss()
         # (a tape_hook rewrites saved tensors between forward and backward -- tests force the oracle's activations there: the YOLO head's backward must
         # not have read them before the hook runs, so it then starts at the old place)
         want_early = self.exchange_active if self.yolo_bwd_early < 0 else bool(self.yolo_bwd_early)
-        early = bool(self.overlap_yolo_bwd and want_early and not self.tape_hook)
+        early = bool(want_early and not self.tape_hook)
         if early:
             self.start_yolo_head_bwd(dyolo)
         if self.sparse_mask_fwd:
@@ -1969,7 +1834,7 @@ class Net(object):
                    *self._wsargs(), X.stream())
         if self.tape_hook:
             self.tape_hook(self)
-        if self.overlap_yolo_bwd and not early:
+        if not early:
             # under the compacted part of the mask head's backward (small launches on the positive ROIs), not under the big
             # forward GEMMs: two streams of small kernels fill the chip together, and the dense kernels keep it to themselves
             self.start_yolo_head_bwd(dyolo)
@@ -2231,8 +2096,8 @@ class Net(object):
             self._fork_now = fork
             if lane > 0:
                 st = self._lane_state(lane)
-                saved = (self._ws_main, self._ws_active, self.bnbuf, self._fz_coeffs)
-                self._ws_main = self._ws_active = st["ws"]
+                saved = (self._ws_main, self.bnbuf, self._fz_coeffs)
+                self._ws_main = st["ws"]
                 self.bnbuf, self._fz_coeffs = st["bnbuf"], st["fz"]
             try:
                 if ent is None:
@@ -2243,7 +2108,7 @@ class Net(object):
             finally:
                 self._fork_now = None
                 if saved is not None:
-                    self._ws_main, self._ws_active, self.bnbuf, self._fz_coeffs = saved
+                    self._ws_main, self.bnbuf, self._fz_coeffs = saved
         graph, static_in, outs = ent
         self._infer_prep_sync()                  # the graph reads the cached weight preparations: re-made here (eagerly) when the weights changed
         static_in.copy_(images)

@@ -915,6 +915,7 @@ def test_side_streams_are_shared_by_every_net_of_the_process():
     """engine._shared_stream: the side streams exist once per device (a later Net's fresh streams could land on the compute stream's hardware
     queue, profiles/r3_notes.md "hardware queues"), and two Nets used alternately still produce what each produces alone."""
     import os
+    from myolo import engine
     from myolo.engine import Net
     assert os.environ.get("GPU_MAX_HW_QUEUES"), "set by tests/conftest.py for the session; the product sets it at the first Net when HIP is not up yet"
     cfg = make_config(ShapesConfig, IMAGE_SHAPE=[128, 128, 3], ALPHA=0.5, BATCH_SIZE=2)
@@ -922,6 +923,7 @@ def test_side_streams_are_shared_by_every_net_of_the_process():
     for name in ("_yolo_stream", "_wgrad_stream", "_copy_stream"):
         assert getattr(a, name) is getattr(b, name), name
     assert a._twg_stream is a._wgrad_stream                       # one weight-gradient stream
+    streams = set(engine._SHARED_STREAMS)
     samples = make_shapes_samples(2, cfg)
     batch, _ = BatchGenerator(samples, cfg, 'training', shuffle=False, norm=True)[0]
     da, db = a.to_device_batch(batch), b.to_device_batch(batch)
@@ -933,6 +935,8 @@ def test_side_streams_are_shared_by_every_net_of_the_process():
     b.forward_backward(db)                                       # interleaved on the shared streams
     ga2, gb2 = a.grads_dict(), b.grads_dict()
     assert all(np.array_equal(ga[k], ga2[k]) for k in ga) and all(np.array_equal(gb[k], gb2[k]) for k in gb)
+    # one weight-gradient stream: the uploads and the training steps create no side stream of their own
+    assert set(engine._SHARED_STREAMS) == streams and ("cuda:0", "trunk_weight_gradients") not in streams
 
 
 def test_inference_folded_frozen_bn_equals_unfolded():
