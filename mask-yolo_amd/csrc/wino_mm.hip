@@ -1134,6 +1134,9 @@ int myolo_matmul_f32_impl(const float* A, const float* B, float* C, int64_t M, i
     R.rows = M; R.a_off = 0; R.b_off = 0; R.c_off = 0; R.nq = 1; R.tile0 = 0;
     R.mtiles = (int)((M + MM_BM - 1) / MM_BM);
     const long long tiles = (long long)R.mtiles * (N / MM_BN);
+#ifdef MM_X6_TUNE
+    a.tune = g_myolo_opt.tune0;
+#endif
     if (products == MYOLO_PRODUCTS_BF16X6) {
         const long long total = (long long)K * N;
         if (b_is_weight) a.Bt = x6_split_weights(B, ws, K, N, b_is_nk ? 0 : 1, s);
@@ -1536,6 +1539,9 @@ int myolo_deconv_x6_fwd(const float* x, const float* w, const float* bias, float
     const int K = Cin, N = 4 * Co;
     MMArgs a{};
     a.A = x; a.C = y; a.K = K; a.N = N; a.nruns = 1; a.bias = bias; a.H = H; a.W = W; a.Co = Co; a.a_act = act;
+#ifdef MM_X6_TUNE
+    a.tune = g_myolo_opt.tune0;
+#endif
     MMRun& R = a.run[0];
     R.rows = M; R.nq = 1; R.mtiles = (int)((M + MM_BM - 1) / MM_BM);
     a.Bt = x6_split_weights(w, split, K, N, 0, s);     // w = [N][K]
@@ -1547,6 +1553,9 @@ int myolo_deconv_x6_bwd_data(const float* dy, const float* w, float* dx, long lo
     const int K = 4 * Co, N = Cin;
     MMArgs a{};
     a.A = dy; a.C = dx; a.K = K; a.N = N; a.nruns = 1; a.H = H; a.W = W; a.Co = Co;
+#ifdef MM_X6_TUNE
+    a.tune = g_myolo_opt.tune0;
+#endif
     MMRun& R = a.run[0];
     R.rows = M; R.nq = 1; R.mtiles = (int)((M + MM_BM - 1) / MM_BM);
     a.Bt = x6_split_weights(w, split, K, N, 1, s);     // w = [K = (tap, co)][N = ci]
