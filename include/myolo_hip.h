@@ -233,10 +233,11 @@ int myolo_shapes_batch(const int32_t* spec, int spec_stride, const double* ancho
 int myolo_unmold_masks(const float* masks, const float* detections, uint8_t* full_masks,
                        int N, int mh, int mw, int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- final mask conv 1x1 + bias + sigmoid (myolo_mask model.py:713-714), C small ---- */
+/* ---- final mask conv 1x1 + bias + sigmoid (myolo_mask model.py:713-714), any C >= 1 (C > 8: fp32 matrix pipe, Cin % 8 == 0) ---- */
 int myolo_mask_head_out_fwd(const float* x, const float* w, const float* bias, float* p,
                             int64_t M, int Cin, int C, void* stream);
-/* backward of the above given dz [M,C] (gradient wrt the pre-sigmoid logits):
+/* backward of the above given dz [M,C] (gradient wrt the pre-sigmoid logits), 1 <= C <= 8 (any C from the selected channel's gradient:
+ * myolo_mask_head_out_bwd_sel, include/myolo_hip_internal.h):
  * dx[M,Cin] = (dz w^T) * (x > 0)   (ReLU of the deconv output folded in), dw[Cin,C], db[C]. */
 int myolo_mask_head_out_bwd(const float* x, const float* w, const float* dz, float* dx, float* dw, float* db,
                             int64_t M, int Cin, int C, void* ws, size_t ws_bytes, void* stream);

@@ -232,6 +232,20 @@ int myolo_pwconv1x1_bnstats_fwd(const float* x, const float* in_scale, const flo
 int myolo_pwconv1x1_bwd_weight_affine_in(const float* x, const float* in_scale, const float* in_shift, int in_act, const float* dy, float* dw,
                                          int64_t M, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the mask loss and the mask conv 1x1's backward for any class count (myolo_mask_loss_graph model.py:718-754 reads one channel per ROI:
+ * class_id of a positive ROI), myolo_mask_head_out_bwd's dense dz [M,C] being limited to C <= 8.
+ * mask_bce_sel: myolo_mask_bce's inputs and loss_out (bit-identical loss) but only the gradient of the selected channel,
+ *   dz_sel [NR*h*w] = dz[r, ids[r / (h*w)]] (0 for a ROI whose id is not in 1..C-1).  ws: as myolo_mask_bce.
+ * mask_head_out_bwd_sel: x [M,Cin] (the ReLU'd deconv output), w [Cin,C], dz_sel [M], ids [M/hw] (class per ROI of hw rows):
+ *   dx[r,c] = (x[r,c] > 0) ? dz_sel[r] * w[c, ids[r/hw]] : 0 (bit-identical to myolo_mask_head_out_bwd on the one-hot dz);
+ *   dw[Cin,C], db[C] = sums over the rows of the ROIs of each class, in doubles, ROI order: every column is written, a class
+ *   without a ROI gets zeros.  Needs Cin / 4 dividing 256.  ws: myolo_mask_head_out_bwd_sel_ws_bytes(M/hw, Cin). ---- */
+int myolo_mask_bce_sel(const float* target_masks, const int32_t* target_class_ids, const float* pred, float loss_weight,
+                       float* loss_out, float* dz_sel, int NR, int h, int w, int C, void* ws, size_t ws_bytes, void* stream);
+size_t myolo_mask_head_out_bwd_sel_ws_bytes(int NR, int Cin);
+int myolo_mask_head_out_bwd_sel(const float* x, const float* w, const float* dz_sel, const int32_t* ids, float* dx, float* dw, float* db,
+                                int64_t M, int Cin, int C, int hw, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- HBM stream-copy microbenchmark (the measured copy bandwidth printed beside the nominal 8 TB/s): dst = src over
  * nbytes (multiple of 16), hand-written float4 kernel, 4 loads in flight per thread.  variant 0 default cache policy, 1 non-temporal
  * stores, 2 non-temporal loads + stores, 3 read only, 4 write only; blocks <= 0: 8 workgroups per CU. ---- */

@@ -1253,6 +1253,98 @@ __global__ __launch_bounds__(256) void mask_out_bf16_kernel(const uint16_t* __re
     }
 }
 
+// the same product for C > 8 classes on the bf16 matrix pipe (mask_out_mfma_kernel of mem_kernels.hip on v_mfma_f32_32x32x16_bf16):
+// a wave owns 32 rows and a group of 32 NU class columns; lane (row l31, half h) loads 8 bf16 of its row per step (k = 16 s + 8 h .. + 7)
+// and the matching 8 of w^T's row n from LDS, where w is rounded to bf16 (as the fused deconv + mask path does) and padded with zero
+// columns; rows padded to Cin + 8 bf16.  fp32 accumulation in a fixed order, bias + sigmoid on the way out, only valid columns stored.
+#define MASK_BF16_THREADS 512
+template <int NU>
+__global__ __launch_bounds__(MASK_BF16_THREADS) void mask_out_bf16_mfma_kernel(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                                               const float* __restrict__ bias, float* __restrict__ p, long long M,
+                                                                               int Cin, int C)
+{
+    extern __shared__ __align__(16) uint16_t mob_lds[];          // [32 NU][Cin + 8]
+    constexpr int NN = 32 * NU;
+    const int ldw = Cin + 8;
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
+    const int c0 = blockIdx.y * NN;
+    for (int e = tid; e < NN * Cin; e += MASK_BF16_THREADS) {
+        const int k = e / NN, n = e - k * NN;
+        mob_lds[n * ldw + k] = c0 + n < C ? f2bf(w[(long long)k * C + c0 + n]) : (uint16_t)0;
+    }
+    float bl[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) bl[u] = c0 + 32 * u + l31 < C ? bias[c0 + 32 * u + l31] : 0.f;
+    __syncthreads();
+    const long long nblk = (M + 31) / 32;
+    constexpr int WPB = MASK_BF16_THREADS / 64;
+    const long long nwave = (long long)gridDim.x * WPB;
+    const uint16_t* wb = mob_lds + l31 * ldw + 8 * half;
+    const int ns = Cin / 16;
+    for (long long blk = (long long)blockIdx.x * WPB + (tid >> 6); blk < nblk; blk += nwave) {
+        const long long row = blk * 32 + l31;
+        const uint16_t* ap = x + (row < M ? row : M - 1) * Cin + 8 * half;
+        f32x16 acc[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+#pragma unroll 4
+        for (int st = 0; st < ns; ++st) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + 16 * st);
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const bf16x8 b = *reinterpret_cast<const bf16x8*>(wb + u * 32 * ldw + 16 * st);
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[u], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long long orow = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (orow < M) {
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    const int col = c0 + 32 * u + l31;
+                    if (col < C) {
+                        float s = acc[u][r];
+                        s += bl[u];
+                        p[orow * C + col] = 1.f / (1.f + expf(-s));
+                    }
+                }
+            }
+        }
+    }
+}
+
+#define MASK_BF16_LDS_MAX (160 * 1024)
+static int mask_bf16_cu_count()
+{
+    static int n = 0;
+    if (!n) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        n = v;
+    }
+    return n;
+}
+template <int NU>
+static void mask_out_bf16_mfma_launch(const uint16_t* x, const float* w, const float* bias, float* p, long long M, int Cin, int C, hipStream_t s)
+{
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)mask_out_bf16_mfma_kernel<NU>, hipFuncAttributeMaxDynamicSharedMemorySize, MASK_BF16_LDS_MAX);
+        attr_set = true;
+    }
+    const size_t lds = (size_t)32 * NU * (Cin + 8) * sizeof(uint16_t);
+    const int groups = (C + 32 * NU - 1) / (32 * NU);
+    long long wgs = (long long)mask_bf16_cu_count() * (int)(MASK_BF16_LDS_MAX / lds);
+    const long long need = ((M + 31) / 32 + MASK_BF16_THREADS / 64 - 1) / (MASK_BF16_THREADS / 64);
+    if (wgs > need) wgs = need;
+    if (wgs < 1) wgs = 1;
+    hipLaunchKernelGGL((mask_out_bf16_mfma_kernel<NU>), dim3((unsigned)wgs, (unsigned)groups), dim3(MASK_BF16_THREADS), lds, s, x, w, bias, p,
+                       M, Cin, C);
+}
+
 
 // weight packing: fp32 [K][N] (HWIO flattened) or [N][K] -> bf16 [N][K], with the frozen BatchNorm that follows
 // the conv folded in:  w'[n,k] = w[k,n] * g[n],  b'[n] = b[n] * g[n] + beta[n] - mean[n] * g[n],  g = gamma / sqrt(var + eps)
@@ -1380,8 +1472,22 @@ int myolo_crop_and_resize_bf16_fwd(const float* image, const float* boxes, const
 
 int myolo_mask_head_out_bf16_fwd(const uint16_t* x, const float* w, const float* bias, float* p, int64_t M, int Cin, int C, void* stream)
 {
-    MYOLO_REQUIRE(x && w && bias && p && M > 0 && (Cin & 3) == 0 && C >= 1 && C <= 8, "mask_head_out_bf16_fwd: bad arguments (1<=C<=8)");
+    MYOLO_REQUIRE(x && w && bias && p && M > 0 && (Cin & 3) == 0 && C >= 1, "mask_head_out_bf16_fwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    if (C > 8) {                  // the matrix-pipe kernel
+        int nu = (C + 31) / 32;
+        if (nu > 4) nu = 4;
+        while (nu > 0 && (size_t)32 * nu * (Cin + 8) * sizeof(uint16_t) > MASK_BF16_LDS_MAX) --nu;
+        MYOLO_REQUIRE((Cin & 15) == 0 && nu > 0, "mask_head_out_bf16_fwd: more than 8 classes need Cin %% 16 == 0 and Cin <= 2552 (got %d)", Cin);
+        switch (nu) {
+        case 1: mask_out_bf16_mfma_launch<1>(x, w, bias, p, M, Cin, C, s); break;
+        case 2: mask_out_bf16_mfma_launch<2>(x, w, bias, p, M, Cin, C, s); break;
+        case 3: mask_out_bf16_mfma_launch<3>(x, w, bias, p, M, Cin, C, s); break;
+        default: mask_out_bf16_mfma_launch<4>(x, w, bias, p, M, Cin, C, s); break;
+        }
+        MYOLO_CHECK_LAUNCH();
+        return MYOLO_OK;
+    }
     long long blocks = (M + 3) / 4;
     if (blocks > 16384) blocks = 16384;
 #define MO_CASE(K) case K: hipLaunchKernelGGL((mask_out_bf16_kernel<K>), dim3((unsigned)blocks), dim3(256), 0, s, x, w, bias, p, M, Cin); break;

@@ -2472,6 +2472,189 @@ __global__ void small_colsum_kernel(const float* __restrict__ dz, float* __restr
 }
 
 // ---------------------------------------------------------------------------------------
+// final mask conv 1x1 for C > MASK_MAXC classes, on the fp32 matrix pipe:  p[M, C] = sigmoid(x[M, Cin] w[Cin, C] + b).
+// A wave owns 32 rows and a group of 32 NU class columns (C padded with zero columns); lane (row l31, half h) loads 16 bytes of its
+// row per step (k = 8 j + 4 h .. + 3) and the matching 16 bytes of w^T's row n from LDS (rows padded to Cin + 4 floats: conflict-free
+// 16-byte reads) and feeds v_mfma_f32_32x32x2_f32 -- exact fp32 products, one fixed fma chain per output, no atomics: bit-reproducible.
+// Where one group holds every class (C <= 128 at Cin = 256) each row of x is read once; bias and sigmoid are applied on the way out and
+// only the C valid columns are stored (rows of p are C floats: not 16-byte aligned for odd C).  Rows past M repeat row M - 1, never stored.
+// ---------------------------------------------------------------------------------------
+typedef float mo_f32x16 __attribute__((ext_vector_type(16)));
+#define MASK_MFMA_THREADS 512
+template <int NU>
+__global__ __launch_bounds__(MASK_MFMA_THREADS) void mask_out_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                           const float* __restrict__ bias, float* __restrict__ p, long long M,
+                                                                           int Cin, int C)
+{
+    extern __shared__ __align__(16) float mo_lds[];              // w^T of this column group: [32 NU][Cin + 4]
+    constexpr int NN = 32 * NU;
+    const int ldw = Cin + 4;
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
+    const int c0 = blockIdx.y * NN;
+    for (int e = tid; e < NN * Cin; e += MASK_MFMA_THREADS) {
+        const int k = e / NN, n = e - k * NN;
+        mo_lds[n * ldw + k] = c0 + n < C ? w[(long long)k * C + c0 + n] : 0.f;
+    }
+    float bl[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) bl[u] = c0 + 32 * u + l31 < C ? bias[c0 + 32 * u + l31] : 0.f;
+    __syncthreads();
+    const long long nblk = (M + 31) / 32;
+    constexpr int WPB = MASK_MFMA_THREADS / 64;
+    const long long nwave = (long long)gridDim.x * WPB;
+    const float* wb = mo_lds + l31 * ldw + 4 * half;
+    const int nj = Cin / 8;
+    for (long long blk = (long long)blockIdx.x * WPB + (tid >> 6); blk < nblk; blk += nwave) {
+        const long long row = blk * 32 + l31;
+        const float* ap = x + (row < M ? row : M - 1) * Cin + 4 * half;
+        mo_f32x16 acc[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < nj; ++j) {
+            const float4 a = ld4g(ap + 8 * j);
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const float4 b = *reinterpret_cast<const float4*>(wb + u * 32 * ldw + 8 * j);
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[u], 0, 0, 0);
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[u], 0, 0, 0);
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[u], 0, 0, 0);
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[u], 0, 0, 0);
+            }
+        }
+        // acc[u][r]: row (r & 3) + 8 (r >> 2) + 4 half of the block, column c0 + 32 u + l31
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long long orow = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (orow < M) {
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    const int col = c0 + 32 * u + l31;
+                    if (col < C) {
+                        float s = acc[u][r];
+                        s += bl[u];
+                        p[orow * C + col] = 1.f / (1.f + expf(-s));
+                    }
+                }
+            }
+        }
+    }
+}
+
+static int mask_cu_count()
+{
+    static int n = 0;
+    if (!n) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        n = v;
+    }
+    return n;
+}
+
+#define MASK_MFMA_LDS_MAX (160 * 1024)
+template <int NU>
+static void mask_out_mfma_launch(const float* x, const float* w, const float* bias, float* p, long long M, int Cin, int C, hipStream_t s)
+{
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)mask_out_mfma_kernel<NU>, hipFuncAttributeMaxDynamicSharedMemorySize, MASK_MFMA_LDS_MAX);
+        attr_set = true;
+    }
+    const size_t lds = (size_t)32 * NU * (Cin + 4) * sizeof(float);
+    const int groups = (C + 32 * NU - 1) / (32 * NU);
+    long long wgs = (long long)mask_cu_count() * (int)(MASK_MFMA_LDS_MAX / lds);      // as many as are resident at once
+    const long long need = ((M + 31) / 32 + MASK_MFMA_THREADS / 64 - 1) / (MASK_MFMA_THREADS / 64);
+    if (wgs > need) wgs = need;
+    if (wgs < 1) wgs = 1;
+    hipLaunchKernelGGL((mask_out_mfma_kernel<NU>), dim3((unsigned)wgs, (unsigned)groups), dim3(MASK_MFMA_THREADS), lds, s, x, w, bias, p, M,
+                       Cin, C);
+}
+
+// the widest column group (at most 128 classes) whose w^T fits in LDS
+static int mask_out_mfma_nu(int Cin, int C)
+{
+    int nu = (C + 31) / 32;
+    if (nu > 4) nu = 4;
+    while (nu > 0 && (size_t)32 * nu * (Cin + 4) * sizeof(float) > MASK_MFMA_LDS_MAX) --nu;
+    return nu;
+}
+
+// ---------------------------------------------------------------------------------------
+// backward of the mask conv 1x1 given only the gradient of the selected class's logit (myolo_mask_loss_graph reads channel
+// class_id of a positive ROI, model.py:739-746): dz_sel [M], ids [M / hw].
+//   dx[r, c] = (x[r, c] > 0) ? dz_sel[r] w[c, id] : 0     -- fmaf(g, w, 0): the same bits as the dense kernel's chain on a one-hot dz
+//   part[roi] = { sum_r x[r, c] dz_sel[r] (c < Cin), sum_r dz_sel[r] } over the ROI's hw rows, in doubles (one workgroup per ROI)
+// then dw[c, k] / db[k] = sum of part over the ROIs of class k, in ROI order (one workgroup per class).  O(M Cin) whatever C is.
+// Cin / 4 divides 256: a thread keeps one channel quad and walks every (256 / (Cin / 4))-th row of its ROI.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_out_bwd_sel_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ dz_sel, const int32_t* __restrict__ ids,
+                                                               float* __restrict__ dx, double* __restrict__ part, int Cin, int C, int hw)
+{
+    __shared__ double red[256][5];
+    const int tid = threadIdx.x, roi = blockIdx.x;
+    const int cq = Cin >> 2, rstep = 256 / cq, q = tid % cq, r0 = tid / cq;
+    const int id = ids[roi];
+    const bool valid = id > 0 && id < C;
+    float4 wq = f4zero();
+    if (valid) wq = make_float4(w[(4 * q + 0) * C + id], w[(4 * q + 1) * C + id], w[(4 * q + 2) * C + id], w[(4 * q + 3) * C + id]);
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, gs = 0;
+    const long long base = (long long)roi * hw;
+    for (int i = r0; i < hw; i += rstep) {
+        const long long r = base + i;
+        const float g = dz_sel[r];
+        const float4 v = ld4g(x + r * Cin + 4 * q);
+        float4 o;
+        o.x = v.x > 0.f ? fmaf(g, wq.x, 0.f) : 0.f; o.y = v.y > 0.f ? fmaf(g, wq.y, 0.f) : 0.f;
+        o.z = v.z > 0.f ? fmaf(g, wq.z, 0.f) : 0.f; o.w = v.w > 0.f ? fmaf(g, wq.w, 0.f) : 0.f;
+        st4g(dx + r * Cin + 4 * q, o);
+        a0 += (double)v.x * g; a1 += (double)v.y * g; a2 += (double)v.z * g; a3 += (double)v.w * g;
+        gs += (double)g;
+    }
+    red[tid][0] = a0; red[tid][1] = a1; red[tid][2] = a2; red[tid][3] = a3; red[tid][4] = gs;
+    __syncthreads();
+    if (r0 != 0) return;
+    for (int t = 1; t < rstep; ++t)
+        for (int e = 0; e < 5; ++e) red[tid][e] += red[t * cq + q][e];
+    double* pr = part + (long long)roi * (Cin + 1);
+    pr[4 * q + 0] = red[tid][0]; pr[4 * q + 1] = red[tid][1]; pr[4 * q + 2] = red[tid][2]; pr[4 * q + 3] = red[tid][3];
+    if (q == 0) pr[Cin] = red[tid][4];
+}
+
+#define MASK_SEL_MAXCOL 4           // columns of part per finishing thread: Cin + 1 <= 1024
+__global__ __launch_bounds__(256) void mask_out_bwd_sel_finish(const double* __restrict__ part, const int32_t* __restrict__ ids, float* __restrict__ dw,
+                                                               float* __restrict__ db, int NR, int Cin, int C)
+{
+    __shared__ int sid[256];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    double acc[MASK_SEL_MAXCOL];
+#pragma unroll
+    for (int j = 0; j < MASK_SEL_MAXCOL; ++j) acc[j] = 0.0;
+    for (int c0 = 0; c0 < NR; c0 += 256) {
+        __syncthreads();
+        sid[tid] = c0 + tid < NR ? ids[c0 + tid] : -1;
+        __syncthreads();
+        const int n = NR - c0 < 256 ? NR - c0 : 256;
+        for (int i = 0; i < n; ++i) {
+            if (sid[i] != k || k == 0) continue;
+            const double* pr = part + (long long)(c0 + i) * (Cin + 1);
+#pragma unroll
+            for (int j = 0; j < MASK_SEL_MAXCOL; ++j)
+                if (tid + 256 * j <= Cin) acc[j] += pr[tid + 256 * j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MASK_SEL_MAXCOL; ++j) {
+        const int c = tid + 256 * j;
+        if (c < Cin) dw[(long long)c * C + k] = (float)acc[j];
+        else if (c == Cin) db[k] = (float)acc[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // mask BCE (K.binary_crossentropy on post-sigmoid p), forward + d/dlogit
 // ---------------------------------------------------------------------------------------
 __global__ void bce_count_kernel(const int32_t* __restrict__ ids, int NR, int* __restrict__ npos)
@@ -2544,6 +2727,44 @@ __global__ __launch_bounds__(256) void bce_finish_kernel(const double* __restric
     const int npos = *npos_p;
     out[0] = npos > 0 ? (float)(red[0] / ((double)npos * hw)) : 0.f;
     out[1] = (float)npos;
+}
+
+// bce_kernel's walk (same grid, same per-thread order of the loss terms: the same partials, bit for bit) that writes only the gradient
+// of the selected channel: dz_sel[i] = dz[i, ids[i / hw]] (0 for a ROI without a class in 1..C-1)
+__global__ __launch_bounds__(256) void bce_sel_kernel(const float* __restrict__ tm, const int32_t* __restrict__ ids,
+                                                      const float* __restrict__ pred, const int* __restrict__ npos_p,
+                                                      float lw, double* __restrict__ part, float* __restrict__ dz_sel,
+                                                      int NR, int hw, int C)
+{
+    __shared__ double red[256];
+    const long long total = (long long)NR * hw;
+    const int npos = *npos_p;
+    const float invn = npos > 0 ? 1.f / ((float)npos * (float)hw) : 0.f;
+    double lsum = 0;
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const float eps = 1e-7f;
+    for (; i < total; i += stride) {
+        const int id = ids[(int)(i / hw)];
+        float g = 0.f;
+        if (id > 0 && id < C) {
+            const float p = pred[i * C + id], t = tm[i];
+            const float pc = fminf(fmaxf(p, eps), 1.f - eps);
+            const float z = logf(pc / (1.f - pc));
+            const float l = fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+            lsum += (double)l;
+            const bool inside = (p >= eps) && (p <= 1.f - eps);
+            g = inside ? (pc - t) * invn * lw : 0.f;
+        }
+        dz_sel[i] = g;
+    }
+    red[threadIdx.x] = lsum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3566,8 +3787,20 @@ int myolo_roialign_bwd_grouped(const float* dout, const float* boxes, float* dim
 
 int myolo_mask_head_out_fwd(const float* x, const float* w, const float* bias, float* p, int64_t M, int Cin, int C, void* stream)
 {
-    MYOLO_REQUIRE(x && w && bias && p && M > 0 && (Cin & 3) == 0 && C >= 1 && C <= MASK_MAXC, "mask_head_out_fwd: bad arguments (1<=C<=8)");
+    MYOLO_REQUIRE(x && w && bias && p && M > 0 && (Cin & 3) == 0 && C >= 1, "mask_head_out_fwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    if (C > MASK_MAXC) {          // the matrix-pipe kernel
+        const int nu = mask_out_mfma_nu(Cin, C);
+        MYOLO_REQUIRE((Cin & 7) == 0 && nu > 0, "mask_head_out_fwd: more than %d classes need Cin %% 8 == 0 and Cin <= 1276 (got %d)", MASK_MAXC, Cin);
+        switch (nu) {
+        case 1: mask_out_mfma_launch<1>(x, w, bias, p, M, Cin, C, s); break;
+        case 2: mask_out_mfma_launch<2>(x, w, bias, p, M, Cin, C, s); break;
+        case 3: mask_out_mfma_launch<3>(x, w, bias, p, M, Cin, C, s); break;
+        default: mask_out_mfma_launch<4>(x, w, bias, p, M, Cin, C, s); break;
+        }
+        MYOLO_CHECK_LAUNCH();
+        return MYOLO_OK;
+    }
     long long blocks = (M + 3) / 4;
     if (blocks > 16384) blocks = 16384;
 #define MO_CASE(K) case K: hipLaunchKernelGGL((mask_out_fwd_kernel<K>), dim3((unsigned)blocks), dim3(256), 0, s, x, w, bias, p, M, Cin); break;
@@ -3580,7 +3813,8 @@ int myolo_mask_head_out_fwd(const float* x, const float* w, const float* bias, f
 int myolo_mask_head_out_bwd(const float* x, const float* w, const float* dz, float* dx, float* dw, float* db, int64_t M, int Cin,
                             int C, void* ws, size_t ws_bytes, void* stream)
 {
-    MYOLO_REQUIRE(x && w && dz && dx && dw && db && M > 0 && (Cin & 3) == 0 && C >= 1 && C <= MASK_MAXC, "mask_head_out_bwd: bad arguments");
+    MYOLO_REQUIRE(x && w && dz && dx && dw && db && M > 0 && (Cin & 3) == 0 && C >= 1 && C <= MASK_MAXC,
+                  "mask_head_out_bwd: bad arguments (1<=C<=%d; more classes: myolo_mask_head_out_bwd_sel)", MASK_MAXC);
     hipStream_t s = (hipStream_t)stream;
     int rc = MYOLO_EINVAL;
 #define MO_CASE(K) case K: rc = mask_out_bwd_impl<K>(x, w, dz, dx, dw, db, M, Cin, ws, ws_bytes, s); break;
@@ -3604,6 +3838,45 @@ int myolo_mask_bce(const float* target_masks, const int32_t* target_class_ids, c
     hipLaunchKernelGGL(bce_kernel, dim3(nblk), dim3(256), 0, s, target_masks, target_class_ids, pred, npos, loss_weight, part, dz,
                        NR, h * w, C);
     hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(256), 0, s, part, nblk, npos, h * w, loss_out);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+int myolo_mask_bce_sel(const float* target_masks, const int32_t* target_class_ids, const float* pred, float loss_weight,
+                       float* loss_out, float* dz_sel, int NR, int h, int w, int C, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(target_masks && target_class_ids && pred && loss_out && dz_sel && NR > 0 && C > 0, "mask_bce_sel: bad arguments");
+    const int nblk = 1024;          // myolo_mask_bce's grid: the same loss partials
+    MYOLO_NEED_WS(256 + nblk * sizeof(double));
+    int* npos = (int*)ws;
+    double* part = (double*)((char*)ws + 256);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bce_count_kernel, dim3(1), dim3(256), 0, s, target_class_ids, NR, npos);
+    hipLaunchKernelGGL(bce_sel_kernel, dim3(nblk), dim3(256), 0, s, target_masks, target_class_ids, pred, npos, loss_weight, part, dz_sel,
+                       NR, h * w, C);
+    hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(256), 0, s, part, nblk, npos, h * w, loss_out);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+size_t myolo_mask_head_out_bwd_sel_ws_bytes(int NR, int Cin)
+{
+    return NR > 0 && Cin > 0 ? (size_t)NR * (Cin + 1) * sizeof(double) : 0;
+}
+
+int myolo_mask_head_out_bwd_sel(const float* x, const float* w, const float* dz_sel, const int32_t* ids, float* dx, float* dw, float* db,
+                                int64_t M, int Cin, int C, int hw, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(x && w && dz_sel && ids && dx && dw && db && M > 0 && C >= 1 && hw > 0 && M % hw == 0 && M / hw <= 0x7fffffff,
+                  "mask_head_out_bwd_sel: bad arguments");
+    MYOLO_REQUIRE((Cin & 3) == 0 && Cin > 0 && 256 % (Cin >> 2) == 0 && Cin + 1 <= 256 * MASK_SEL_MAXCOL,
+                  "mask_head_out_bwd_sel: Cin / 4 must divide 256 (got Cin %d)", Cin);
+    const int NR = (int)(M / hw);
+    MYOLO_NEED_WS(myolo_mask_head_out_bwd_sel_ws_bytes(NR, Cin));
+    double* part = (double*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mask_out_bwd_sel_kernel, dim3((unsigned)NR), dim3(256), 0, s, x, w, dz_sel, ids, dx, part, Cin, C, hw);
+    hipLaunchKernelGGL(mask_out_bwd_sel_finish, dim3((unsigned)C), dim3(256), 0, s, part, ids, dw, db, NR, Cin, C);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -110,6 +110,8 @@ SIGS = {
     "myolo_mask_head_out_bf16_fwd": [P, P, P, P, L, I, I, P],
     "myolo_mask_head_out_bwd": [P, P, P, P, P, P, L, I, I, P, Z, P],
     "myolo_mask_bce": [P, P, P, F, P, P, I, I, I, I, P, Z, P],
+    "myolo_mask_bce_sel": [P, P, P, F, P, P, I, I, I, I, P, Z, P],
+    "myolo_mask_head_out_bwd_sel": [P, P, P, P, P, P, P, L, I, I, I, P, Z, P],
     "myolo_adam_step": [P, P, P, P, L, F, F, F, F, F, P],
     "myolo_matmul_f32": [P, P, P, L, I, I, I, I, P, Z, P],
     "myolo_stream_copy": [P, P, Z, I, I, P],
@@ -189,6 +191,8 @@ def load():
     lib.myolo_deconv2x2s2_mask_ws_bytes.restype = Z
     lib.myolo_wino_output_transform_bn_ws_bytes.argtypes = [I]
     lib.myolo_wino_output_transform_bn_ws_bytes.restype = Z
+    lib.myolo_mask_head_out_bwd_sel_ws_bytes.argtypes = [I, I]
+    lib.myolo_mask_head_out_bwd_sel_ws_bytes.restype = Z
     lib.myolo_wprep_create.argtypes = [P, Z, P]
     lib.myolo_wprep_create.restype = I
     for fn in (lib.myolo_wprep_destroy, lib.myolo_wprep_activate, lib.myolo_wprep_invalidate):
@@ -207,7 +211,7 @@ def load():
 def exported_symbols():
     return list(SIGS) + ["myolo_version", "myolo_last_error_string", "myolo_workspace_bytes", "myolo_conv3x3_wino_ws_bytes", "myolo_wino_plane_elems", "myolo_wino_u_elems", "myolo_wino63_u_elems", "myolo_wino63_plane_elems", "myolo_wino63_ok", "myolo_wino63_bwd_data_ws_bytes", "myolo_wino63_bwd_weight_ws_bytes", "myolo_wino63_bwd_data_from_v_ws_bytes", "myolo_wino63_bwd_weight_from_q_ws_bytes", "myolo_wino63_output_transform_bn_ws_bytes", "myolo_conv3x3_wino63_ws_bytes", "myolo_matmul_f32_ws_bytes", "myolo_conv3x3s2_c3_bnstats_ws_bytes", "myolo_dwconv3x3_bnstats_ws_bytes", "myolo_dwconv3x3_bwd_weight_ws_bytes",
                               "myolo_pwconv1x1_bnstats_ws_bytes", "myolo_pwconv1x1_bnstats_ok",
-                              "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes",
+                              "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh"]
 
 
@@ -503,3 +507,7 @@ def deconv_mask_ws_bytes(n, h, w, cin, cout, ncls):
 
 def wino_out_bn_ws_bytes(c):
     return int(load().myolo_wino_output_transform_bn_ws_bytes(int(c)))
+
+
+def mask_bwd_sel_ws_bytes(nr, cin):
+    return int(load().myolo_mask_head_out_bwd_sel_ws_bytes(int(nr), int(cin)))

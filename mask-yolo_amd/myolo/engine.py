@@ -27,6 +27,9 @@ ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 BACKBONE_BLOCKS = [(64, 1), (64, 2), (128, 1), (256, 2), (256, 1), (512, 1)]                      # model.py:68-77
 YOLO_BLOCKS = [(512, 2), (512, 1), (512, 1), (512, 1), (512, 1), (512, 1), (1024, 2), (1024, 1)]   # model.py:256-268
 MASK_FILTERS = 256                                                                                 # model.py:688-711
+# classes above this take the mask loss / 1x1 backward that carry only the selected class's logit gradient (myolo_mask_bce_sel,
+# myolo_mask_head_out_bwd_sel: dz_sel [rows] + the class ids in place of a dense dz [rows, C]); up to it, the dense kernels
+MASK_DENSE_MAX_CLASSES = 8
 
 
 WINO_MIN_ROWS = 8192       # CONV3X3_ALGO='auto': output pixels from which the Winograd form of a 3x3 conv is used (Rice 416 at batch 4: feature_map has 10816)
@@ -1186,8 +1189,9 @@ class Net(object):
                NR * 4 * ps * ps, MASK_FILTERS, C, X.stream())
         return p
 
-    def mask_head_bwd(self, dz):
-        """dz [NR*mh*mw, C] gradient wrt the pre-sigmoid mask logits.  Returns dF."""
+    def mask_head_bwd(self, dz, ids=None):
+        """dz [NR*mh*mw, C] gradient wrt the pre-sigmoid mask logits (C > MASK_DENSE_MAX_CLASSES: the selected channel's
+        gradient [NR*mh*mw, 1] of myolo_mask_bce_sel, and ids [NR] the class id per ROI).  Returns dF."""
         cfg = self.cfg
         convs, a4, d = self.tape["mask"]
         boxes, bind, fshape, NR = self.tape["roi"]
@@ -1195,8 +1199,7 @@ class Net(object):
         C = cfg.NUM_CLASSES
         Md = NR * 4 * ps * ps
         dd = self._new(Md, MASK_FILTERS)
-        X.call("myolo_mask_head_out_bwd", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(dz), X.ptr(dd),
-               X.ptr(self.g["myolo_mask/kernel"]), X.ptr(self.g["myolo_mask/bias"]), Md, MASK_FILTERS, C, *self._wsargs(), X.stream())
+        self._mask_out_bwd(d, dz, ids, dd, Md, C)
         X.call("myolo_deconv2x2s2_bwd_weight", X.ptr(a4), X.ptr(dd), X.ptr(self.g["myolo_mask_deconv/kernel"]), NR, ps, ps,
                MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
         self.colsum(dd, self.g["myolo_mask_deconv/bias"])
@@ -1220,6 +1223,29 @@ class Net(object):
             self.on_bucket_ready(BUCKET_MASK_REST)
             self.on_bucket_ready(BUCKET_MASK_CONV1)
         return dF
+
+    def _mask_out_bwd(self, d, dz, ids, dd, Md, C):
+        """backward of the mask 1x1 (+ the deconv's ReLU) into dd and the myolo_mask gradients: dense dz, or dz_sel + ids above MASK_DENSE_MAX_CLASSES"""
+        if C > MASK_DENSE_MAX_CLASSES:
+            hw = 4 * self.cfg.MASK_POOL_SIZE ** 2
+            self.ws.ensure(X.mask_bwd_sel_ws_bytes(Md // hw, MASK_FILTERS))
+            X.call("myolo_mask_head_out_bwd_sel", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(dz), X.ptr(ids), X.ptr(dd),
+                   X.ptr(self.g["myolo_mask/kernel"]), X.ptr(self.g["myolo_mask/bias"]), Md, MASK_FILTERS, C, hw, *self._wsargs(), X.stream())
+        else:
+            X.call("myolo_mask_head_out_bwd", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(dz), X.ptr(dd),
+                   X.ptr(self.g["myolo_mask/kernel"]), X.ptr(self.g["myolo_mask/bias"]), Md, MASK_FILTERS, C, *self._wsargs(), X.stream())
+
+    def mask_bce(self, tmask, tcls, pred, w2, nr):
+        """myolo_mask_loss_graph (model.py:718-754): (mask_terms [2], dz) -- dz the dense logit gradient [rows, C], or above
+        MASK_DENSE_MAX_CLASSES the selected channel's [rows, 1] (myolo_mask_bce_sel: the same loss bits)"""
+        C = self.cfg.NUM_CLASSES
+        mh, mw = self.cfg.MASK_SHAPE
+        mterms = self._new(2)
+        sel = C > MASK_DENSE_MAX_CLASSES
+        dz = self._new(pred.shape[0], 1 if sel else C)
+        X.call("myolo_mask_bce_sel" if sel else "myolo_mask_bce", X.ptr(tmask), X.ptr(tcls), X.ptr(pred), w2, X.ptr(mterms), X.ptr(dz), nr,
+               mh, mw, C, *self._wsargs(), X.stream())
+        return mterms, dz
 
     def _gather(self, t, idx, n, group_rows):
         C = t.shape[1]
@@ -1351,7 +1377,7 @@ class Net(object):
         X.call("myolo_gather_groups", X.ptr(tcls), X.ptr(idx_d), X.ptr(tcls_p), NP, 1, X.stream())
         return pred, tmask_p, tcls_p
 
-    def mask_head_bwd_sparse(self, dz, B, R):
+    def mask_head_bwd_sparse(self, dz, B, R, ids=None):
         """Same gradients as mask_head_bwd, exploiting a structural zero: bn2-4 are frozen affine maps
         (model.py:696,702,708) and the mask loss only reads positive ROIs (model.py:739-746), so behind bn1
         every non-positive ROI's gradient is exactly 0.  conv2-4 / deconv / myolo_mask backward therefore run
@@ -1404,8 +1430,11 @@ class Net(object):
             d_p = gather(d, 4 * q)
         Md = NP * 4 * q
         dd = self._new(Md, MASK_FILTERS)
-        X.call("myolo_mask_head_out_bwd", X.ptr(d_p), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(dz_p), X.ptr(dd),
-               X.ptr(self.g["myolo_mask/kernel"]), X.ptr(self.g["myolo_mask/bias"]), Md, MASK_FILTERS, C, *self._wsargs(), X.stream())
+        ids_p = ids
+        if C > MASK_DENSE_MAX_CLASSES and not compact:          # the positives' class ids beside their dz_sel rows
+            ids_p = self._new(NP, dtype=torch.int32)
+            X.call("myolo_gather_groups", X.ptr(ids), X.ptr(idx_d), X.ptr(ids_p), NP, 1, X.stream())
+        self._mask_out_bwd(d_p, dz_p, ids_p, dd, Md, C)
         # The compacted part is a chain of data gradients (deconv -> conv4 -> conv3 -> conv2 -> bn1's coefficients) that conv1's dense backward
         # waits for; the weight / bias gradients hanging off it have no consumer before the bucket's all-reduce.  They go to the stream (and
         # scratch) conv1's weight gradient uses later: queued in front of it, finished before the bucket is released there.
@@ -1828,17 +1857,14 @@ class Net(object):
             mterms = torch.zeros(2, dtype=torch.float32, device=self.dev)
             dz = None
         else:
-            mterms = self._new(2)
-            dz = self._new(pred.shape[0], pred.shape[1])
-            X.call("myolo_mask_bce", X.ptr(tmask_l), X.ptr(tcls_l), X.ptr(pred), w2, X.ptr(mterms), X.ptr(dz), tcls_l.numel(), mh, mw, C,
-                   *self._wsargs(), X.stream())
+            mterms, dz = self.mask_bce(tmask_l, tcls_l, pred, w2, tcls_l.numel())
         if self.tape_hook:
             self.tape_hook(self)
         if not early:
             # under the compacted part of the mask head's backward (small launches on the positive ROIs), not under the big
             # forward GEMMs: two streams of small kernels fill the chip together, and the dense kernels keep it to themselves
             self.start_yolo_head_bwd(dyolo)
-        dF = self.mask_head_bwd_sparse(dz, B, R) if self.sparse_mask_bwd else self.mask_head_bwd(dz)
+        dF = self.mask_head_bwd_sparse(dz, B, R, tcls_l) if self.sparse_mask_bwd else self.mask_head_bwd(dz, tcls_l)
         self.trunk_bwd(dF, dyolo)
         self.join_conv1_wgrad()
         if self.sparse_mask_fwd:          # the positives' masks only, in positive order (see mask_head_fwd_positives)
@@ -1885,10 +1911,7 @@ class Net(object):
         X.call("myolo_mask_targets", X.ptr(proposals), X.ptr(db["gt_ids"]), X.ptr(db["gt_boxes"]), X.ptr(db["gt_masks"]),
                X.ptr(rois), X.ptr(tcls), X.ptr(tmask), X.ptr(npos), B, R, T, H, W, mh, mw, X.stream())
         pred = self.mask_head_fwd(Fm, fshape, rois, False)
-        mterms = self._new(2)
-        dz = self._new(pred.shape[0], pred.shape[1])
-        X.call("myolo_mask_bce", X.ptr(tmask), X.ptr(tcls), X.ptr(pred), w2, X.ptr(mterms), X.ptr(dz), tcls.numel(), mh, mw, C,
-               *self._wsargs(), X.stream())
+        mterms, _ = self.mask_bce(tmask, tcls, pred, w2, tcls.numel())
         self.tape = {}
         return dict(yolo_terms=yterms, mask_terms=mterms, loss_weights=(w1, w2), yolo_output=yo.view(B, G, G, A, 5 + C),
                     output_rois=rois, target_class_ids=tcls, myolo_mask=pred.view(B, R, mh, mw, C), n_pos=npos)
