@@ -10,10 +10,13 @@ forward (backbone, YOLO head, decode, mask targets, ROIAlign, mask head on ALL R
 (the mask head behind bn1 on the positive ROIs only -- exact), gradient all-reduce (N>1) and the
 Adam update.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task
 statement) with:
-  roofline      -- the dominant kernel, timed live with HIP events on its launch stream inside the timed region, plus
+  roofline      -- the dominant kernel, timed live with HIP events on its launch stream inside the timed region, plus (--full)
                    objects for the kernels north_star names: depthwise (14 layers), ROIAlign (SURVEY 8(d) bytes), pointwise
-  cpu_baseline  -- the CPU restatement (oracle/torch_ref.py, torch-CPU) timed on this box's host cores
-  variants      -- the same K steps with the dense mask-head backward / the positives-only forward / forced positive counts
+  cpu_baseline  -- (--full) the CPU restatement (oracle/torch_ref.py, torch-CPU) timed on this box's host cores
+  variants      -- (--full) the same K steps with the dense mask-head backward / the positives-only forward / forced positive counts
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs and the line.  Everything else
+(the second per-kernel pass, variants, probes, public-call rates, the N_BOX=5 and Rice-416 runs, the CPU baseline, the cross-rank
+weight check) runs after the timed region, and only with --full.
 """
 import argparse
 import json
@@ -539,7 +542,7 @@ def bench_train(args, rank, world, local):
     bucket_ms = reducer.bucket_ms() if world > 1 else None
     release_ms = reducer.release_ms_before_wait() if world > 1 else None
     weights_same = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank must hold bit-identical weights after the K averaged updates: an integer digest of the flat parameter buffer, MIN == MAX over ranks
         net.join_conv1_wgrad()
         net.join_trunk_wgrad()
@@ -553,32 +556,34 @@ def bench_train(args, rank, world, local):
         dist.all_reduce(hi_, op=dist.ReduceOp.MAX)
         weights_same = bool(torch.equal(lo_, hi_))
 
-    # ---- second pass (not part of `value`): per-launch timings of the kernels north_star names
-    net.timed_tags = {"roialign_fwd", "wino_in", "wino_out_in"} | {"dw%d_fwd" % i for i in range(1, 15)} | {"pw%d_fwd" % i for i in range(1, 15)}
-    net.timings = {}
-    ksteps = 3
-    for i in range(ksteps):
-        net.train_step(dbs[i % nb], args.lr)
-    torch.cuda.synchronize()
-    kt = KernelTimer(net)
-    dw_ms, _ = kt.total_ms_per_step("dw", ksteps)
-    pw_ms, _ = kt.total_ms_per_step("pw", ksteps)
-    layer_ms = {tag: net.kernel_ms(tag)[0] for tag in list(net.timings) if tag[:2] in ("dw", "pw")}
-    roi_ms, _ = net.kernel_ms("roialign_fwd")
-    win_ms, win_n = net.kernel_ms("wino_in")
-    woi_ms, woi_n = net.kernel_ms("wino_out_in")
-    # what such an event bracket costs by itself: the same pair of timing events around a 4-byte fill (a ~2 us kernel).  The brackets of the
-    # trunk's 5-50 us launches carry this much on top of the kernel (rocprofv3's kernel times of the same launches are in profiles/)
-    from myolo import _ext as Xb
-    net.timed_tags = {"empty_bracket"}
-    net.timings = {}
-    probe_buf = torch.zeros(4, device=dev)
-    for _ in range(50):
-        net._call_timed("empty_bracket", "myolo_fill", Xb.ptr(probe_buf), 0.0, 1, Xb.stream())
-    torch.cuda.synchronize()
-    br = sorted(a.elapsed_time(b) for a, b in net.timings["empty_bracket"])
-    bracket_ms = br[len(br) // 2]
-    net.timed_tags = set()
+    # ---- second pass (--full, not part of `value`): per-launch timings of the kernels north_star names
+    layer_ms = None
+    if args.full:
+        net.timed_tags = {"roialign_fwd", "wino_in", "wino_out_in"} | {"dw%d_fwd" % i for i in range(1, 15)} | {"pw%d_fwd" % i for i in range(1, 15)}
+        net.timings = {}
+        ksteps = 3
+        for i in range(ksteps):
+            net.train_step(dbs[i % nb], args.lr)
+        torch.cuda.synchronize()
+        kt = KernelTimer(net)
+        dw_ms, _ = kt.total_ms_per_step("dw", ksteps)
+        pw_ms, _ = kt.total_ms_per_step("pw", ksteps)
+        layer_ms = {tag: net.kernel_ms(tag)[0] for tag in list(net.timings) if tag[:2] in ("dw", "pw")}
+        roi_ms, _ = net.kernel_ms("roialign_fwd")
+        win_ms, win_n = net.kernel_ms("wino_in")
+        woi_ms, woi_n = net.kernel_ms("wino_out_in")
+        # what such an event bracket costs by itself: the same pair of timing events around a 4-byte fill (a ~2 us kernel).  The brackets of the
+        # trunk's 5-50 us launches carry this much on top of the kernel (rocprofv3's kernel times of the same launches are in profiles/)
+        from myolo import _ext as Xb
+        net.timed_tags = {"empty_bracket"}
+        net.timings = {}
+        probe_buf = torch.zeros(4, device=dev)
+        for _ in range(50):
+            net._call_timed("empty_bracket", "myolo_fill", Xb.ptr(probe_buf), 0.0, 1, Xb.stream())
+        torch.cuda.synchronize()
+        br = sorted(a.elapsed_time(b) for a, b in net.timings["empty_bracket"])
+        bracket_ms = br[len(br) // 2]
+        net.timed_tags = set()
 
     # ---- variants (reported beside `value`, never as `value`)
     variants = {}
@@ -772,45 +777,47 @@ def bench_train(args, rank, world, local):
                 "conv_op": {"algo": (("winograd F(6,3)/F(4,3) tiling" if c1_63 else "winograd: conv1 F(4,3)/F(2,3) tiling, conv2-4 F(6,3)/F(4,3) tiling (average of the four ops)") if t63 else "winograd_f4x4_3x3") if mul_n else "direct",
                             "avg_ms": conv_ms, "ops_timed": conv_n, "direct_conv_flop": flop_direct,
                             "direct_equivalent_tflops": flop_direct / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
-                            "winograd_flop_frac_of_peak": wflop / (conv_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK if conv_ms > 0 else 0.0},
-                "depthwise": hbm_obj("dw_rows_kernel (row-sliding LDS-staged, round 4), the 14 depthwise 3x3 layers of backbone + YOLO head (sum over the layers, one step)",
-                                     dwb, dw_ms, note="SURVEY 8(d): activation in + out once, 20.97 MB/img at 224^2 alpha 1"),
-                "roialign": hbm_obj("ROIAlign forward (fused into conv1's Winograd input transform when CONV3X3_ALGO != direct)", roi_bytes, roi_ms,
-                                    note="SURVEY 8(d) bytes: the [B*R,14,14,256] crops + one read of the feature map; the fused kernel of the default "
-                                         "path writes conv1's Winograd image instead: %s" % (
-                                             "64 planes / 400 point-tiles per ROI = 2.04x those bytes" if c1_63 else "36 planes / 484 point-tiles per ROI = 2.47x those bytes"),
-                                    written_bytes=float(ptiles if not t63 else 400 * args.batch * R) * 256 * 4 if mul_n else roi_bytes,
-                                    achieved_on_written_bytes=(float(ptiles if not t63 else 400 * args.batch * R) * 256 * 4 / (roi_ms * 1e-3) / 1e9) if (mul_n and roi_ms > 0) else None),
-                "pointwise": {"kernel": "gemm_nn<PLAIN> 1x1 convs, the 14 pointwise layers (sum over the layers, one step)", "bound": "mfma+hbm",
-                              "algorithmic_flop": pwf, "algorithmic_bytes": pwb, "avg_ms": pw_ms,
-                              "achieved_tflops": pwf / (pw_ms * 1e-3) / 1e12 if pw_ms > 0 else 0.0,
-                              "frac_of_fp32_mfma_peak": pwf / (pw_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK if pw_ms > 0 else 0.0,
-                              "achieved_gbs": pwb / (pw_ms * 1e-3) / 1e9 if pw_ms > 0 else 0.0,
-                              "frac_of_hbm_peak": pwb / (pw_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if pw_ms > 0 else 0.0}}
-    roofline["trunk_layers"] = trunk_layer_table(args.size, args.alpha, args.batch, layer_ms, bracket_ms)
-    roofline["event_bracket_ms"] = bracket_ms
-    roofline["event_bracket_note"] = ("median HIP-event bracket around a 4-byte fill kernel on the compute stream: what every per-launch figure of the second pass "
-                                      "(depthwise, pointwise, trunk_layers, roialign, hbm_stages) carries on top of its kernel; '*_net' fields subtract it once per "
-                                      "bracket (they over-correct by the fill kernel's own ~2 us)")
-    n_dw = sum(1 for t in layer_ms if t.startswith("dw"))
-    n_pw = sum(1 for t in layer_ms if t.startswith("pw"))
-    for key, nbr in (("depthwise", n_dw), ("pointwise", n_pw)):
-        o = roofline[key]
-        net_ms = max(o["avg_ms"] - nbr * bracket_ms, 1e-6)
-        o["avg_ms_net"] = net_ms
-        if key == "depthwise":
-            o["frac_net"] = o["algorithmic_bytes"] / (net_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        else:
-            o["frac_of_fp32_mfma_peak_net"] = o["algorithmic_flop"] / (net_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK
-    mf = [l for l in roofline["trunk_layers"] if l["layer"].startswith("pw") and l["roof"] == "mfma" and l["ms"] > 0]
-    if mf:
-        fl, ms_ = sum(l["flop"] for l in mf), sum(l["ms"] for l in mf)
-        roofline["pointwise"]["mfma_bound_layers"] = {"layers": [l["layer"] for l in mf], "flop": fl, "ms": ms_, "achieved_tflops": fl / (ms_ * 1e-3) / 1e12,
-                                                      "frac_of_fp32_mfma_peak": fl / (ms_ * 1e-3) / 1e12 / FP32_MFMA_PEAK}
-    if mul_n and woi_n:
-        vbytes = float(400 * args.batch * R if t63 else ptiles) * 256 * 4          # the timed boundary launches are all on the conv2-4 tiling
-        roofline["hbm_stages"] = ([hbm_obj("wino_in_kernel (input transform: activation -> V)", float(M) * 256 * 4 + vbytes, win_ms)] if win_n else []) + [
-            hbm_obj("%s (layer boundary M_i -> V_{i+1} through LDS)" % ("wino63_boundary_kernel<FROM_M, TO_V>" if t63 else "wino_out_in_kernel"), 2 * vbytes, woi_ms)]
+                            "winograd_flop_frac_of_peak": wflop / (conv_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK if conv_ms > 0 else 0.0}}
+    if layer_ms is not None:                 # the second pass ran (--full)
+        roofline.update({
+            "depthwise": hbm_obj("dw_rows_kernel (row-sliding LDS-staged, round 4), the 14 depthwise 3x3 layers of backbone + YOLO head (sum over the layers, one step)",
+                                 dwb, dw_ms, note="SURVEY 8(d): activation in + out once, 20.97 MB/img at 224^2 alpha 1"),
+            "roialign": hbm_obj("ROIAlign forward (fused into conv1's Winograd input transform when CONV3X3_ALGO != direct)", roi_bytes, roi_ms,
+                                note="SURVEY 8(d) bytes: the [B*R,14,14,256] crops + one read of the feature map; the fused kernel of the default "
+                                     "path writes conv1's Winograd image instead: %s" % (
+                                         "64 planes / 400 point-tiles per ROI = 2.04x those bytes" if c1_63 else "36 planes / 484 point-tiles per ROI = 2.47x those bytes"),
+                                written_bytes=float(ptiles if not t63 else 400 * args.batch * R) * 256 * 4 if mul_n else roi_bytes,
+                                achieved_on_written_bytes=(float(ptiles if not t63 else 400 * args.batch * R) * 256 * 4 / (roi_ms * 1e-3) / 1e9) if (mul_n and roi_ms > 0) else None),
+            "pointwise": {"kernel": "gemm_nn<PLAIN> 1x1 convs, the 14 pointwise layers (sum over the layers, one step)", "bound": "mfma+hbm",
+                          "algorithmic_flop": pwf, "algorithmic_bytes": pwb, "avg_ms": pw_ms,
+                          "achieved_tflops": pwf / (pw_ms * 1e-3) / 1e12 if pw_ms > 0 else 0.0,
+                          "frac_of_fp32_mfma_peak": pwf / (pw_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK if pw_ms > 0 else 0.0,
+                          "achieved_gbs": pwb / (pw_ms * 1e-3) / 1e9 if pw_ms > 0 else 0.0,
+                          "frac_of_hbm_peak": pwb / (pw_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if pw_ms > 0 else 0.0}})
+        roofline["trunk_layers"] = trunk_layer_table(args.size, args.alpha, args.batch, layer_ms, bracket_ms)
+        roofline["event_bracket_ms"] = bracket_ms
+        roofline["event_bracket_note"] = ("median HIP-event bracket around a 4-byte fill kernel on the compute stream: what every per-launch figure of the second pass "
+                                          "(depthwise, pointwise, trunk_layers, roialign, hbm_stages) carries on top of its kernel; '*_net' fields subtract it once per "
+                                          "bracket (they over-correct by the fill kernel's own ~2 us)")
+        n_dw = sum(1 for t in layer_ms if t.startswith("dw"))
+        n_pw = sum(1 for t in layer_ms if t.startswith("pw"))
+        for key, nbr in (("depthwise", n_dw), ("pointwise", n_pw)):
+            o = roofline[key]
+            net_ms = max(o["avg_ms"] - nbr * bracket_ms, 1e-6)
+            o["avg_ms_net"] = net_ms
+            if key == "depthwise":
+                o["frac_net"] = o["algorithmic_bytes"] / (net_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            else:
+                o["frac_of_fp32_mfma_peak_net"] = o["algorithmic_flop"] / (net_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK
+        mf = [l for l in roofline["trunk_layers"] if l["layer"].startswith("pw") and l["roof"] == "mfma" and l["ms"] > 0]
+        if mf:
+            fl, ms_ = sum(l["flop"] for l in mf), sum(l["ms"] for l in mf)
+            roofline["pointwise"]["mfma_bound_layers"] = {"layers": [l["layer"] for l in mf], "flop": fl, "ms": ms_, "achieved_tflops": fl / (ms_ * 1e-3) / 1e12,
+                                                          "frac_of_fp32_mfma_peak": fl / (ms_ * 1e-3) / 1e12 / FP32_MFMA_PEAK}
+        if mul_n and woi_n:
+            vbytes = float(400 * args.batch * R if t63 else ptiles) * 256 * 4          # the timed boundary launches are all on the conv2-4 tiling
+            roofline["hbm_stages"] = ([hbm_obj("wino_in_kernel (input transform: activation -> V)", float(M) * 256 * 4 + vbytes, win_ms)] if win_n else []) + [
+                hbm_obj("%s (layer boundary M_i -> V_{i+1} through LDS)" % ("wino63_boundary_kernel<FROM_M, TO_V>" if t63 else "wino_out_in_kernel"), 2 * vbytes, woi_ms)]
     wtxt = ("mixed F(6,3)/F(4,3) tiling of the 14x14 maps, 400 point-tiles per ROI; F(4,3)/F(2,3) elsewhere" if net.wino_tiles == "f63"
             else "mixed F(4,3)/F(2,3) tiling, 484 point-tiles per 14x14 ROI")
     res = {
@@ -1012,6 +1019,20 @@ def bench_infer(args):
         el = time.perf_counter() - t0
     if gc_was:
         gc.enable()
+    res = {"metric": "images/sec inference, Rice 416x416, 5 anchors, 28x28 mask head, bf16 mask head, 1 MI355X",
+           "value": bsz * args.steps / el, "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": max(2, args.warmup),
+           "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "bf16", "data": "synthetic",
+           "one_in_flight": {"value": bsz * args.steps / el1, "ms_per_step": 1e3 * el1 / args.steps,
+                             "note": "the same forwards strictly one after the other on one stream (Net.predict_graphed), as rounds 1-2 reported"},
+           "config": {"workload": "Rice 416x416 inference forward, batch %d, N_BOX=5 (R=845 boxes/img, all through the mask head as the "
+                                  "reference graph does, model.py:926-931), fp32 trunk (frozen BatchNorm + ReLU6 folded into the depthwise / pointwise conv epilogues) + bf16 ROIAlign / 3x3 convs / deconv with fp32 accumulation; the timed forwards are replays of captured hipGraphs "
+                                  "(cfg.INFERENCE_HIP_GRAPH, as detect() runs them), %d batch(es) in flight (Net.predict_stream: one stream, graph and scratch per lane; "
+                                  "ms_per_step = wall time / batches)" % (bsz, nfl),
+                      "global_batch": bsz, "in_flight": nfl, "parallelism": "dp1"}}
+    if not args.full:
+        return res
+    res["config"]["workload"] += "; kernel timings from a separate eager pass"
     # per-kernel timings (HIP events around eager launches) in a second pass, outside the timed region
     net.timed_tags = {"mask_conv3x3_fwd", "roialign_fwd", "mask_deconv_fwd"}
     net.timings = {}
@@ -1052,31 +1073,20 @@ def bench_infer(args):
         del m
     except Exception as e:          # never lets the line fail
         api = {"error": repr(e)[:200]}
-    res = {"metric": "images/sec inference, Rice 416x416, 5 anchors, 28x28 mask head, bf16 mask head, 1 MI355X",
-           "value": bsz * args.steps / el, "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": max(2, args.warmup),
-           "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "bf16", "data": "synthetic",
-           "detect_many": api,
-           "one_in_flight": {"value": bsz * args.steps / el1, "ms_per_step": 1e3 * el1 / args.steps,
-                             "note": "the same forwards strictly one after the other on one stream (Net.predict_graphed), as rounds 1-2 reported"},
-           "config": {"workload": "Rice 416x416 inference forward, batch %d, N_BOX=5 (R=845 boxes/img, all through the mask head as the "
-                                  "reference graph does, model.py:926-931), fp32 trunk (frozen BatchNorm + ReLU6 folded into the depthwise / pointwise conv epilogues) + bf16 ROIAlign / 3x3 convs / deconv with fp32 accumulation; the timed forwards are replays of captured hipGraphs "
-                                  "(cfg.INFERENCE_HIP_GRAPH, as detect() runs them), %d batch(es) in flight (Net.predict_stream: one stream, graph and scratch per lane; "
-                                  "ms_per_step = wall time / batches); kernel timings from a separate eager pass" % (bsz, nfl),
-                      "global_batch": bsz, "in_flight": nfl, "parallelism": "dp1"},
-           "roofline": {"kernel": "conv3_bf16_256 (mask-head 3x3 conv as an implicit GEMM with the activation block resident in LDS across the nine taps, "
-                                  "bf16 operands, fp32 accumulate, M=%d K=2304 N=256)" % M,
-                        "bound": "mfma", "achieved": ach, "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s", "frac": ach / BF16_MFMA_PEAK,
-                        "traffic": traffic, "traffic_source": traffic_src, "algorithmic_flop": flop, "algorithmic_bytes": 2.0 * M * 256 * 2 + 9 * 256 * 256 * 2,
-                        "launches_timed": conv_n, "avg_launch_ms": conv_ms,
-                        "deconv_mask": {"kernel": "gemm_bf16_256<PLAIN, DECONV_MASK, LOOPN, MEP, FIN> (2x2/s2 transposed conv + ReLU + 1x1 mask conv on the matrix pipe + sigmoid in ONE launch, "
-                                                  "the 28x28x256 tensor never written)", "bound": "mfma", "avg_ms": dec_ms,
-                                        "algorithmic_flop": 2.0 * M * 256 * 4 * 256,
-                                        "achieved": 2.0 * M * 256 * 4 * 256 / (dec_ms * 1e-3) / 1e12 if dec_ms > 0 else 0.0, "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s"},
-                        "roialign": {"kernel": "crop_fwd_bf16_walk_kernel (a feature-map column fetched once per output row)", "bound": "hbm", "avg_ms": roi_ms,
-                                     "algorithmic_bytes": M * 256 * 2.0 + bsz * 52 * 52 * 256 * 4.0,
-                                     "achieved": (M * 256 * 2.0 + bsz * 52 * 52 * 256 * 4.0) / (roi_ms * 1e-3) / 1e9 if roi_ms > 0 else 0.0,
-                                     "peak": HBM_PEAK_GBS, "unit": "GB/s"}}}
+    res["detect_many"] = api
+    res["roofline"] = {"kernel": "conv3_bf16_256 (mask-head 3x3 conv as an implicit GEMM with the activation block resident in LDS across the nine taps, "
+                                 "bf16 operands, fp32 accumulate, M=%d K=2304 N=256)" % M,
+                       "bound": "mfma", "achieved": ach, "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s", "frac": ach / BF16_MFMA_PEAK,
+                       "traffic": traffic, "traffic_source": traffic_src, "algorithmic_flop": flop, "algorithmic_bytes": 2.0 * M * 256 * 2 + 9 * 256 * 256 * 2,
+                       "launches_timed": conv_n, "avg_launch_ms": conv_ms,
+                       "deconv_mask": {"kernel": "gemm_bf16_256<PLAIN, DECONV_MASK, LOOPN, MEP, FIN> (2x2/s2 transposed conv + ReLU + 1x1 mask conv on the matrix pipe + sigmoid in ONE launch, "
+                                                 "the 28x28x256 tensor never written)", "bound": "mfma", "avg_ms": dec_ms,
+                                       "algorithmic_flop": 2.0 * M * 256 * 4 * 256,
+                                       "achieved": 2.0 * M * 256 * 4 * 256 / (dec_ms * 1e-3) / 1e12 if dec_ms > 0 else 0.0, "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s"},
+                       "roialign": {"kernel": "crop_fwd_bf16_walk_kernel (a feature-map column fetched once per output row)", "bound": "hbm", "avg_ms": roi_ms,
+                                    "algorithmic_bytes": M * 256 * 2.0 + bsz * 52 * 52 * 256 * 4.0,
+                                    "achieved": (M * 256 * 2.0 + bsz * 52 * 52 * 256 * 4.0) / (roi_ms * 1e-3) / 1e9 if roi_ms > 0 else 0.0,
+                                    "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
     if args.cpu_images > 0:
         try:
             res["cpu_baseline"] = cpu_baseline(cfg, 1, infer=True, budget_s=60.0)
@@ -1098,14 +1108,19 @@ def main():
     ap.add_argument("--in-flight", type=int, default=3, help="--config rice416-bf16: inference batches in flight (Net.predict_stream); 1 = strictly serial")
     ap.add_argument("--config", choices=["shapes224-train", "rice416-bf16"], default="shapes224-train",
                     help="shapes224-train = BASELINE configs[1] (the metric); rice416-bf16 = configs[3] inference throughput")
-    ap.add_argument("--cpu-images", type=int, default=32, help="images in the CPU-baseline step (0 = skip; halved while host memory is short)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: the CPU baseline, the variants, the per-kernel second pass and its roofline "
+                         "objects, the probes, the public-call rates, the N_BOX=5 and Rice-416 runs, the cross-rank weight check "
+                         "(--cpu-images / --no-extras / --no-variant / --no-live-pmc trim it).  Without it a run sets up, warms up, times "
+                         "the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--cpu-images", type=int, default=32, help="--full: images in the CPU-baseline step (0 = skip; halved while host memory is short)")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--device-warm", type=int, default=8, help="untimed forward+backward passes (no optimizer update) in front of the warm-up steps: allocator pre-sizing + a cold GPU's first load transient")
     ap.add_argument("--mask-head-rois", choices=["all", "positives"], default="all",
                     help="cfg.TRAIN_MASK_HEAD_ROIS of the run that produces `value` (default: all ROIs, as the reference graph)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not measure the dominant kernel's HBM traffic with rocprofv3 --pmc in a child process (default line only)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra objects of the default line (HBM copy bandwidth, comm probe, N_BOX=5 and Rice-416 bf16 runs)")
-    ap.add_argument("--no-variant", action="store_true", help="skip the extra timed runs (dense backward, positives-only forward, n_pos sweep)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: do not measure the dominant kernel's HBM traffic with rocprofv3 --pmc in a child process")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra objects (HBM copy bandwidth, comm probe, N_BOX=5 and Rice-416 bf16 runs)")
+    ap.add_argument("--no-variant", action="store_true", help="--full: skip the extra timed runs (dense backward, positives-only forward, n_pos sweep)")
     ap.add_argument("--conv3x3", choices=["auto", "direct", "winograd"], default="auto", help="cfg.CONV3X3_ALGO")
     ap.add_argument("--comm", choices=["torch", "capi"], default="torch",
                     help="N>1: gradient all-reduce through torch.distributed (nccl = RCCL) or through the library's own myolo_comm_* entry points")
@@ -1131,6 +1146,8 @@ def main():
     args = ap.parse_args()
     if args.dump_outputs and args.config != "shapes224-train":
         ap.error("--dump-outputs covers the training step (--config shapes224-train)")
+    if not args.full:
+        args.cpu_images, args.no_extras, args.no_variant = 0, True, True
     args.batch_given = args.batch is not None
     if args.batch is None:
         args.batch = 32

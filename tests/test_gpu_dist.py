@@ -246,6 +246,35 @@ def test_engine_step_with_capi_reducer_is_bit_identical_to_no_reducer():
     assert torch.equal(outs[0], outs[1])
 
 
+def test_bench_plain_run_measures_only_the_headline(tmp_path):
+    """`python bench.py` without --full on one GPU: set-up, warm-up, the timed steps, --dump-outputs and the ONE line -- no CPU baseline, no
+    variants, no second per-kernel pass, probes or secondary configurations.  The dominant kernel's roofline, timed inside the region, stays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    detail = os.path.join(root, "plain_bench_detail.json")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--size", "128", "--alpha", "0.5",
+                        "--detail-name", os.path.basename(detail), "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 6000, lines
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-5 * d["value"]
+    assert d["cpu_baseline"] is None and d["roofline"]["avg_launch_ms"] > 0 and "depthwise" not in d["roofline"]
+    full = json.load(open(detail))
+    os.remove(detail)
+    for k in ("variants", "train_api", "hbm_copy_measured_gbs", "power_limit_probe", "secondary_nbox5", "inference_rice416_bf16", "comm"):
+        assert k not in full, k
+    assert "trunk_layers" not in full["roofline"] and "traffic_live" not in full["roofline"]
+    assert len(os.listdir(str(tmp_path / "out"))) == 12                          # what the last timed step returned + the weights after it
+
+
 def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2` end to end on this one-GPU box: the script re-launches itself under torch.distributed.run, two ranks
     build the engine, exchange gradients every step (gloo instead of RCCL: --share-gpu puts both ranks on cuda:0), take the MAX over
@@ -259,7 +288,7 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1", "--batch", "4",
-                        "--size", "128", "--alpha", "0.5", "--cpu-images", "0", "--dump-outputs", str(tmp_path / "out")],
+                        "--size", "128", "--alpha", "0.5", "--cpu-images", "0", "--full", "--dump-outputs", str(tmp_path / "out")],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -295,7 +324,7 @@ def test_bench_four_ranks_at_full_config2_size_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--share-gpu", "--steps", "3", "--warmup", "1", "--cpu-images", "0",
-                        "--no-variant", "--no-extras"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--full", "--no-variant", "--no-extras"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 6000, lines

@@ -5,7 +5,7 @@ TAG=${1:-r6}
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/evidence_$TAG
 mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 --detail-name ${TAG}_bench_detail.json 2> $OUT/bench.err | tail -1 > $OUT/${TAG}_bench.json      # the ONE compact line the driver parses
+python bench.py --steps 20 --warmup 5 --full --detail-name ${TAG}_bench_detail.json 2> $OUT/bench.err | tail -1 > $OUT/${TAG}_bench.json      # the ONE compact line the driver parses
 cp gpurun_out/${TAG}_bench_detail.json $OUT/${TAG}_bench_detail.json          # the full object (per-layer table, probes, variants)
 rm -f ${TAG}_bench_detail.json
 bash tools/profile_step.sh $TAG --steps 10 > /dev/null 2>&1

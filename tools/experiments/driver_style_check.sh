@@ -11,5 +11,5 @@ d=json.loads(lines[0])
 for k in ("metric","value","unit","n_gpus","steps","warmup","ms_per_step","higher_is_better","scaling","vs_baseline","dtype","data","config","roofline","cpu_baseline"):
     assert k in d, k
 assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1
-print(len(lines[0]), "bytes:", d["metric"], d["value"], d["ms_per_step"], d["roofline"]["frac"], d["cpu_baseline"]["value"])
+print(len(lines[0]), "bytes:", d["metric"], d["value"], d["ms_per_step"], d["roofline"]["frac"], (d["cpu_baseline"] or {}).get("value"))
 PY

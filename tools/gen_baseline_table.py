@@ -24,7 +24,7 @@ mf = r["pointwise"].get("mfma_bound_layers", {})
 rows = "\n".join("| %s | %s | %.1f | %.0f | %.1f | %s | %.2f | %.1f | %.2f |" % (l["layer"], l["shape"], l["ms"] * 1e3, l["gbs"], l["tflops"], l["roof"], l["frac"],
                                                                            l.get("ms_net", 0.0) * 1e3, l.get("frac_net", 0.0))
                  for l in r.get("trunk_layers", []))
-new = '''## %(sec)d. Results (round %(rnd)s, measured on 1x MI355X by ONE `python bench.py --steps 20 --warmup 5`; evidence `profiles/%(tag)s_*`, notes `profiles/r%(rnd)s_notes.md`)
+new = '''## %(sec)d. Results (round %(rnd)s, measured on 1x MI355X by ONE `python bench.py --full --steps 20 --warmup 5`; evidence `profiles/%(tag)s_*`, notes `profiles/r%(rnd)s_notes.md`)
 
 (generated from `profiles/%(tag)s_bench_detail.json` by `tools/gen_baseline_table.py`; %(spread)s)
 

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_infer_$TAG
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw -o p -- python bench.py --config rice416-bf16 --steps 20 --cpu-images 0 > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw -o p -- python bench.py --config rice416-bf16 --steps 20 --full --cpu-images 0 > $OUT/bench.log 2>&1
 python - "$OUT" "$TAG" <<'PY'
 import csv, glob, shutil, sys
 out, tag = sys.argv[1], sys.argv[2]
