@@ -48,16 +48,25 @@ const char* myolo_last_error_string(void);
  * `cols` output channels (weights-gradient split-K partials dominate). */
 size_t      myolo_workspace_bytes(int64_t rows, int cin, int cout);
 
-/* Tuning / ablation switches (process-wide ints, default 0 = shipped behaviour).  Names: "no_nt", "gemm_generic",
- * "no_splitk", "gemm_w256", "wino_nt", "wino_w256", "bf16_regstage", "bf16_no256", "bf16_force256", "crop_bwd_nolds",
- * "tune0", "dw_rows1", "dw_legacy", "dw_bwd_legacy", "dw_min_wg", "wino_no_mixed", "wino_no_bt", "wino_x6", "w63_order", "w63_legacy" (the one-unit Winograd transform kernels of rounds 3-5 instead of the
- * persistent ones; same bits), "w63_wgs" (persistent workgroups per CU, 0 = 1), "deconv_mask_legacy" (myolo_deconv2x2s2_mask_fwd[_keep] under "wino_x6": 1 = the
- * untransposed tile with the per-class butterfly epilogue of rounds 3-5, 2 = the transposed tile with partial logits + the finish launch -- same bits as 0),
- * "bf16_mask_nofin" (myolo_deconv2x2s2_mask_bf16_fwd: partial logits + the finish launch; same bits), "crop_bf16_legacy" (myolo_crop_and_resize_bf16_fwd: four corner
- * loads per output element instead of the column walk; same bits), "pw_no_smallm" (pointwise convs with few rows and K >= 256: the split-K pair of launches of
- * rounds 2-5 instead of the one-launch small-M kernel; another fp32 summation order), "pw_skinny_nw4" (conv_23: four waves per workgroup also from K = 512 up; another
- * fp32 summation order).  Unknown name -> MYOLO_EINVAL.  Every switch selects between
- * kernels with the same contract.  One switch changes NUMERICS within the bf16 inference path: "bf16_mask_valu" = 1 keeps the deconv output and the 1x1 mask kernel of
+/* Process-wide switches (ints; default 0 = shipped behaviour unless noted).  Unknown name -> MYOLO_EINVAL.  Each kernel-choice switch
+ * reaches a kernel with the same contract that a test holds the shipped one against, or a fallback a test must reach:
+ *   gemm:             "gemm_generic" (the guarded kernels), "no_splitk" (no K split for under-filled grids);
+ *   bf16 inference:   "bf16_no256" / "bf16_force256" (never / always the 256x256-tile GEMM), "bf16_no_c3" (the nine-fetch 3x3 conv),
+ *                     "bf16_no_loopn" (a workgroup per row tile and tap), "bf16_mask_nofin" (myolo_deconv2x2s2_mask_bf16_fwd: partial logits +
+ *                     the finish launch; same bits), "crop_bf16_legacy" (myolo_crop_and_resize_bf16_fwd: four corner loads per output element
+ *                     instead of the column walk; same bits);
+ *   fp32 products:    "wino_x6" (set by the engine for FP32_MATMUL = "bf16x6": six exact bf16 piece products per fp32 product), "deconv_no_x6",
+ *                     "pw_no_x6", "tn_no_x6" (the fp32-MFMA kernels even under "wino_x6"), "x6_no_half_tiles" (128 x 256 tiles even when they
+ *                     do not fill the chip), "pw_x6_min_rows" (fewest rows for the bf16x6 pointwise kernels, 0 = 4096), "pw_no_smallm" (pointwise
+ *                     convs with few rows and K >= 256: the split-K pair of launches instead of the one-launch small-M kernel; another fp32
+ *                     summation order), "deconv_mask_legacy" (myolo_deconv2x2s2_mask_fwd[_keep] under "wino_x6": 1 = the untransposed tile with
+ *                     the per-class butterfly epilogue of rounds 3-5, 2 = the transposed tile with partial logits + the finish launch -- same
+ *                     bits as 0), "tn_wgs" (wino_tn_x6_kernel: workgroups per launch, default 224, 0 = one launch);
+ *   Winograd:         "wino_no_bt" (gemm_nn_fast on [K][N] filters), "wino_no_mixed" (F(4,3) for every tile), "w63_legacy" (the one-unit
+ *                     F(6,3) transform kernels of rounds 3-5 instead of the persistent ones; same bits);
+ *   trunk:            "no_trunk_fusion" (the conv, then a separate BatchNorm statistics pass);
+ *   experiments:      "tune0" (scratch integer of the -DMM_X6_TUNE / -DBF16_TUNE builds only; no default build reads it).
+ * One switch changes NUMERICS within the bf16 inference path: "bf16_mask_valu" = 1 keeps the deconv output and the 1x1 mask kernel of
  * myolo_deconv2x2s2_mask_bf16_fwd in fp32 (rounds 3-5, VALU epilogue); the default rounds both to bf16 like every other activation / weight of that path and runs the
  * 1x1 conv on the matrix pipe (256-row kernels, i.e. >= 1536 row tiles of 256 channels; smaller problems keep the fp32 form).
  * One semantic switch: "bn_fused_tf_variance" (default 1) -- the BatchNormalization moving-variance update of bn_stats

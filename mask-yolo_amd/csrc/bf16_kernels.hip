@@ -4,11 +4,10 @@
 // fp32 MFMA rate, so the ROIAlign output, the four 3x3 convs (BatchNorm folded into the weights -- all
 // BN layers are frozen in inference, model.py:690-708) and the 2x2 transposed conv are kept in bf16.
 //
-//   gemm_bf16<AMODE, EPI>:  C[m, n] = act( sum_k A(m, k) * Wt[n, k] + bias[n] )
+//   gemm_bf16_glds<AMODE, EPI>:  C[m, n] = act( sum_k A(m, k) * Wt[n, k] + bias[n] )
 //     A bf16, gathered im2col-free (PLAIN rows or CONV3 taps with hardware zero-fill through a raw buffer
 //     descriptor), Wt bf16 [N][K] (k contiguous: weights are static, so they are stored transposed once),
-//     128x128x64 tiles, 4 waves x (2x2) MFMA 32x32x16, LDS rows padded to 144 B so every ds_read_b128
-//     fragment read (8 bf16 of one row) is bank-conflict-free, double-buffered, one barrier per K tile.
+//     128x128x64 tiles, 4 waves x (2x2) MFMA 32x32x16, operands staged into LDS by LDS-DMA, double-buffered.
 //     EPI PLAIN stores bf16 [M, N]; EPI DECONV scatters the 2x2/s2 transposed-conv output (bf16).
 #include "myolo_common.h"
 #include <stdlib.h>
@@ -20,7 +19,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define TBM 128
 #define TBN 128
 #define TBK 64
-#define LDSROW 72            // bf16 elements per LDS row (64 + 8 pad = 144 bytes)
 #define OOB_OFF 0x7fffff00u
 
 template <int V> struct IntC { static constexpr int value = V; };
@@ -53,10 +51,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, long
     if (nbytes > 0x7ffffe00ll) nbytes = 0x7ffffe00ll;
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(unsigned)nbytes, 0x00020000);
 }
-__device__ __forceinline__ u32x4 bufld(__amdgpu_buffer_rsrc_t r, unsigned off)
-{
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-}
 __device__ __forceinline__ uint16_t f2bf(float f)
 {   // round to nearest even
     unsigned u = __float_as_uint(f);
@@ -65,154 +59,7 @@ __device__ __forceinline__ uint16_t f2bf(float f)
 }
 __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float(((unsigned)h) << 16); }
 
-template <int AMODE, int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_bf16(Bf16Args p)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t As[2][TBM][LDSROW];
-    __shared__ __attribute__((aligned(16))) uint16_t Bs[2][TBN][LDSROW];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ntn = (p.N + TBN - 1) / TBN;
-    long long bid;
-    {   // XCD-aware order (speed only): each XCD gets a contiguous run of tiles
-        const long long nwg = gridDim.x, orig = blockIdx.x;
-        const long long q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    }
-    const int tn = (int)(bid % ntn);
-    const long long m0 = (bid / ntn) * TBM;
-    const int n0 = tn * TBN;
-    const long long hw = (long long)p.H * p.W;
-
-    // A descriptor with a per-workgroup base (32-bit offsets, out-of-range => zeros)
-    long long base_row, end_row, row_elems;
-    if (AMODE == AM_PLAIN) { base_row = m0; end_row = (m0 + TBM < p.M) ? m0 + TBM : p.M; row_elems = p.K; }
-    else {
-        base_row = m0 - (p.W + 1); if (base_row < 0) base_row = 0;
-        end_row = m0 + TBM + p.W + 1; if (end_row > p.M) end_row = p.M;
-        row_elems = p.Cc;
-    }
-    const __amdgpu_buffer_rsrc_t ra = mk_rsrc(p.A + base_row * row_elems, (end_row - base_row) * row_elems * 2);
-    const __amdgpu_buffer_rsrc_t rb = mk_rsrc(p.Wt, (long long)p.N * p.K * 2);
-
-    // each thread stages half a row (32 bf16 = 64 B = 4 x 16 B) of A and of B per K tile
-    const int lrow = tid >> 1, lhalf = tid & 1;
-    const long long am = m0 + lrow;
-    const bool avalid = am < p.M;
-    int ay = 0, ax = 0;
-    if (AMODE == AM_CONV3) {
-        const long long mm = avalid ? am : m0;
-        const long long n_img = mm / hw;
-        const int rem = (int)(mm - n_img * hw);
-        ay = rem / p.W; ax = rem - ay * p.W;
-    }
-    const unsigned arow = (unsigned)(((avalid ? am : m0) - base_row) * row_elems + lhalf * 32) * 2u;
-    const int bn = n0 + lrow;
-    const bool bvalid = bn < p.N;
-    const unsigned brow = (unsigned)((long long)(bvalid ? bn : 0) * p.K + lhalf * 32) * 2u;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][u][r] = 0.f;
-
-    const int nk = p.K / TBK;
-    int tap = 0, c0 = 0;
-    u32x4 va[4], vb[4];
-    auto gload = [&](int kt) {
-        unsigned aoff;
-        if (AMODE == AM_PLAIN) {
-            aoff = avalid ? arow + (unsigned)(kt * TBK) * 2u : OOB_OFF;
-        } else {
-            const int ty = (tap * 11) >> 5, tx = tap - ty * 3;
-            const bool v = avalid && (unsigned)(ay + ty - 1) < (unsigned)p.H && (unsigned)(ax + tx - 1) < (unsigned)p.W;
-            const int shift = ((ty - 1) * p.W + (tx - 1)) * p.Cc + c0;
-            aoff = v ? arow + (unsigned)(shift * 2) : OOB_OFF;
-            c0 += TBK;
-            if (c0 == p.Cc) { c0 = 0; ++tap; }
-        }
-        const unsigned boff = bvalid ? brow + (unsigned)(kt * TBK) * 2u : OOB_OFF;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            va[i] = bufld(ra, aoff == OOB_OFF ? OOB_OFF : aoff + 16u * i);
-            vb[i] = bufld(rb, boff == OOB_OFF ? OOB_OFF : boff + 16u * i);
-        }
-    };
-    auto sstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<u32x4*>(&As[buf][lrow][lhalf * 32 + i * 8]) = va[i];
-            *reinterpret_cast<u32x4*>(&Bs[buf][lrow][lhalf * 32 + i * 8]) = vb[i];
-        }
-    };
-
-    const int half = lane >> 5, l31 = lane & 31;
-    if (nk > 0) { gload(0); sstore(0); }
-    __syncthreads();
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) gload(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < TBK / 16; ++ks) {
-            const int kc = ks * 16 + half * 8;
-            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&As[cur][wm * 64 + l31][kc]);
-            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[cur][wm * 64 + 32 + l31][kc]);
-            const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(&Bs[cur][wn * 64 + l31][kc]);
-            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bs[cur][wn * 64 + 32 + l31][kc]);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-            if (ks == 1 && more) sstore(cur ^ 1);
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-
-    // ---- epilogue: bias + activation, bf16 stores ----
-    float cb[2];
-    int ccol[2], ctap[2];
-    bool cok[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int col = n0 + wn * 64 + u * 32 + l31;
-        cok[u] = col < p.N;
-        const int colc = cok[u] ? col : 0;
-        ctap[u] = 0; ccol[u] = colc;
-        if (EPI == EP_DECONV) { ctap[u] = colc / p.Co; ccol[u] = colc - ctap[u] * p.Co; }
-        cb[u] = p.bias ? p.bias[ccol[u]] : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long long row = m0 + wm * 64 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (row >= p.M) continue;
-            long long rowoff;
-            if (EPI == EP_PLAIN) rowoff = row * p.N;
-            else {
-                const long long n_img = row / hw;
-                const int rem = (int)(row - n_img * hw);
-                const int y = rem / p.W, x = rem - y * p.W;
-                rowoff = n_img * 4 * hw + (long long)y * 4 * p.W + 2 * x;
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (!cok[u]) continue;
-                float v = acc[t][u][r] + cb[u];
-                if (p.act == MYOLO_ACT_RELU) v = fmaxf(v, 0.f);
-                if (EPI == EP_PLAIN) p.C[rowoff + ccol[u]] = f2bf(v);
-                else p.C[(rowoff + (long long)(ctap[u] >> 1) * 2 * p.W + (ctap[u] & 1)) * p.Co + ccol[u]] = f2bf(v);
-            }
-        }
-}
-
-// ---- the same GEMM staged by LDS-DMA (buffer_load_dwordx4 ... lds): no staging VGPRs, no ds_write pass ----
+// ---- the GEMM, staged by LDS-DMA (buffer_load_dwordx4 ... lds): no staging VGPRs, no ds_write pass ----
 // LDS image per operand and buffer: 128 rows x 128 B (64 bf16), unpadded (the DMA destination is wave-uniform base +
 // lane x 16 B, so padding is impossible); bank conflicts are avoided by an XOR swizzle of the 16-B chunk index with
 // bits 1..3 of the row, applied on the per-lane SOURCE address when filling and on the ds_read_b128 address when reading.
@@ -1372,11 +1219,10 @@ static void launch_bf16(const Bf16Args& a, hipStream_t s)
 {
     const long long tiles = cdiv64(a.M, TBM) * ((a.N + TBN - 1) / TBN);
     if (tiles <= 0) return;
-    const bool regstage = g_myolo_opt.bf16_regstage != 0;    // ablation: register-staged variant (myolo_set_option)
     if constexpr (EPI == EP_PLAIN) {
         const bool no256 = g_myolo_opt.bf16_no256 != 0, force256 = g_myolo_opt.bf16_force256 != 0;
         const long long tiles256 = cdiv64(a.M, T2M) * ((a.N + T2N - 1) / T2N);
-        if (!no256 && !regstage && (a.N % T2N) == 0 && (tiles256 >= 1536 || force256)) {
+        if (!no256 && (a.N % T2N) == 0 && (tiles256 >= 1536 || force256)) {
             if (AMODE == AM_CONV3 && a.W + 1 <= (C3_AROWS - T2M) / 2 && !g_myolo_opt.bf16_no_c3)
                 hipLaunchKernelGGL(conv3_bf16_256, dim3((unsigned)tiles256), dim3(512), 0, s, a);
             else
@@ -1384,8 +1230,7 @@ static void launch_bf16(const Bf16Args& a, hipStream_t s)
             return;
         }
     }
-    if (regstage) hipLaunchKernelGGL((gemm_bf16<AMODE, EPI>), dim3((unsigned)tiles), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm_bf16_glds<AMODE, EPI>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gemm_bf16_glds<AMODE, EPI>), dim3((unsigned)tiles), dim3(256), 0, s, a);
 }
 
 extern "C" {

@@ -433,11 +433,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, l
         acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1, fb1, acc[1][1], 0, 0, 0);         \
     }
 
-// WNT = MFMA 32x32 tiles per wave along N: 2 -> 128x128 block tile (4 waves/SIMD), 4 -> 128x256 (2 waves/SIMD,
-// A fetched once for 256 output channels, 25 % fewer loads and LDS reads per MFMA).
-template <int AMODE, int EPI, int WNT = 2>
+template <int AMODE, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_nn_fast(GemmArgs p)
 {
+    constexpr int WNT = 2;                 // MFMA 32x32 tiles per wave along N: 128x128 block tile (4 waves/SIMD)
     __shared__ float As[2][BK][LDAS];
     constexpr int BN_ = 64 * WNT;          // block tile width
     constexpr int BLANES = BN_ / 4;        // lanes covering one B row with float4
@@ -648,7 +647,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_fast(GemmArgs p)
             }
         return;
     }
-    if constexpr (EPI == EP_DECONV_MASK && WNT == 2) {
+    if constexpr (EPI == EP_DECONV_MASK) {
         // myolo_mask_deconv + ReLU + the 1x1 myolo_mask conv (model.py:711-714) without ever writing the
         // [N,2H,2W,Co] tensor: this tile holds 128 of the Co channels of ONE tap (Co % 128 == 0) for 128 input pixels.
         // Per class, each lane forms relu(acc + bias) * w2 for its 32 row slots and 2 columns, then a 5-step
@@ -1176,7 +1175,7 @@ static int launch_nn(const GemmArgs& a, hipStream_t s, void* sk_ws = nullptr, si
     const bool aligned = (a.N & 3) == 0 && (a.ldb & 3) == 0 && ((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0;
     const bool kfast = (AMODE == AM_PLAIN) ? ((a.K % BK) == 0 && (a.lda & 3) == 0) : ((a.Cc % BK) == 0);
     GemmArgs& am = const_cast<GemmArgs&>(a);
-    am.nt = ((long long)a.M * a.N * 4 > (64ll << 20)) && !g_myolo_opt.no_nt;
+    am.nt = (long long)a.M * a.N * 4 > (64ll << 20);
     if (aligned && kfast && !g_myolo_opt.gemm_generic) {
         // under-filled grid (fewer tiles than the 1024 resident-workgroup slots) and a long K loop: split K so the
         // whole chip works on it; a lone 128x128 tile with K = 2304 takes ~185 us however few tiles there are
@@ -1191,11 +1190,6 @@ static int launch_nn(const GemmArgs& a, hipStream_t s, void* sk_ws = nullptr, si
             if (splits < 2) splits = 1;
         }
         if (path) *path = splits > 1 ? splits : 1;
-        if (g_myolo_opt.gemm_w256 && (a.N % 256) == 0 && tiles >= 1024 && !a.stat) {
-            const long long tiles256 = cdiv64(a.M, BM) * (a.N / 256);
-            hipLaunchKernelGGL((gemm_nn_fast<AMODE, EPI, 4>), dim3((unsigned)tiles256), dim3(256), 0, s, a);
-            return MYOLO_OK;
-        }
         if (splits > 1) {
             am.ksplits = splits;
             am.part = (float*)sk_ws;
@@ -1274,14 +1268,9 @@ int myolo_gemm_nn_batched(const float* A, const float* B, float* C, long long M,
     GemmArgs a = {};
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = N; a.ldc = N; a.act = MYOLO_ACT_NONE;
     a.sA = M * (long long)K; a.sB = (long long)K * N; a.sC = M * (long long)N; a.batch = batch;
-    a.nt = g_myolo_opt.wino_nt ? 1 : 0;          // the product is read back at once by the output transform
+    // (nt stays 0: the product is read back at once by the output transform)
     const long long tiles = cdiv64(M, BM) * ((N + BN - 1) / BN);
     if (tiles <= 0 || batch <= 0) return MYOLO_OK;
-    if (g_myolo_opt.wino_w256 && (N % 256) == 0) {      // tuning knob: 128x256 tiles (A read once)
-        const long long tiles256 = cdiv64(M, BM) * (N / 256);
-        hipLaunchKernelGGL((gemm_nn_fast<AM_PLAIN, EP_PLAIN, 4>), dim3((unsigned)tiles256, 1, batch), dim3(256), 0, s, a);
-        return MYOLO_OK;
-    }
     hipLaunchKernelGGL((gemm_nn_fast<AM_PLAIN, EP_PLAIN>), dim3((unsigned)tiles, 1, batch), dim3(256), 0, s, a);
     return MYOLO_OK;
 }
@@ -1441,10 +1430,10 @@ __global__ __launch_bounds__(256) void pw_bwd_data_thin_kernel(const float* __re
     }
 }
 
-// Forward of the THIN pointwise layers in training (conv_pw_1..3: 32 / 64 input, 64 / 128 output channels, 100 352 - 401 408 rows), the mirror of the
+// Forward of the THIN pointwise layers in training (conv_pw_1 / 2: 32 / 64 input, 64 output channels, 100 352 - 401 408 rows), the mirror of the
 // kernel above:  y [M][N] = act(x * in_scale + in_shift) [M][K] * w [K][N], column sums of y and y^2 for the BatchNorm that follows.
 // A wave owns 32 rows and all N columns; lane (row l31, half h) loads 16 bytes of its row per step (k = 8 j + 4 h .. + 3), normalises them in
-// registers, and reads the matching 16 bytes of w^T's row n from LDS (w, 8-32 KB, transposed into LDS once per workgroup, rows padded to K + 4
+// registers, and reads the matching 16 bytes of w^T's row n from LDS (w, 8-16 KB, transposed into LDS once per workgroup, rows padded to K + 4
 // floats: conflict-free 16-byte reads).  The statistics: 16 rows per lane in fp32, then doubles -- over the wave's row blocks, the two half-waves,
 // the four waves (LDS); one row of partials per workgroup, summed in a fixed order by the finish kernel: bit-reproducible.
 template <int NU, int NJ>
@@ -1689,10 +1678,9 @@ static void pw_smallm_launch(const GemmArgs& a, hipStream_t s)
 
 static bool pw_fwd_thin_ok(long long M, int Cin, int Cout)
 {
-    // 128 output channels (conv_pw_3, 100 352 rows = one row block per wave): 43 us here against 36 us on gemm_nn_fast -- the 32 KB of w^T every
-    // workgroup stages are not amortised; tune0 & 8192 lets the test reach that instantiation
-    return (Cin == 32 || Cin == 64) && (Cout == 64 || (Cout == 128 && (g_myolo_opt.tune0 & 8192))) && M >= 8192 && !(g_myolo_opt.tune0 & 4096) &&
-           !g_myolo_opt.no_trunk_fusion;
+    // (128 output channels, conv_pw_3 with 100 352 rows = one row block per wave: 43 us here against 36 us on gemm_nn_fast -- the 32 KB of w^T
+    // every workgroup stages are not amortised)
+    return (Cin == 32 || Cin == 64) && Cout == 64 && M >= 8192 && !g_myolo_opt.no_trunk_fusion;
 }
 
 // workgroups of pw_fwd_thin_kernel = rows of statistics partials it writes (never more than the 128-row tiles the scratch is sized for)
@@ -1711,17 +1699,15 @@ static void pw_fwd_thin_launch(const float* x, const float* in_scale, const floa
     size_t lds = (size_t)Cout * (Cin + 4) * sizeof(float);
     if (lds < (size_t)8 * Cout * sizeof(double)) lds = (size_t)8 * Cout * sizeof(double);
 #define PWT(NU_, NJ_) hipLaunchKernelGGL((pw_fwd_thin_kernel<NU_, NJ_>), dim3(wgs), dim3(256), lds, s, x, w, y, stat, M, in_scale, in_shift, in_act, o_scale, o_shift, o_act)
-    if (Cin == 32 && Cout == 64) PWT(2, 4);
-    else if (Cin == 32) PWT(4, 4);
-    else if (Cout == 64) PWT(2, 8);
-    else PWT(4, 8);
+    if (Cin == 32) PWT(2, 4);
+    else PWT(2, 8);
 #undef PWT
 }
 
 static bool pw_bwd_data_thin_ok(long long M, int Cin, int Cout)
 {
     // (Cin = 128, i.e. conv_pw_4 with 25 088 rows: 784 waves of 32 steps x 16 MFMAs each do not fill the chip -- gemm_nn_fast keeps that layer)
-    return (Cin == 32 || Cin == 64) && Cout <= 256 && (Cout % 8) == 0 && M >= 8192 && !(g_myolo_opt.tune0 & 2048);
+    return (Cin == 32 || Cin == 64) && Cout <= 256 && (Cout % 8) == 0 && M >= 8192;
 }
 
 
@@ -1735,7 +1721,7 @@ int myolo_pwconv1x1_fwd(const float* x, const float* w, const float* bias, float
     a.A = x; a.B = w; a.C = y; a.bias = bias; a.M = M; a.N = Cout; a.K = Cin;
     a.lda = Cin; a.ldb = Cout; a.ldc = Cout; a.act = MYOLO_ACT_NONE;
     if (Cout <= 64 && (Cout & 3) != 0 && (Cin & 15) == 0 && ((uintptr_t)x & 15) == 0 && !g_myolo_opt.gemm_generic) {
-        if (Cin >= 512 && (Cin & 63) == 0 && !g_myolo_opt.pw_skinny_nw4)
+        if (Cin >= 512 && (Cin & 63) == 0)
             hipLaunchKernelGGL(pw_skinny_fwd_kernel<16>, dim3((unsigned)cdiv64(M, 4)), dim3(1024), 0, (hipStream_t)stream, x, w, bias, y, (long long)M, Cin, Cout);
         else
             hipLaunchKernelGGL(pw_skinny_fwd_kernel<4>, dim3((unsigned)cdiv64(M, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, (long long)M, Cin, Cout);
@@ -1854,7 +1840,7 @@ static int pw_bwd_weight_impl(const float* x, const float* in_scale, const float
     MYOLO_REQUIRE(x && dy && dw && M > 0, "pwconv1x1_bwd_weight: bad arguments");
     if ((Cin == 32 || Cin == 64) && (Cout == 64 || Cout == 128) && M >= 16384 && !g_myolo_opt.gemm_generic) {
         // thin layer: one wave holds the whole result (pw_wgrad_thin)
-        const int nblk = M >= 300000 ? 512 : 256;     // measured: tools/pw_layers.py (tune0 is a bit mask of A/B switches: it must not size anything here)
+        const int nblk = M >= 300000 ? 512 : 256;     // measured: tools/pw_layers.py
         const size_t need = (size_t)nblk * Cin * Cout * sizeof(float);
         if (ws && need <= ws_bytes) {
             hipStream_t s = (hipStream_t)stream;
@@ -1953,7 +1939,7 @@ int myolo_pwconv1x1_bnstats_fwd(const float* x, const float* in_scale, const flo
         return MYOLO_OK;
     }
     if (pw_fwd_thin_ok(M, Cin, Cout)) {
-        // conv_pw_1..3: the register-fed kernel (pw_fwd_thin_kernel); its partial rows are one per workgroup
+        // conv_pw_1 / 2: the register-fed kernel (pw_fwd_thin_kernel); its partial rows are one per workgroup
         const int wgs = pw_fwd_thin_wgs(M);
         if (phases & 1) pw_fwd_thin_launch(x, in_scale, in_shift, in_act, w, y, part, M, Cin, Cout, s);
         MYOLO_CHECK_LAUNCH();

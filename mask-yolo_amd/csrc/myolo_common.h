@@ -7,16 +7,12 @@
 
 extern "C" void myolo_set_error(const char* fmt, ...);
 
-// Process-wide tuning switches, changed ONLY through myolo_set_option() (include/myolo_hip.h): the launch path reads
-// plain ints, never the environment.  Tuning switches default to 0 = the shipped behaviour (tn_wgs: 224, see below).
+// Process-wide switches, changed ONLY through myolo_set_option() (include/myolo_hip.h): the launch path reads plain ints, never the
+// environment.  Each kernel-choice switch reaches a path that a test holds the shipped one against, or a fallback a test must reach; 0 = the
+// shipped behaviour (tn_wgs: 224, bn_fused_tf_variance: 1, see below).
 struct MyoloOptions {
-    int no_nt;            // gemm: never use streaming (non-temporal) stores for large outputs
     int gemm_generic;     // gemm: force the generic (guarded) kernels
     int no_splitk;        // gemm: never split K for under-filled grids
-    int gemm_w256;        // gemm: 128x256 block tiles for big launches
-    int wino_nt;          // winograd multiply: streaming stores of the product
-    int wino_w256;        // winograd multiply: 128x256 block tiles
-    int bf16_regstage;    // bf16 gemm: register-staged variant instead of LDS-DMA
     int bf16_no256;       // bf16 gemm: never the 256x256-tile kernel
     int bf16_no_loopn;    // bf16 deconv+mask: a workgroup per (row tile, tap) instead of one per row tile walking all four taps (ablation)
     int bf16_mask_valu;   // bf16 deconv+mask, 256-row kernels: 1 = the 1x1 mask conv on the VALU from the fp32 deconv output (rounds 3-5) instead of on the matrix pipe from its bf16 rounding
@@ -25,23 +21,14 @@ struct MyoloOptions {
     int bf16_no_c3;       // bf16 3x3 conv: the nine-fetch implicit GEMM instead of the LDS-resident activation block (ablation)
     int bf16_force256;    // bf16 gemm: always the 256x256-tile kernel
     int crop_bf16_legacy; // bf16 ROIAlign forward: 1 = four corner loads per output element (rounds 2-5) instead of the column walk; the same bits (test reference)
-    int crop_bwd_nolds;   // ROIAlign backward: per-box terms recomputed per thread instead of staged in LDS
-    int tune0;            // scratch integer for kernel-tuning experiments (0 = off); never set by the product
-    int dw_min_wg;        // depthwise forward (row-sliding kernel): workgroups wanted before rows stop being split into chunks (0 = default 1024)
-    int dw_rows1;         // depthwise forward (round-3 kernel): one output row per thread (no vertical strip)
-    int dw_bwd_legacy;    // depthwise data gradient, stride 1: the round-3 gather kernel instead of the row-sliding one (ablation)
-    int dw_legacy;        // depthwise forward: the round-3 register-tiled kernel also where the row-sliding LDS-staged one applies (ablation)
+    int tune0;            // scratch integer of the -DMM_X6_TUNE / -DBF16_TUNE experiment builds (tools/experiments); read by no default build
     int wino_x6;          // winograd multiply on the bf16 matrix pipe: 6 piece products per fp32 product, fp32 accumulation (csrc/wino_mm.hip)
     int wino_no_bt;       // winograd multiply: gemm_nn_fast on [K][N] filters instead of wino_mm_kernel on transposed ones
     int wino_no_mixed;    // winograd: F(4,3) for every tile (no F(2,3) on the ragged last tile row / column)
     int x6_no_half_tiles; // bf16x6 plain products: 1 = keep 128 x 256 tiles when they do not fill the chip (default: 128 x 128 tiles then)
-    int w63_order;        // wino63 boundary kernels: 1 = the previous workgroup order (all images of channel slice 0, then slice 1, ...)
-    int w63_wgs;          // wino63 boundary kernels: persistent workgroups per CU (0 = default 1)
     int w63_legacy;       // wino63 boundary kernels: 1 = the round-5 kernel (scalar transforms); the packed form gives the same bits (test reference)
     int pw_x6_min_rows;   // pointwise convs: fewest rows for the bf16x6 kernels (0 = default 4096)
     int deconv_no_x6;     // deconv forward / data gradient: the fp32-MFMA kernels even when "wino_x6" is on (ablation)
-    int dw_wgrad_generic; // depthwise weight gradient: the generic 9-accumulator column reduction instead of the tiled kernel (ablation)
-    int pw_skinny_nw4;    // conv_23 (pw_skinny_fwd_kernel): four waves per workgroup also from K = 512 up (rounds 2-5; ablation -- another summation order)
     int pw_no_smallm;     // pointwise convs with few rows and K >= 256: the split-K pair of gemm_nn_fast launches instead of pw_smallm_kernel (ablation)
     int pw_no_x6;         // pointwise convs with >= 256 channels: the fp32-MFMA kernels even when "wino_x6" is on (ablation)
     int tn_no_x6;         // winograd weight gradient: gemm_tn_fast (fp32 MFMA) even when "wino_x6" is on (ablation of wino_tn_x6_kernel)

@@ -180,7 +180,6 @@ struct W63Args {
     // FROM_M with BatchNorm statistics: per-image partial sums [NR][2*C] (sum | sum of squares) of the values written to y
     double* stats;
     float* Qn;               // TO_VQ: the adjoint-output-transformed planes (TO_Q alone writes them to Vn)
-    int order;               // workgroup order, see the kernel (set by w63_launch from option "w63_order")
     // FROM_M: the value BEFORE the affine + activation (A^T m A + bias = the conv's pre-BatchNorm output) written where flags[img] != 0 (NULL:
     // everywhere); with ypre set, `flags` governs ypre and y (if any) is written everywhere.  The exact-sparsity backward reads the frozen BatchNorms'
     // backward off THIS tensor for the positive ROIs: no (a - beta) / gamma reconstruction from the post-activation value
@@ -341,8 +340,8 @@ template <int FRONT, int BACK>
 __device__ __forceinline__ void w63_unit_body(const W63Args& a, float* act_lds, long long unit)
 {
     const int ns = a.C / W63_CS;
-    const long long img = a.order ? unit / ns : unit % a.NR;
-    const int slice = (int)(a.order ? unit - img * ns : unit / a.NR);
+    const long long img = unit / ns;                 // the slices of one image are consecutive units
+    const int slice = (int)(unit - img * ns);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = slice * W63_CS + lane;
     const int ty = wave / 3, tx = wave - ty * 3;
@@ -460,7 +459,7 @@ template <int FRONT, int BACK>
 __global__ __launch_bounds__(W63_TILES * 64) void wino63_boundary_legacy_kernel(W63Args a)
 {
     extern __shared__ __attribute__((aligned(16))) float act_lds[];         // [14][14][64]
-    // workgroup -> (image, 64-channel slice).  a.order = 1: the slices of one image are consecutive workgroups
+    // workgroup -> (image, 64-channel slice): the slices of one image are consecutive workgroups
     w63_unit_body<FRONT, BACK>(a, act_lds, blockIdx.x);
 }
 
@@ -973,8 +972,6 @@ static void w63_launch_act(const W63Args& b, unsigned grid, size_t lds, hipStrea
 template <int FRONT, int BACK>
 static int w63_launch(const W63Args& a, hipStream_t s)
 {
-    W63Args b = a;
-    b.order = g_myolo_opt.w63_order ? 0 : 1;
     const long long units = a.NR * (a.C / W63_CS);
     if (units <= 0 || units >= (1LL << 31)) return MYOLO_EINVAL;
     // The ROIAlign front gathers from the (cache-resident) feature map in five dependent passes: nothing to prefetch, and what hides its latency is a
@@ -988,22 +985,21 @@ static int w63_launch(const W63Args& a, hipStream_t s)
             (void)hipFuncSetAttribute((const void*)wino63_boundary_legacy_kernel<FRONT, BACK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_set = true;
         }
-        hipLaunchKernelGGL((wino63_boundary_legacy_kernel<FRONT, BACK>), dim3((unsigned)units), dim3(W63_TILES * 64), lds, s, b);
+        hipLaunchKernelGGL((wino63_boundary_legacy_kernel<FRONT, BACK>), dim3((unsigned)units), dim3(W63_TILES * 64), lds, s, a);
         return MYOLO_OK;
     }
-    // one persistent workgroup per CU (option "w63_wgs": workgroups per CU, default 1), a multiple of the slices per image so that a workgroup's slice
+    // one persistent workgroup per CU, a multiple of the slices per image so that a workgroup's slice
     // never changes; two LDS buffers (without a back half nobody reads the tile: only the statistics' partial sums pass through LDS)
     const int ns = a.C / W63_CS;
-    const int per_cu = g_myolo_opt.w63_wgs > 0 ? g_myolo_opt.w63_wgs : 1;
-    long long grid = (long long)w63_num_cus() * per_cu;
+    long long grid = w63_num_cus();
     grid -= grid % ns;
     if (grid < ns) grid = ns;
     if (grid > units) grid = units;                                        // units % ns == 0
     const size_t lds = 2 * sizeof(float) * (BACK == W63_TO_NONE ? (size_t)2 * W63_TILES * W63_CS : (size_t)W63_HW * W63_HW * W63_CS);
     // the activation is a compile-time parameter where the kernel applies it element by element (FROM_LAZY reads it as a mask: run time)
-    if (FRONT == W63_FROM_LAZY || FRONT == W63_FROM_CROP || a.act == MYOLO_ACT_NONE) w63_launch_act<FRONT, BACK, MYOLO_ACT_NONE>(b, (unsigned)grid, lds, s);
-    else if (a.act == MYOLO_ACT_RELU) w63_launch_act<FRONT, BACK, MYOLO_ACT_RELU>(b, (unsigned)grid, lds, s);
-    else w63_launch_act<FRONT, BACK, MYOLO_ACT_RELU6>(b, (unsigned)grid, lds, s);
+    if (FRONT == W63_FROM_LAZY || FRONT == W63_FROM_CROP || a.act == MYOLO_ACT_NONE) w63_launch_act<FRONT, BACK, MYOLO_ACT_NONE>(a, (unsigned)grid, lds, s);
+    else if (a.act == MYOLO_ACT_RELU) w63_launch_act<FRONT, BACK, MYOLO_ACT_RELU>(a, (unsigned)grid, lds, s);
+    else w63_launch_act<FRONT, BACK, MYOLO_ACT_RELU6>(a, (unsigned)grid, lds, s);
     return MYOLO_OK;
 }
 

@@ -744,7 +744,7 @@ static int wino_tn_all(const float* V, const float* Q, float* dU, const TileGeom
 {
     GroupRun runs[4];
     const int n = group_runs(g, runs);
-    if (myolo_gemm_tn_x6_ok(Cin, Cout) && !(g_myolo_opt.tune0 & 32768)) {
+    if (myolo_gemm_tn_x6_ok(Cin, Cout)) {
         // FP32_MATMUL = "bf16x6": all 36 planes in one launch of wino_tn_x6_kernel, as the F(6,3) chain does (feature_map's weight gradient, 512 -> 256
         // channels on 28 x 28: 166-185 us in the step on the fp32 matrix pipe, one gemm_tn_fast launch per run of planes)
         long long rows[4], ao[4], bo[4];

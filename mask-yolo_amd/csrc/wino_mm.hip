@@ -43,7 +43,6 @@ struct MMArgs {
     float* C;
     int K, N;
     int nruns;
-    int nt;
     // MM_EP_DECONV_MASK only (csrc/gemm_kernels.hip EP_DECONV_MASK, model.py:711-714): columns = (tap, co) of a 2x2 / s2 deconv
     const float* bias;     // [Co]
     const float* w2;       // [Co][ncls]: the 1x1 mask conv
@@ -430,10 +429,7 @@ __global__ __launch_bounds__(256, 2) void wino_mm_kernel(MMArgs p)
             if (row >= M) continue;
             float* dst = Cp + row * p.N + n0 + wn * 128 + l31;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (p.nt) __builtin_nontemporal_store(acc[t][u][r], dst + 32 * u);
-                else dst[32 * u] = acc[t][u][r];
-            }
+            for (int u = 0; u < 4; ++u) dst[32 * u] = acc[t][u][r];
         }
 }
 
@@ -936,10 +932,7 @@ __global__ __launch_bounds__(256, 2) void wino_mm_x6_kernel(MMArgs p)
             if (row >= M) continue;
             float* dst = Cp + row * p.N + n0 + wn * 32 * NU + l31;
 #pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                if (p.nt) __builtin_nontemporal_store(acc[t][u][r], dst + 32 * u);
-                else dst[32 * u] = acc[t][u][r];
-            }
+            for (int u = 0; u < NU; ++u) dst[32 * u] = acc[t][u][r];
         }
 }
 
@@ -962,7 +955,7 @@ int myolo_gemm_nt_batched_runs(const float* A, const float* Bt, float* C, int nr
         return MYOLO_EINVAL;
     }
     MMArgs a{};
-    a.A = A; a.Bt = Bt; a.C = C; a.K = K; a.N = N; a.nt = g_myolo_opt.wino_nt ? 1 : 0;
+    a.A = A; a.Bt = Bt; a.C = C; a.K = K; a.N = N;
     a.tune = g_myolo_opt.tune0;
     long long tiles = 0;
     for (int r = 0; r < nruns; ++r) {
@@ -1066,7 +1059,7 @@ int myolo_deconv_mask_mm(const float* x, const float* w, const float* bias, cons
     if (finished) *finished = 0;              // 1: the kernel stored the probabilities itself (no deconv_mask_finish launch wanted)
     const int K = Cin, N = 4 * Cout;
     MMArgs a{};
-    a.A = x; a.C = nullptr; a.K = K; a.N = N; a.nruns = 1; a.nt = 0;
+    a.A = x; a.C = nullptr; a.K = K; a.N = N; a.nruns = 1;
     a.bias = bias; a.w2 = w2; a.part = part; a.H = H; a.W = W; a.Co = Cout; a.ncls = ncls;
     a.keep_inv = keep_d ? keep_inv : nullptr; a.keep_d = keep_inv ? keep_d : nullptr; a.keep_cap = keep_cap;
     MMRun& R = a.run[0];
@@ -1129,7 +1122,7 @@ int myolo_matmul_f32_impl(const float* A, const float* B, float* C, int64_t M, i
     MYOLO_NEED_WS(myolo_matmul_f32_ws_bytes(K, N, b_is_nk, products));
     hipStream_t s = (hipStream_t)stream;
     MMArgs a{};
-    a.A = A; a.C = C; a.K = K; a.N = N; a.nruns = 1; a.nt = 0;
+    a.A = A; a.C = C; a.K = K; a.N = N; a.nruns = 1;
     MMRun& R = a.run[0];
     R.rows = M; R.a_off = 0; R.b_off = 0; R.c_off = 0; R.nq = 1; R.tile0 = 0;
     R.mtiles = (int)((M + MM_BM - 1) / MM_BM);
@@ -1500,15 +1493,15 @@ int myolo_gemm_tn_x6_runs(const float* A, const float* B, float* C, int nruns, c
 /* pointwise conv of the trunk on the bf16 matrix pipe with six exact piece products (FP32_MATMUL = "bf16x6", layers with Cout % 256 == 0):
  * y [M][N] = act_in(x * in_scale + in_shift) [M][K] * w [K][N], optional per-row-tile partial sums of y's columns (stat).
  * ws: the split filters (K*N*6 bytes).  Two launches (split, GEMM). */
-// (tune0 & 65536: from 128 input channels -- conv_pw_4, 25 088 x 128 -> 256, is 34.4 -> 28.2 us stand-alone that way and the step 0.05 ms SLOWER, four runs each:
-//  one more weight split on the side stream and one more bf16-MFMA kernel in the trunk; not the default)
-bool myolo_pw_x6_ok(int K, int N) { return g_myolo_opt.wino_x6 && !g_myolo_opt.pw_no_x6 && K >= ((g_myolo_opt.tune0 & 65536) ? 128 : 256) && (K % MM_BK) == 0 && (N % MM_BN) == 0; }
+// (from 128 input channels instead, conv_pw_4, 25 088 x 128 -> 256, is 34.4 -> 28.2 us stand-alone and the step 0.05 ms SLOWER, four runs each:
+//  one more weight split on the side stream and one more bf16-MFMA kernel in the trunk)
+bool myolo_pw_x6_ok(int K, int N) { return g_myolo_opt.wino_x6 && !g_myolo_opt.pw_no_x6 && K >= 256 && (K % MM_BK) == 0 && (N % MM_BN) == 0; }
 size_t myolo_pw_x6_split_bytes(int K, int N) { return align256((size_t)K * N * 6); }
 int myolo_pw_x6_fwd(const float* x, const float* in_scale, const float* in_shift, int in_act, const float* w, float* y, double* stat,
                     long long M, int K, int N, void* split, hipStream_t s)
 {
     MMArgs a{};
-    a.A = x; a.C = y; a.K = K; a.N = N; a.nruns = 1; a.nt = 0;
+    a.A = x; a.C = y; a.K = K; a.N = N; a.nruns = 1;
     a.a_scale = in_scale; a.a_shift = in_shift; a.a_act = in_act; a.stat = stat;
 #ifdef MM_X6_TUNE
     a.tune = g_myolo_opt.tune0;

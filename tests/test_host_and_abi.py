@@ -270,7 +270,9 @@ def test_set_option_roundtrip_and_unknown_name():
     lib.myolo_get_option(b"bf16_no256", ctypes.byref(v))
     assert v.value == 1
     _ext.set_option("bf16_no256", 0)
-    assert lib.myolo_set_option(b"no_such_switch", 1) == -1 and b"unknown option" in lib.myolo_last_error_string()
+    for name in ("no_such_switch", "no_nt", "gemm_w256", "wino_nt", "wino_w256", "bf16_regstage", "crop_bwd_nolds", "dw_rows1", "dw_min_wg",
+                 "dw_legacy", "dw_bwd_legacy", "dw_wgrad_generic", "w63_order", "w63_wgs", "pw_skinny_nw4"):     # (the switches retired in version 212)
+        assert lib.myolo_set_option(name.encode(), 1) == -1 and b"unknown option" in lib.myolo_last_error_string(), name
     for src in ("gemm_kernels.hip", "mem_kernels.hip", "bf16_kernels.hip", "wino_kernels.hip", "exact_kernels.hip", "comm_rccl.hip"):
         assert "getenv" not in open(os.path.join(ROOT, "mask-yolo_amd", "csrc", src)).read(), src
 

@@ -13,22 +13,18 @@ cp gpurun_out/prof_$TAG/${TAG}_bench_kernel_stats.csv gpurun_out/prof_$TAG/${TAG
 bash tools/profile_step.sh ${TAG}_pos20 --steps 10 --force-pos 20 > /dev/null 2>&1
 cp gpurun_out/prof_${TAG}_pos20/${TAG}_pos20_bench_kernel_stats.csv gpurun_out/prof_${TAG}_pos20/${TAG}_pos20_bench_kernel_by_grid.csv gpurun_out/prof_${TAG}_pos20/${TAG}_pos20_timeline.txt gpurun_out/prof_${TAG}_pos20/${TAG}_pos20_step_sequence.txt $OUT/
 {
-  echo "--- depthwise forward as the step runs it (cold inputs); then with the round-3 kernel (dw_legacy=1)"
+  echo "--- depthwise forward as the step runs it (cold inputs)"
   python tools/kbench.py dw_fused --iters 20 2>&1 | grep -v amdgpu
-  KBENCH_OPTIONS=dw_legacy=1 python tools/kbench.py dw_fused --iters 20 2>&1 | grep -v amdgpu | tail -1
-  echo "--- depthwise data / weight gradients (cold inputs); then with the round-3 kernels (dw_bwd_legacy=1)"
+  echo "--- depthwise data / weight gradients (cold inputs)"
   python tools/kbench.py dw_bwd --iters 20 2>&1 | grep -v amdgpu
-  KBENCH_OPTIONS=dw_bwd_legacy=1 python tools/kbench.py dw_bwd --iters 20 2>&1 | grep -v amdgpu | grep total
   echo "--- BatchNorm + ReLU6 backward of the trunk layers (three launches: sums, finish, dx; cold inputs; in the step the sums of 14 of the 29 come from the depthwise data gradient's epilogue, round 5)"
   python tools/kbench.py bn_bwd --iters 20 2>&1 | grep -v amdgpu
   echo "--- pointwise layers (fp32 MFMA kernels; then wino_x6=1 = the product's FP32_MATMUL=bf16x6)"
   python tools/kbench.py pw_fused --iters 20 2>&1 | grep -v amdgpu
   KBENCH_OPTIONS=wino_x6=1 python tools/kbench.py pw_fused --iters 20 2>&1 | grep -v amdgpu
-  echo "--- ROIAlign forward / backward (backward: default, tune0=1 = round-3 pixel order, tune0=4 = 4x4 tiles)"
+  echo "--- ROIAlign forward / backward"
   python tools/kbench.py roialign_fwd --iters 20 --warm 10 2>&1 | grep -v amdgpu
   python tools/kbench.py roialign_bwd --iters 20 --warm 10 2>&1 | grep -v amdgpu
-  KBENCH_OPTIONS=tune0=1 python tools/kbench.py roialign_bwd --iters 20 --warm 10 2>&1 | grep -v amdgpu
-  KBENCH_OPTIONS=tune0=4 python tools/kbench.py roialign_bwd --iters 20 --warm 10 2>&1 | grep -v amdgpu
   echo "--- Winograd kernels, steady state (boundary: round 6 persistent kernel; then the round-5 kernel, w63_legacy=1)"
   for k in wino63_mm wino63_wgrad wino63_boundary wino63_lazy; do KBENCH_OPTIONS=wino_x6=1 python tools/kbench.py $k --warm 30 --iters 20 2>&1 | grep -vE "amdgpu.ids|^$" | tail -3; done
   for k in wino63_boundary wino63_lazy; do KBENCH_OPTIONS=wino_x6=1,w63_legacy=1 python tools/kbench.py $k --warm 30 --iters 20 2>&1 | grep -vE "amdgpu.ids|^$" | tail -3; done

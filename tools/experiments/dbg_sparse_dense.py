@@ -37,5 +37,3 @@ def run(opts):
     print(opts, seen, flush=True)
 run({})
 run({"pw_no_smallm": 1})
-run({"pw_skinny_nw4": 1})
-run({"pw_no_smallm": 1, "pw_skinny_nw4": 1})

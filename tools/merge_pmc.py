@@ -18,17 +18,13 @@ out = {"method": "tools/pmc_kbench.py: separate rocprofv3 --pmc passes (FETCH_SI
        "families": {}}
 notes = {
     "dw_fwd": "depthwise forward as the training step runs it (producer BatchNorm on load + statistics epilogue), dw_rows_kernel (round 4)",
-    "dw_fwd_round3_kernel": "the same with option dw_legacy=1: round 3's register-tiled dw_fwd_kernel",
     "dw_bwd_data_s1": "depthwise data gradient, stride 1: dw_rows_kernel with the filter rotated (round 4)",
     "dw_bwd_data": "depthwise data gradient, stride 2 layers (gather kernel; stride-1 layers no longer use it)",
-    "dw_bwd_data_round3_kernel": "option dw_bwd_legacy=1: round 3's gather kernel on every layer",
     "dw_wgrad": "depthwise weight gradient, dw_rows_wgrad_kernel (round 4)",
-    "dw_wgrad_round3_kernel": "option dw_bwd_legacy=1: round 3's dw_wgrad_kernel",
     "pw_gemm": "pointwise layers on gemm_nn_fast<PLAIN> (fp32 MFMA; every layer when wino_x6 is off, the < 256-channel ones in the product)",
     "pw_x6": "pointwise layers with >= 256 channels on wino_mm_x6_kernel<PLAIN, PW> (option wino_x6=1 = the product's FP32_MATMUL='bf16x6')",
     "crop_fwd": "ROIAlign forward, stand-alone crop_fwd_kernel (the step fuses it into conv1's Winograd input transform); algorithmic 0.970 GB",
     "crop_bwd": "ROIAlign backward, 2 x 2 pixel quads in XCD-contiguous order (round 4); algorithmic 0.944 GB read + 0.026 GB written",
-    "crop_bwd_round3_order": "option tune0=1: round 3's workgroup = four consecutive pixels, plain order",
     "dw_bwd_data_s2": "depthwise data gradient, stride 2: dw_bwd_data_s2_kernel (late round 4: a dy pixel's thread writes its 2 x 2 block of dx); algorithmic = dy + dx of dw2 / dw4 / dw7 / dw13",
     "pw_thin_fwd": "conv_pw_1 / conv_pw_2 forward on pw_fwd_thin_kernel (late round 4: register-fed fp32 MFMA, BatchNorm of the input in registers, statistics epilogue); algorithmic = x + y: 154 / 51 MB",
     "bn_bwd_sums": "BatchNorm + ReLU6 backward, pass 1 (colreduce_kernel<OpBnBwd>: reads dy and x) at the trunk shapes of tools/kbench.py bn_bwd; algorithmic = 2 x M x C x 4 bytes",

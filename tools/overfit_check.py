@@ -14,7 +14,7 @@ from myolo.model import MaskYOLO
 from myolo.shapes import make_shapes_samples
 from myolo.myolo_utils import BatchGenerator
 B = 8
-for kv in os.environ.get("MYOLO_LIB_OPTIONS", "").split(","):          # kernel selections for A/B runs, e.g. MYOLO_LIB_OPTIONS=tune0=23552
+for kv in os.environ.get("MYOLO_LIB_OPTIONS", "").split(","):          # kernel selections for A/B runs, e.g. MYOLO_LIB_OPTIONS=pw_no_smallm=1
     if "=" in kv:
         from myolo import _ext as _X
         _X.load(); _X.set_option(kv.split("=")[0], int(kv.split("=")[1]))

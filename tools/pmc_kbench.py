@@ -3,7 +3,7 @@
 /opt/skills/guides/MI355X_MICROARCH.md -- SEPARATE `rocprofv3 --pmc` passes with --kernel-trace only (FETCH_SIZE | WRITE_SIZE | an SQ set), traffic =
 2 x FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts half of a wide streaming read), KB x 1024.  Means over the last `--last` launches of each group.
 
-    python tools/pmc_kbench.py dw_fused --match dw_rows_kernel --out gpurun_out/r4_pmc_dw.json [--opts dw_legacy=1]
+    python tools/pmc_kbench.py dw_fused --match dw_rows_kernel --out pmc_dw.json [--opts wino_x6=1]
 """
 import argparse
 import collections
