@@ -256,6 +256,39 @@ int myolo_stream_copy(const void* src, void* dst, size_t nbytes, int variant, in
  * flop per launch = blocks * 4 * iters * 8 * flop-per-instruction.  `out` (blocks * 256 floats) is practically never written. */
 int myolo_mfma_probe(int kind, int iters, int blocks, float* out, void* stream);
 
+/* ---- ResNet-50 backbone (cfg.BACKBONE = "resnet50": keras_applications ResNet50 v1) : csrc/resnet_kernels.hip.  Declared here rather than in
+ * the operator API (myolo_hip.h, held to 70 entries): the engine composes the ResNet trunk from these and the existing operators ----
+ * conv1: ZeroPadding2D(3) + Conv2D 7x7 stride 2 'valid', 3 -> Cout, + bias; x [N,H,W,3], y [N,Ho,Wo,Cout], Ho = (H-1)/2+1.  An EXPLICIT im2col
+ *   ([M][160] fp32 in ws: K = 147 taps, column 147 = 1 meeting the bias as row 147 of the padded weights) followed by the pointwise MFMA GEMMs;
+ *   ws >= myolo_conv7x7s2_c3_ws_bytes (at 16 x 512^2: 671 MB of im2col matrix, written and read back by the forward and again by the weight
+ *   gradient).  _bnstats_fwd: training form, the GEMM's epilogue leaves the column sums of y (bias included) and the finish writes mean / var /
+ *   scale / shift and updates the moving statistics (as myolo_bn_stats).  _affine_act_fwd: inference form, act((conv + bias)*scale + shift) in the
+ *   GEMM's store.  bwd_weight writes dw [7,7,3,Cout] and (if non-NULL) db [Cout] (per-workgroup partials, fixed-order reduction: deterministic). */
+size_t myolo_conv7x7s2_c3_ws_bytes(int N, int H, int W, int Cout);
+int myolo_conv7x7s2_c3_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cout,
+                           void* ws, size_t ws_bytes, void* stream);
+int myolo_conv7x7s2_c3_bnstats_fwd(const float* x, const float* w, const float* bias, float* y, const float* gamma, const float* beta, float* mean,
+                                   float* var, float* scale, float* shift, float* moving_mean, float* moving_var, int N, int H, int W, int Cout,
+                                   void* ws, size_t ws_bytes, void* stream);
+int myolo_conv7x7s2_c3_affine_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift, int act, float* y,
+                                      int N, int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream);
+int myolo_conv7x7s2_c3_bwd_weight(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cout,
+                                  void* ws, size_t ws_bytes, void* stream);
+/* ZeroPadding2D(1) + MaxPool2D 3x3 stride 2 'valid' of act(x*scale + shift) (scale = shift = NULL: of x; the training step folds bn_conv1's
+ * apply + ReLU into this load).  y [N,Ho,Wo,C], arg [N,Ho,Wo,C] uint8 = row-major window index 0..8 of the first maximum (a padding cell, value 0,
+ * can win).  bwd: dx [N,H,W,C] = sum over the <= 4 windows that chose the pixel, in window order; a gradient routed to padding is dropped. */
+int myolo_maxpool3x3s2_fwd(const float* x, const float* scale, const float* shift, int act, float* y, uint8_t* arg,
+                           int N, int H, int W, int C, void* stream);
+int myolo_maxpool3x3s2_bwd(const float* dy, const uint8_t* arg, float* dx, int N, int H, int W, int C, void* stream);
+/* strided 1x1 convs: xs [N,(H-1)/2+1,(W-1)/2+1,C] = x at the even rows / columns; scatter: dx [N,H,W,C] = a + b there (b may be NULL), 0 elsewhere */
+int myolo_gather_s2(const float* x, float* xs, int N, int H, int W, int C, void* stream);
+int myolo_scatter_s2(const float* a, const float* b, float* dx, int N, int H, int W, int C, void* stream);
+/* residual join: out = ReLU(y*scale + shift + r), r = sc*sc_scale + sc_shift (projection block) or sc (identity: sc_scale = sc_shift = NULL);
+ * bwd: g = dout * [out > 0] (the gradient of both BatchNorm inputs and, in an identity block, of the block input through the shortcut) */
+int myolo_residual_fwd(const float* y, const float* scale, const float* shift, const float* sc, const float* sc_scale, const float* sc_shift,
+                       float* out, int64_t M, int C, void* stream);
+int myolo_residual_bwd(const float* dout, const float* out, float* g, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,16 @@ SIGS = {
     "myolo_pwconv1x1_bwd_weight_affine_in": [P, P, P, I, P, P, L, I, I, P, Z, P],
     "myolo_gather_groups_affine_act": [P, P, P, P, I, P, P, I, L, I, P],
     "myolo_add_inplace": [P, P, L, P],
+    "myolo_conv7x7s2_c3_fwd": [P, P, P, P, I, I, I, I, P, Z, P],
+    "myolo_conv7x7s2_c3_bnstats_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, Z, P],
+    "myolo_conv7x7s2_c3_affine_act_fwd": [P, P, P, P, P, I, P, I, I, I, I, P, Z, P],
+    "myolo_conv7x7s2_c3_bwd_weight": [P, P, P, P, I, I, I, I, P, Z, P],
+    "myolo_maxpool3x3s2_fwd": [P, P, P, I, P, P, I, I, I, I, P],
+    "myolo_maxpool3x3s2_bwd": [P, P, P, I, I, I, I, P],
+    "myolo_gather_s2": [P, P, I, I, I, I, P],
+    "myolo_scatter_s2": [P, P, P, I, I, I, I, P],
+    "myolo_residual_fwd": [P, P, P, P, P, P, P, L, I, P],
+    "myolo_residual_bwd": [P, P, P, L, P],
     "myolo_fill": [P, F, L, P],
     "myolo_u8_to_unit_f32": [P, P, L, P],
     "myolo_set_option": [ctypes.c_char_p, I],
@@ -202,6 +212,8 @@ def load():
     lib.myolo_wprep_count.restype = I
     lib.myolo_dwconv3x3_bwd_data_bnsums_rows.argtypes = [I, I, I, I, I]
     lib.myolo_dwconv3x3_bwd_data_bnsums_rows.restype = I
+    lib.myolo_conv7x7s2_c3_ws_bytes.argtypes = [I, I, I, I]
+    lib.myolo_conv7x7s2_c3_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
     lib.myolo_wprep_refresh.restype = I
     _LIB = lib
@@ -212,7 +224,8 @@ def exported_symbols():
     return list(SIGS) + ["myolo_version", "myolo_last_error_string", "myolo_workspace_bytes", "myolo_conv3x3_wino_ws_bytes", "myolo_wino_plane_elems", "myolo_wino_u_elems", "myolo_wino63_u_elems", "myolo_wino63_plane_elems", "myolo_wino63_ok", "myolo_wino63_bwd_data_ws_bytes", "myolo_wino63_bwd_weight_ws_bytes", "myolo_wino63_bwd_data_from_v_ws_bytes", "myolo_wino63_bwd_weight_from_q_ws_bytes", "myolo_wino63_output_transform_bn_ws_bytes", "myolo_conv3x3_wino63_ws_bytes", "myolo_matmul_f32_ws_bytes", "myolo_conv3x3s2_c3_bnstats_ws_bytes", "myolo_dwconv3x3_bnstats_ws_bytes", "myolo_dwconv3x3_bwd_weight_ws_bytes",
                               "myolo_pwconv1x1_bnstats_ws_bytes", "myolo_pwconv1x1_bnstats_ok",
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
-                              "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh"]
+                              "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
+                              "myolo_conv7x7s2_c3_ws_bytes"]
 
 
 def ptr(t):
@@ -411,6 +424,10 @@ def measure_mfma_tflops(iters=20000, reps=3, device="cuda:0"):
         torch.cuda.synchronize()
         res[name] = blocks * 4.0 * it * 8 * flop * reps / (e0.elapsed_time(e1) * 1e-3) / 1e12
     return res
+
+
+def conv7x7s2_ws_bytes(n, h, w, cout):
+    return int(load().myolo_conv7x7s2_c3_ws_bytes(int(n), int(h), int(w), int(cout)))
 
 
 def workspace_bytes(rows, cin, cout):

@@ -16,6 +16,8 @@ unchanged.  Two deliberate differences:
 """
 import numpy as np
 
+BACKBONES = ("mobilenet", "resnet50")
+
 
 class Config(object):
     """Base configuration class.  Sub-class and override, as in the reference."""
@@ -42,7 +44,7 @@ class Config(object):
     VALIDATION_STEPS = 5
 
     # ---- backbone (config.py:61-92) ---------------------------------------
-    BACKBONE = "mobilenet"
+    BACKBONE = "mobilenet"       # or "resnet50" (keras_applications ResNet50 v1; res3d plays C4, res4-5 the YOLO branch)
     ALPHA = 1.0                  # new: MobileNet width multiplier
     COMPUTE_BACKBONE_SHAPE = None
     BACKBONE_STRIDES = [8]
@@ -143,6 +145,10 @@ class Config(object):
         assert self.TRUE_BOX_BUFFER == self.MAX_GT_INSTANCES, \
             "BatchGenerator sizes gt arrays by both (myolo_utils.py:742-745)"
         assert int(getattr(self, "WARM_UP_BATCHES", 0)) >= 0, "WARM_UP_BATCHES counts loss evaluations (model.py:194-196)"
+        if self.BACKBONE not in BACKBONES:
+            raise ValueError("BACKBONE must be one of %s: only these are built (got %r)" % (", ".join(repr(b) for b in BACKBONES), self.BACKBONE))
+        if self.BACKBONE == "resnet50" and float(self.ALPHA) != 1.0:
+            raise ValueError("ALPHA (the MobileNet width multiplier) must be 1.0 with BACKBONE='resnet50' (got %r)" % (self.ALPHA,))
         self.TRAIN_ROIS_PER_IMAGE = self.GRID_H * self.GRID_W * self.N_BOX
         cw = np.asarray(self.CLASS_WEIGHTS, dtype='float32')
         if cw.shape[0] != self.NUM_CLASSES:

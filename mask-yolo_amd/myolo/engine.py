@@ -27,6 +27,24 @@ ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 BACKBONE_BLOCKS = [(64, 1), (64, 2), (128, 1), (256, 2), (256, 1), (512, 1)]                      # model.py:68-77
 YOLO_BLOCKS = [(512, 2), (512, 1), (512, 1), (512, 1), (512, 1), (512, 1), (1024, 2), (1024, 1)]   # model.py:256-268
 MASK_FILTERS = 256                                                                                 # model.py:688-711
+# cfg.BACKBONE = "resnet50": keras_applications ResNet50 v1 (Keras 2.2), (stage, block letters, filters of branch 2a / 2b / 2c, stride of
+# block a).  Stages 2-3 are the backbone (res3d's output, stride 8, plays C4), stages 4-5 the YOLO branch (res5c's output feeds conv_23).
+RESNET_STAGES = [(2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2), (5, "abc", (512, 512, 2048), 2)]
+RESNET_C4_STAGE = 3
+# The ResNet trunk is held to the mask-head sizes a tested config reaches: at most this many ROIs per launch (images x GRID^2 x N_BOX; BASELINE
+# configs[1], 32 x 147).  Then every tensor of the trunk stays under 1 GB as well (the largest, conv1's im2col matrix, is 640 B per conv1 output
+# pixel <= 770 MB).  16 x 512^2 (configs[4], 12 288 ROIs) has not had the audit of each launch's byte extent against its 32-bit buffer
+# descriptors (make_rsrc / mm_rsrc / w63_rsrc) and is refused.
+RESNET_MAX_MASK_ROIS = 32 * 7 * 7 * 3
+
+
+def resnet_check_size(n_images, h, w, n_box):
+    """raise unless a ResNet-50 forward of n_images h x w images stays within RESNET_MAX_MASK_ROIS mask-head ROIs"""
+    rois = int(n_images) * (int(h) // 32) * (int(w) // 32) * int(n_box)
+    if rois > RESNET_MAX_MASK_ROIS:
+        raise ValueError("BACKBONE='resnet50': %d images of %dx%d with N_BOX=%d give %d mask-head ROIs per launch; only up to %d are supported "
+                         "(larger launches have not been audited against the kernels' 32-bit buffer descriptors)"
+                         % (n_images, h, w, n_box, rois, RESNET_MAX_MASK_ROIS))
 # classes above this take the mask loss / 1x1 backward that carry only the selected class's logit gradient (myolo_mask_bce_sel,
 # myolo_mask_head_out_bwd_sel: dz_sel [rows] + the class ids in place of a dense dz [rows, C]); up to it, the dense kernels
 MASK_DENSE_MAX_CLASSES = 8
@@ -45,7 +63,15 @@ def layer_table(cfg):
     buffer is laid out bucket by bucket, so each is one contiguous slice): 0 backbone (complete at the end of the step), 1 YOLO blocks + conv_23
     (complete when the YOLO head's backward retires, under the mask head's forward), 2 feature_map, 3 myolo_mask_conv1 + bn1 (conv1's dense weight
     gradient: late), 4 the rest of the mask head (complete when the compact chain's weight gradients retire).  Same flat layout as rounds 1-5."""
-    a, C = cfg.ALPHA, cfg.NUM_CLASSES
+    if getattr(cfg, "BACKBONE", "mobilenet") == "resnet50":
+        t, cin, c4 = _resnet_trunk_table()
+    else:
+        t, cin, c4 = _mobilenet_trunk_table(cfg)
+    return t + _head_table(cfg, cin, c4)
+
+
+def _mobilenet_trunk_table(cfg):
+    a = cfg.ALPHA
     t = [("conv1", "conv", (3, 3, 3, int(32 * a)), 0), ("conv1_bn", "bn", int(32 * a), 0)]
     cin, bid = int(32 * a), 1
     blocks = [(f, s, 0) for f, s in BACKBONE_BLOCKS] + [(f, s, 1) for f, s in YOLO_BLOCKS]
@@ -57,7 +83,36 @@ def layer_table(cfg):
             c4 = co
         cin = co
         bid += 1
-    t += [("conv_23", "convb", (1, 1, cin, cfg.N_BOX * (5 + C)), BUCKET_YOLO),
+    return t, cin, c4
+
+
+def resnet_block_names(stage, block):
+    """(conv name base, BatchNorm name base) of a bottleneck block: 'res3a_branch' / 'bn3a_branch' + '2a' | '2b' | '2c' | '1'"""
+    return "res%d%s_branch" % (stage, block), "bn%d%s_branch" % (stage, block)
+
+
+def _resnet_trunk_table():
+    """conv1 / bn_conv1 and the 16 bottleneck blocks in keras_applications' layer order; every Conv2D has a bias (use_bias defaults to True)"""
+    t = [("conv1", "convb", (7, 7, 3, 64), BUCKET_BACKBONE), ("bn_conv1", "bn", 64, BUCKET_BACKBONE)]
+    cin = 64
+    for st, blocks, (f1, f2, f3), _ in RESNET_STAGES:
+        bk = BUCKET_BACKBONE if st <= RESNET_C4_STAGE else BUCKET_YOLO
+        for b in blocks:
+            cb, bb = resnet_block_names(st, b)
+            t += [(cb + "2a", "convb", (1, 1, cin, f1), bk), (bb + "2a", "bn", f1, bk),
+                  (cb + "2b", "convb", (3, 3, f1, f2), bk), (bb + "2b", "bn", f2, bk),
+                  (cb + "2c", "convb", (1, 1, f2, f3), bk), (bb + "2c", "bn", f3, bk)]
+            if b == "a":
+                t += [(cb + "1", "convb", (1, 1, cin, f3), bk), (bb + "1", "bn", f3, bk)]
+            cin = f3
+        if st == RESNET_C4_STAGE:
+            c4 = cin
+    return t, cin, c4
+
+
+def _head_table(cfg, cin, c4):
+    C = cfg.NUM_CLASSES
+    t = [("conv_23", "convb", (1, 1, cin, cfg.N_BOX * (5 + C)), BUCKET_YOLO),
           ("feature_map", "convb", (3, 3, c4, cfg.TOP_FEATURE_MAP_DEPTH), BUCKET_FEATURE_MAP)]
     cm = cfg.TOP_FEATURE_MAP_DEPTH
     for i in range(1, 5):
@@ -69,6 +124,20 @@ def layer_table(cfg):
     return t
 
 
+def _he_normal(rng, shape, fan_in):
+    """Keras 2.2 he_normal: VarianceScaling(2, 'fan_in', 'normal') = a normal of sigma sqrt(2 / fan_in) truncated at two sigma (redrawn)"""
+    z = rng.standard_normal(size=shape)
+    bad = np.abs(z) > 2.0
+    while bad.any():
+        z[bad] = rng.standard_normal(size=int(bad.sum()))
+        bad = np.abs(z) > 2.0
+    return (z * np.sqrt(2.0 / fan_in)).astype(np.float32)
+
+
+def _is_resnet_layer(name):
+    return name == "conv1" or name.startswith("res")
+
+
 def _glorot(rng, shape, fan_in, fan_out):
     lim = np.sqrt(6.0 / (fan_in + fan_out))
     return rng.uniform(-lim, lim, size=shape).astype(np.float32)
@@ -76,13 +145,18 @@ def _glorot(rng, shape, fan_in, fan_out):
 
 def init_state_dict(cfg, seed=0):
     """Keras default initialisers: glorot_uniform kernels, zero biases, BN gamma=1 beta=0,
-    moving mean 0 / variance 1.  Same draw order on every rank (seeded)."""
+    moving mean 0 / variance 1.  Same draw order on every rank (seeded).  The ResNet-50 trunk's convs (cfg.BACKBONE = "resnet50") follow
+    keras_applications: he_normal kernels."""
     rng = np.random.default_rng(seed)
     sd = {}
+    resnet = getattr(cfg, "BACKBONE", "mobilenet") == "resnet50"
     for name, kind, shp, _ in layer_table(cfg):
         if kind in ("conv", "convb"):
             kh, kw, ci, co = shp
-            sd[name + "/kernel"] = _glorot(rng, shp, kh * kw * ci, kh * kw * co)
+            if resnet and _is_resnet_layer(name):
+                sd[name + "/kernel"] = _he_normal(rng, shp, kh * kw * ci)
+            else:
+                sd[name + "/kernel"] = _glorot(rng, shp, kh * kw * ci, kh * kw * co)
             if kind == "convb":
                 sd[name + "/bias"] = np.zeros(co, np.float32)
         elif kind == "dw":
@@ -175,6 +249,7 @@ class Net(object):
         X.load()
         self.cfg = cfg
         self.dev = torch.device(device)
+        self.resnet = getattr(cfg, "BACKBONE", "mobilenet") == "resnet50"
         self.table = layer_table(cfg)
         # ---- flat parameter / BN-state layout ----
         self.pslots, self.sslots = {}, {}
@@ -592,7 +667,7 @@ class Net(object):
         if self._fz_table is None:
             rows, off = [], 0
             self._fz_slot = {}
-            for name in sorted(k[:-len("/gamma")] for k in self.pslots if k.endswith("_bn/gamma") and (k.startswith("conv_dw_") or k.startswith("conv_pw_") or k.startswith("conv1_bn/"))):
+            for name in sorted(k[:-len("/gamma")] for k in self.pslots if self._trunk_bn(k)):
                 C = int(self.p[name + "/gamma"].numel())
                 rows.append([self.pslots[name + "/gamma"][0], self.pslots[name + "/beta"][0], self.sslots[name + "/moving_mean"][0],
                              self.sslots[name + "/moving_variance"][0], off, C])
@@ -602,6 +677,14 @@ class Net(object):
             self._fz_coeffs = torch.empty(off, dtype=torch.float32, device=self.dev)
         X.call("myolo_bn_frozen_coeffs_batched", X.ptr(self.flat_p), X.ptr(self.flat_s), self._fz_table.data_ptr(), int(self._fz_table.shape[0]),
                X.ptr(self._fz_coeffs), X.stream())
+
+    def _trunk_bn(self, key):
+        """key '<layer>/gamma' of a trunk BatchNorm (the ones _frozen_affine_all covers)"""
+        if not key.endswith("/gamma"):
+            return False
+        if self.resnet:
+            return key.startswith("bn_conv1/") or (key.startswith("bn") and key[2:3].isdigit())
+        return key.endswith("_bn/gamma") and (key.startswith("conv_dw_") or key.startswith("conv_pw_") or key.startswith("conv1_bn/"))
 
     def _frozen_affine(self, name):
         off, C = self._fz_slot[name]
@@ -738,6 +821,8 @@ class Net(object):
 
     # ---- trunk: backbone, feature_map, YOLO head -----------------------------------
     def trunk_fwd(self, images, train):
+        if self.resnet:
+            return self._rn_trunk_fwd(images, train)
         cfg = self.cfg
         N, H, W, _ = images.shape
         C0 = self.p["conv1/kernel"].shape[3]
@@ -816,6 +901,8 @@ class Net(object):
 
     def yolo_head_bwd(self, dyolo):
         """conv_23 and the YOLO blocks (conv_dw/pw_7..14) backward: returns the gradient reaching C4 through the YOLO head."""
+        if self.resnet:
+            return self._rn_yolo_head_bwd(dyolo)
         C4, c4shape, a14, s14 = self.tape["trunk"]
         n2, h2, w2, c2 = s14
         D = dyolo.shape[1]
@@ -882,17 +969,236 @@ class Net(object):
         # a reducer was attached).
         self._release(BUCKET_FEATURE_MAP, self._wgrad_side)
         da = dC4
-        for _ in BACKBONE_BLOCKS:
-            da = self.dw_block_bwd(bid, da, next_bn=("conv_pw_%d_bn" % (bid - 1)) if bid > 1 else "conv1_bn", wside=self._yolo_side)
-            bid -= 1
-        dy = self.bn_act_bwd("conv1_bn", da)
-        images = self.tape["images"]
-        N, H, W, _ = images.shape
-        C0 = self.p["conv1/kernel"].shape[3]
-        X.call("myolo_conv3x3s2_c3_bwd_weight", X.ptr(images), X.ptr(dy), X.ptr(self.g["conv1/kernel"]), N, H, W, C0, *self._wsargs(), X.stream())
+        if self.resnet:
+            self._rn_backbone_bwd(da)
+        else:
+            for _ in BACKBONE_BLOCKS:
+                da = self.dw_block_bwd(bid, da, next_bn=("conv_pw_%d_bn" % (bid - 1)) if bid > 1 else "conv1_bn", wside=self._yolo_side)
+                bid -= 1
+            dy = self.bn_act_bwd("conv1_bn", da)
+            images = self.tape["images"]
+            N, H, W, _ = images.shape
+            C0 = self.p["conv1/kernel"].shape[3]
+            X.call("myolo_conv3x3s2_c3_bwd_weight", X.ptr(images), X.ptr(dy), X.ptr(self.g["conv1/kernel"]), N, H, W, C0, *self._wsargs(), X.stream())
         self.join_trunk_wgrad()
         if self.on_bucket_ready:
             self.on_bucket_ready(BUCKET_BACKBONE)
+
+    # ---- ResNet-50 trunk (cfg.BACKBONE = "resnet50") --------------------------------------------------------------------
+    # Same contract as the MobileNet trunk: trunk_fwd returns (feature_map output, its shape, YOLO output) and leaves tape["trunk"] =
+    # (C4, its shape, conv_23's input, its shape); yolo_head_bwd returns the gradient reaching C4 through stages 4-5; the weight gradients run
+    # beside the data-gradient chain on the same side streams.  Every BatchNorm is kept as its coefficients (bnbuf[name][2:4]: batch statistics in
+    # training, the moving statistics otherwise) and applied where its output is read: bn_conv1 + ReLU in the max-pool's load, branch 2c and the
+    # projection shortcut's BatchNorm in the residual join; branches 2a / 2b through one apply + ReLU pass each.
+    def _rn_bn(self, name, y, act, train):
+        """BatchNorm coefficients of y [M,C] -> (scale, shift) device pointers; tapes (y, act, train) for bn_act_bwd"""
+        M, C = y.shape
+        if train:
+            buf = self.bnbuf[name]
+            X.call("myolo_bn_stats", X.ptr(y), *[X.ptr(t) for t in (self.p[name + "/gamma"], self.p[name + "/beta"], buf[0], buf[1], buf[2], buf[3],
+                   self.s[name + "/moving_mean"], self.s[name + "/moving_variance"])], M, C, *self._wsargs(), X.stream())
+            self.tape[name] = (y, act, True)
+            return X.ptr(buf[2]), X.ptr(buf[3])
+        if self.fold_frozen_bn:
+            return self._frozen_affine(name)              # (computed for every trunk BatchNorm at the start of the forward)
+        buf = self.bnbuf[name]
+        X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]), X.ptr(self.s[name + "/moving_mean"]),
+               X.ptr(self.s[name + "/moving_variance"]), X.ptr(buf[2]), X.ptr(buf[3]), C, X.stream())
+        return X.ptr(buf[2]), X.ptr(buf[3])
+
+    def _rn_bn_relu(self, name, y, train):
+        sc, sh = self._rn_bn(name, y, ACT_RELU, train)
+        a = self._new(*y.shape)
+        X.call("myolo_bn_apply_act", X.ptr(y), sc, sh, X.ptr(a), y.shape[0], y.shape[1], ACT_RELU, X.stream())
+        return a
+
+    def _rn_pw_fwd(self, x, M, layer):
+        k = self.p[layer + "/kernel"]
+        ci, co = int(k.shape[2]), int(k.shape[3])
+        y = self._new(M, co)
+        X.call("myolo_pwconv1x1_fwd", X.ptr(x), X.ptr(k), X.ptr(self.p[layer + "/bias"]), X.ptr(y), M, ci, co, *self._wsargs(), X.stream())
+        return y
+
+    def _rn_block_fwd(self, st, b, a, shape, stride, train):
+        """one bottleneck block: a [N*H*W, C] -> (ReLU(BN(2c) + shortcut) [N*Ho*Wo, f3], new shape)"""
+        N, H, W, C = shape
+        cb, bb = resnet_block_names(st, b)
+        f1, f2, f3 = (int(self.p[cb + s + "/kernel"].shape[3]) for s in ("2a", "2b", "2c"))
+        if stride == 2:             # 1x1 / s2 'valid' of branch 2a and branch 1: both read the even rows / columns, gathered once
+            Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+            xs = self._new(N * Ho * Wo, C)
+            X.call("myolo_gather_s2", X.ptr(a), X.ptr(xs), N, H, W, C, X.stream())
+        else:
+            Ho, Wo, xs = H, W, a
+        M = N * Ho * Wo
+        self.ws.ensure(X.workspace_bytes(M, max(C, f2), max(f1, f3)))
+        a2a = self._rn_bn_relu(bb + "2a", self._rn_pw_fwd(xs, M, cb + "2a"), train)
+        y2b = self._new(M, f2)
+        self.conv3x3_fwd(a2a, cb + "2b", y2b, N, Ho, Wo, f1, f2)
+        a2b = self._rn_bn_relu(bb + "2b", y2b, train)
+        y2c = self._rn_pw_fwd(a2b, M, cb + "2c")
+        s2c, t2c = self._rn_bn(bb + "2c", y2c, ACT_NONE, train)
+        if b == "a":
+            y1 = self._rn_pw_fwd(xs, M, cb + "1")
+            s1, t1 = self._rn_bn(bb + "1", y1, ACT_NONE, train)
+            sc = y1
+        else:
+            assert stride == 1 and C == f3
+            sc, s1, t1 = a, None, None
+        out = self._new(M, f3)
+        X.call("myolo_residual_fwd", X.ptr(y2c), s2c, t2c, X.ptr(sc), s1, t1, X.ptr(out), M, f3, X.stream())
+        if train:
+            self.tape[cb] = (shape, stride, xs, a2a, a2b, out)
+        return out, (N, Ho, Wo, f3)
+
+    def _rn_trunk_fwd(self, images, train):
+        cfg = self.cfg
+        N, H, W, _ = images.shape
+        if not train and self.fold_frozen_bn:
+            self._frozen_affine_all()
+        resnet_check_size(N, H, W, cfg.N_BOX)
+        C0 = int(self.p["conv1/kernel"].shape[3])
+        Hs, Ws = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y0 = self._new(N * Hs * Ws, C0)
+        self.ws.ensure(max(X.conv7x7s2_ws_bytes(N, H, W, C0), X.workspace_bytes(N * Hs * Ws, C0, C0)))
+        stem = (X.ptr(images), X.ptr(self.p["conv1/kernel"]), X.ptr(self.p["conv1/bias"]))
+        Hp, Wp = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+        a = self._new(N * Hp * Wp, C0)
+        arg = self._new(N * Hp * Wp * C0, dtype=torch.uint8)
+        if train:
+            # the conv's GEMM leaves bn_conv1's column sums in its epilogue; bn_conv1's apply + ReLU happen in the max-pool's load, so the
+            # normalised conv1 output is never written
+            X.call("myolo_conv7x7s2_c3_bnstats_fwd", *stem, X.ptr(y0), *self._bn_args("bn_conv1"), N, H, W, C0, *self._wsargs(), X.stream())
+            self.tape["bn_conv1"] = (y0, ACT_RELU, True)
+            buf = self.bnbuf["bn_conv1"]
+            pool_in = (X.ptr(buf[2]), X.ptr(buf[3]), ACT_RELU)
+        elif self.fold_frozen_bn:
+            # inference: the frozen bn_conv1 + ReLU in the conv's store
+            sc, sh = self._frozen_affine("bn_conv1")
+            X.call("myolo_conv7x7s2_c3_affine_act_fwd", *stem, sc, sh, ACT_RELU, X.ptr(y0), N, H, W, C0, *self._wsargs(), X.stream())
+            pool_in = (None, None, ACT_NONE)
+        else:
+            X.call("myolo_conv7x7s2_c3_fwd", *stem, X.ptr(y0), N, H, W, C0, *self._wsargs(), X.stream())
+            sc, sh = self._rn_bn("bn_conv1", y0, ACT_RELU, train)
+            pool_in = (sc, sh, ACT_RELU)
+        # ZeroPadding(1) + max-pool 3x3/s2
+        X.call("myolo_maxpool3x3s2_fwd", X.ptr(y0), *pool_in, X.ptr(a), X.ptr(arg), N, Hs, Ws, C0, X.stream())
+        if train:
+            self.tape["stem"] = (images, (N, Hs, Ws, C0), arg)
+            self._wprep_wait(0)
+        shape = (N, Hp, Wp, C0)
+        for st, blocks, _, stride in RESNET_STAGES:
+            for i, b in enumerate(blocks):
+                a, shape = self._rn_block_fwd(st, b, a, shape, stride if i == 0 else 1, train)
+            if st == RESNET_C4_STAGE:
+                if train:
+                    self._wprep_phase2()
+                C4, c4shape = a, shape
+                n, h, w, c = c4shape
+                Cf = cfg.TOP_FEATURE_MAP_DEPTH
+                Fm = self._new(n * h * w, Cf)
+                self.conv3x3_fwd(C4, "feature_map", Fm, n, h, w, c, Cf)
+        n2, h2, w2, c2 = shape
+        D = cfg.N_BOX * (5 + cfg.NUM_CLASSES)
+        yo = self._new(n2 * h2 * w2, D)
+        X.call("myolo_pwconv1x1_fwd", X.ptr(a), X.ptr(self.p["conv_23/kernel"]), X.ptr(self.p["conv_23/bias"]), X.ptr(yo),
+               n2 * h2 * w2, c2, D, *self._wsargs(), X.stream())
+        self.tape["trunk"] = (C4, c4shape, a, shape)
+        if train:
+            self._wprep_mark_trunk()
+            self._wprep_wait(1)
+        return Fm, (n, h, w, Cf), yo
+
+    def _rn_pw_wgrad(self, wside, x, dy, layer, M):
+        """kernel and bias gradients of a 1x1 conv with bias, on the weight-gradient side"""
+        k = self.p[layer + "/kernel"]
+        ci, co = int(k.shape[2]), int(k.shape[3])
+        with self._on(wside, x, dy):
+            self.ws.ensure(X.workspace_bytes(M, ci, co))
+            X.call("myolo_pwconv1x1_bwd_weight", X.ptr(x), X.ptr(dy), X.ptr(self.g[layer + "/kernel"]), M, ci, co, *self._wsargs(), X.stream())
+            self.colsum(dy, self.g[layer + "/bias"])
+
+    def _rn_pw_bwd_data(self, dy, layer, M):
+        k = self.p[layer + "/kernel"]
+        ci, co = int(k.shape[2]), int(k.shape[3])
+        dx = self._new(M, ci)
+        X.call("myolo_pwconv1x1_bwd_data", X.ptr(dy), X.ptr(k), X.ptr(dx), M, ci, co, *self._wsargs(), X.stream())
+        return dx
+
+    def _rn_block_bwd(self, st, b, dout, wside):
+        """gradient of a bottleneck block's output -> gradient of its input.  The conv biases sit in front of training-mode BatchNorms: their
+        gradient is the column sum of the BatchNorm input's gradient (zero up to rounding)."""
+        cb, bb = resnet_block_names(st, b)
+        # (the tape is read, not popped: it keeps these tensors alive until the step ends.  This backward may run on the YOLO-head stream, and
+        # tensors the compute stream allocated in the forward must not go back to its pool while this stream still reads them)
+        shape, stride, xs, a2a, a2b, out = self.tape[cb]
+        N, H, W, C = shape
+        M, f3 = out.shape
+        f1, f2 = int(a2a.shape[1]), int(a2b.shape[1])
+        Ho, Wo = (H, W) if stride == 1 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+        self.ws.ensure(X.workspace_bytes(M, max(C, f2), max(f1, f3)))
+        g = self._new(M, f3)
+        X.call("myolo_residual_bwd", X.ptr(dout), X.ptr(out), X.ptr(g), M * f3, X.stream())
+        dy2c = self.bn_act_bwd(bb + "2c", g)
+        self._rn_pw_wgrad(wside, a2b, dy2c, cb + "2c", M)
+        dy2b = self.bn_act_bwd(bb + "2b", self._rn_pw_bwd_data(dy2c, cb + "2c", M))
+        with self._on(wside, a2a, dy2b):
+            self.ws.ensure(X.workspace_bytes(M, f1, f2))
+            self.conv3x3_bwd_weight(a2a, None, dy2b, cb + "2b", N, Ho, Wo, f1, f2)
+            self.colsum(dy2b, self.g[cb + "2b/bias"])
+        da2a = self._new(M, f1)
+        self.conv3x3_bwd_data(dy2b, cb + "2b", da2a, N, Ho, Wo, f1, f2)
+        dy2a = self.bn_act_bwd(bb + "2a", da2a)
+        self._rn_pw_wgrad(wside, xs, dy2a, cb + "2a", M)
+        dxs = self._rn_pw_bwd_data(dy2a, cb + "2a", M)
+        if b != "a":                               # identity shortcut
+            X.call("myolo_add_inplace", X.ptr(dxs), X.ptr(g), dxs.numel(), X.stream())
+            return dxs
+        dy1 = self.bn_act_bwd(bb + "1", g)
+        self._rn_pw_wgrad(wside, xs, dy1, cb + "1", M)
+        dxs1 = self._rn_pw_bwd_data(dy1, cb + "1", M)
+        if stride == 1:
+            X.call("myolo_add_inplace", X.ptr(dxs), X.ptr(dxs1), dxs.numel(), X.stream())
+            return dxs
+        dx = self._new(N * H * W, C)
+        X.call("myolo_scatter_s2", X.ptr(dxs), X.ptr(dxs1), X.ptr(dx), N, H, W, C, X.stream())
+        return dx
+
+    def _rn_yolo_head_bwd(self, dyolo):
+        """conv_23 and stages 4-5 backward: the gradient reaching C4 (res3d's output) through the YOLO branch"""
+        C4, c4shape, a5, s5 = self.tape["trunk"]
+        n2, h2, w2, c2 = s5
+        D = dyolo.shape[1]
+        M = n2 * h2 * w2
+        self.ws.ensure(X.workspace_bytes(M, c2, D))
+        X.call("myolo_pwconv1x1_bwd_weight", X.ptr(a5), X.ptr(dyolo), X.ptr(self.g["conv_23/kernel"]), M, c2, D, *self._wsargs(), X.stream())
+        self.colsum(dyolo, self.g["conv_23/bias"])
+        da = self._new(M, c2)
+        X.call("myolo_pwconv1x1_bwd_data", X.ptr(dyolo), X.ptr(self.p["conv_23/kernel"]), X.ptr(da), M, c2, D, *self._wsargs(), X.stream())
+        for st, blocks, _, _ in reversed(RESNET_STAGES):
+            if st <= RESNET_C4_STAGE:
+                break
+            for b in reversed(blocks):
+                da = self._rn_block_bwd(st, b, da, self._wgrad_side)
+        return da
+
+    def _rn_backbone_bwd(self, dC4):
+        """stages 3-2, the max-pool, bn_conv1 and conv1's weight / bias gradients (their weight gradients beside the chain on the YOLO-head
+        stream, idle by now, as the MobileNet backbone's)"""
+        da = dC4
+        for st, blocks, _, _ in reversed(RESNET_STAGES):
+            if st > RESNET_C4_STAGE:
+                continue
+            for b in reversed(blocks):
+                da = self._rn_block_bwd(st, b, da, self._yolo_side)
+        images, (N, Hs, Ws, C0), arg = self.tape["stem"]
+        dact = self._new(N * Hs * Ws, C0)
+        X.call("myolo_maxpool3x3s2_bwd", X.ptr(da), X.ptr(arg), X.ptr(dact), N, Hs, Ws, C0, X.stream())
+        dy0 = self.bn_act_bwd("bn_conv1", dact)             # ReLU mask re-formed from the saved pre-BN conv1 output
+        H, W = images.shape[1], images.shape[2]
+        self.ws.ensure(max(X.conv7x7s2_ws_bytes(N, H, W, C0), X.workspace_bytes(N * Hs * Ws, C0, C0)))
+        X.call("myolo_conv7x7s2_c3_bwd_weight", X.ptr(images), X.ptr(dy0), X.ptr(self.g["conv1/kernel"]), X.ptr(self.g["conv1/bias"]), N, H, W, C0,
+               *self._wsargs(), X.stream())
 
     def _box_image_index(self, B, R):
         """box_ind of crop_and_resize for R boxes per image (cached: no host-synchronising op in the step / under graph capture)."""
@@ -1726,7 +2032,8 @@ class Net(object):
             elif v.dim() >= 2:
                 n += int(v.numel()) * 10
             n += 512
-        return int(min(max(n, 64 << 20), 768 << 20))
+        # the ResNet-50 net's 3x3 kernels alone need ~1.1 GB by this formula (11.3 M weights x 96 B): its cap is 1.5 GiB
+        return int(min(max(n, 64 << 20), (1536 if self.resnet else 768) << 20))
 
     def _wprep_phase2(self):
         """the preparations the mask head and the backward will ask for (Winograd filter transforms, transposes, splits: ~0.25 ms of small kernels):

@@ -253,7 +253,7 @@ class MaskYOLO(object):
         if w % 32 != 0 or h % 32 != 0:
             raise Exception("Image size must be dividable by 32 to adapt with YOLO framework. "
                             "For example, use 224, 256, 288, 320, 356, ... etc. ")
-        assert config.BACKBONE == "mobilenet"          # model.py:62
+        # (the reference asserts BACKBONE == "mobilenet", model.py:62; Config.finalize() accepts "mobilenet" and "resnet50" and rejects the rest)
         net = Net(config, device=self._device, seed=self._seed)
         if self.yolo_pretrain_dir is not None:          # model.py:854-868
             self._load_npz_into(net, self.yolo_pretrain_dir, by_name=True)
