@@ -1326,6 +1326,13 @@ size_t myolo_workspace_bytes(int64_t rows, int cin, int cout)
     size_t b = tn_ws_bytes(rows, 4 * cout, cin);
     size_t c = (size_t)9 * cin * cout * sizeof(float);          // transformed weights
     size_t m = a > b ? a : b;
+    if ((cin % 256) == 0 && (cout % 256) == 0 && cin > 0 && cout > 0) {
+        // the pointwise weight gradient's bf16x6 form (wino_tn_x6_kernel's partials): with less than this pw_bwd_weight_impl runs the fp32 kernel instead
+        const long long r[1] = {rows};
+        const int nq[1] = {1};
+        const size_t x6 = myolo_gemm_tn_x6_ws_bytes(1, r, nq, cin, cout);
+        if (x6 > m) m = x6;
+    }
     return align256(m > c ? m : c) + align256(c) + (size_t)(1 << 20);
 }
 
@@ -1665,8 +1672,11 @@ static int pw_smallm_T(long long M, int K, int N)
 }
 static bool pw_smallm_ok(const GemmArgs& a)
 {
-    return pw_smallm_T(a.M, a.K, a.N) != 0 && (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C) & 15) == 0 && (a.lda & 3) == 0 && (a.ldb & 3) == 0 &&
-           (a.ldc & 3) == 0 && !g_myolo_opt.gemm_generic;
+    // (a_scale / a_shift, when given, are read as float4 beside the A operand, as in every other kernel that takes them: null pointers pass the mask;
+    // myolo_pwconv1x1_bnstats_fwd realigns an unaligned pair before it dispatches, myolo_pwconv1x1_bwd_weight_affine_in refuses one)
+    return pw_smallm_T(a.M, a.K, a.N) != 0 &&
+           (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C | (uintptr_t)a.a_scale | (uintptr_t)a.a_shift) & 15) == 0 && (a.lda & 3) == 0 &&
+           (a.ldb & 3) == 0 && (a.ldc & 3) == 0 && !g_myolo_opt.gemm_generic;
 }
 static void pw_smallm_launch(const GemmArgs& a, hipStream_t s)
 {
@@ -1827,8 +1837,9 @@ int myolo_pwconv1x1_bwd_weight(const float* x, const float* dy, float* dw,
 int myolo_pwconv1x1_bwd_weight_affine_in(const float* x, const float* in_scale, const float* in_shift, int in_act, const float* dy, float* dw,
                                          int64_t M, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream)
 {
-    MYOLO_REQUIRE(in_scale && in_shift && (Cin & 3) == 0 && (Cout & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
-                  !g_myolo_opt.gemm_generic, "pwconv1x1_bwd_weight_affine_in: needs in_scale / in_shift, Cin %% 4 == 0, Cout %% 4 == 0, 16-byte aligned operands");
+    MYOLO_REQUIRE(in_scale && in_shift && (Cin & 3) == 0 && (Cout & 3) == 0 &&
+                  (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)in_scale | (uintptr_t)in_shift) & 15) == 0 && !g_myolo_opt.gemm_generic,
+                  "pwconv1x1_bwd_weight_affine_in: needs in_scale / in_shift, Cin %% 4 == 0, Cout %% 4 == 0, 16-byte aligned operands and coefficients");
     return pw_bwd_weight_impl(x, in_scale, in_shift, in_act, dy, dw, M, Cin, Cout, ws, ws_bytes, stream);
 }
 
@@ -1920,6 +1931,18 @@ int myolo_pwconv1x1_bnstats_fwd(const float* x, const float* in_scale, const flo
                   "pwconv1x1_bnstats_fwd: needs Cin %% 16 == 0, Cout %% 4 == 0 and 16-byte aligned operands");
     MYOLO_NEED_WS(myolo_pwconv1x1_bnstats_ws_bytes(M, Cin, Cout));
     hipStream_t s = (hipStream_t)stream;
+    if (in_scale && (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) != 0) {
+        // every kernel below reads the coefficients as float4 beside the A operand: a pair that is not 16-byte aligned is copied to the aligned
+        // end of the workspace first (2 x Cin floats), and the kernels see the rest of it
+        const size_t coef = align256((size_t)Cin * sizeof(float));
+        const size_t need = myolo_pwconv1x1_bnstats_ws_bytes(M, Cin, Cout) + 2 * coef + 256;
+        if (ws_bytes < need) { myolo_set_error("pwconv1x1_bnstats_fwd: unaligned in_scale / in_shift need %zu bytes of workspace (%zu given)", need, ws_bytes); return MYOLO_EWORKSPACE; }
+        float* cs = (float*)(((uintptr_t)ws + ws_bytes - 2 * coef) & ~(uintptr_t)255);
+        (void)hipMemcpyAsync(cs, in_scale, (size_t)Cin * sizeof(float), hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync((char*)cs + coef, in_shift, (size_t)Cin * sizeof(float), hipMemcpyDeviceToDevice, s);
+        in_scale = cs; in_shift = (const float*)((char*)cs + coef);
+        ws_bytes = (size_t)((char*)cs - (char*)ws);
+    }
     GemmArgs a = {};
     a.A = x; a.B = w; a.C = y; a.M = M; a.N = Cout; a.K = Cin;
     a.lda = Cin; a.ldb = Cout; a.ldc = Cout; a.act = MYOLO_ACT_NONE;

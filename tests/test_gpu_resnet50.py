@@ -294,9 +294,9 @@ def gpu_decisions(net):
     return out
 
 
-def _cfg(nc, B=2, **kw):
+def _cfg(nc, B=2, size=128, **kw):
     labels = ["background"] + ["class%d" % i for i in range(1, nc)]
-    return make_config(ShapesConfig, BACKBONE="resnet50", IMAGE_SHAPE=[128, 128, 3], BATCH_SIZE=B, NUM_CLASSES=nc, LABELS=labels, **kw)
+    return make_config(ShapesConfig, BACKBONE="resnet50", IMAGE_SHAPE=[size, size, 3], BATCH_SIZE=B, NUM_CLASSES=nc, LABELS=labels, **kw)
 
 
 def _params(cfg, seed):
@@ -317,11 +317,14 @@ def _params(cfg, seed):
 _CASES = {}
 
 
-def resnet_case(nc, seed=0, need_pos=2, min_margin=1e-3, min_roi_px=4e-3):
-    """first seeded Shapes batch (class ids remapped into 1..80 at nc = 81) with positives and safe decision margins (test_gpu_step._make_case)"""
-    if nc in _CASES:
-        return _CASES[nc]
-    cfg = _cfg(nc)
+def resnet_case(nc, seed=0, need_pos=2, min_margin=1e-3, min_roi_px=4e-3, size=128, batch=2, oracle=None):
+    """first seeded Shapes batch (class ids remapped into 1..80 at nc = 81) with positives and safe decision margins (test_gpu_step._make_case)
+    -> (cfg, P, batch, unforced oracle's results).  size, batch: image side and images per step.  oracle(ref, batch): what to run on the screened
+    batch instead of the whole unforced train_step (the full-size tests take a forward only: tests/test_gpu_resnet50_fullsize.py)."""
+    key = (nc, size, batch)
+    if key in _CASES:
+        return _CASES[key]
+    cfg = _cfg(nc, B=batch, size=size)
     P = _params(cfg, seed)
     B = cfg.BATCH_SIZE
     for start in range(0, 200 * B, B):
@@ -340,10 +343,10 @@ def resnet_case(nc, seed=0, need_pos=2, min_margin=1e-3, min_roi_px=4e-3):
             continue
         mg = decision_margins(cfg, batch, yo, prop, rois, Fm.shape[2])
         if min(mg["partition"], mg["noobj"]) > min_margin and mg["roi_px"] > min_roi_px:
-            out = ref.train_step(batch)
+            out = ref.train_step(batch) if oracle is None else oracle(ref, batch)
             out.update(target_mask=tmask, n_pos=npos, bn_batch=dict(ref.bn_batch))
-            _CASES[nc] = (cfg, P, batch, out)
-            return _CASES[nc]
+            _CASES[key] = (cfg, P, batch, out)
+            return _CASES[key]
     raise RuntimeError("no batch with positive ROIs and safe decision margins found")
 
 
@@ -355,15 +358,10 @@ def _bn_of_bias(k):
     return "bn" + layer[3:] if layer.startswith("res") else None
 
 
-@pytest.mark.parametrize("fp32_matmul", ["bf16x6", "native"])
-@pytest.mark.parametrize("nc", [4, 81])
-def test_train_step_matches_oracle(nc, fp32_matmul):
-    """One step against the float64 oracle.  The oracle takes the trunk's activation decisions (ReLU masks, max-pool argmax) from the GPU's
-    forward: every ReLU is a hard branch on an activation with ~1e-5 fp32 noise, and at 128^2 stage 5 normalises 32 rows per channel, so a
-    single branch taken the other way behind one BatchNorm moves every gradient below it by a few percent (measured: 1.5-2.9 % relative L2 from
-    one flip behind bn5c_branch2a).  Screening the case for trunk margins is no way out: stages 4-5 alone hold ~1.5 M pre-ReLU values, ~10 of
-    them within fp32 noise of 0 in any batch.  With the decisions shared, the backward's arithmetic is held to the 2 % bound."""
-    cfg, P, batch, screen = resnet_case(nc)
+def step_against_oracle(case, fp32_matmul, forced_oracle=lambda P, cfg, seen, batch, out: ResNetRef(P, cfg, forced=seen).train_step(batch)):
+    """one training step of the engine on `case` (resnet_case) against the float64 oracle run with the GPU's trunk decisions; forced_oracle(P, cfg,
+    decisions, batch, the engine's results) runs that oracle.  -> {gradient key: relative L2 error}"""
+    cfg, P, batch, screen = case
     cfg = make_config(type(cfg), FP32_MATMUL=fp32_matmul)
     model = MaskYOLO(mode="training", config=cfg)
     assert model.net.resnet and model.net.fp32_matmul == fp32_matmul
@@ -374,7 +372,7 @@ def test_train_step_matches_oracle(nc, fp32_matmul):
     grads = model.net.grads_dict()
     torch.cuda.synchronize()
     # the shared decisions differ from the oracle's own in a handful of elements at most
-    ref = ResNetRef(P, cfg, forced=seen).train_step(batch)
+    ref = forced_oracle(P, cfg, seen, batch, out)
     assert np.array_equal(out["target_class_ids"], ref["target_class_ids"])
     assert np.array_equal(out["n_pos"], screen["n_pos"])
     assert np.array_equal(out["target_mask"], screen["target_mask"])
@@ -403,6 +401,18 @@ def test_train_step_matches_oracle(nc, fp32_matmul):
     # the trunk, where no mask-head branch decision is left to move anything (the shared decisions cover all of its own)
     trunk = {k: e for k, e in worst.items() if not (k.startswith("myolo_mask") or k.startswith("feature_map"))}
     assert max(trunk.values()) < 0.02, max(trunk.items(), key=lambda kv: kv[1])
+    return worst
+
+
+@pytest.mark.parametrize("fp32_matmul", ["bf16x6", "native"])
+@pytest.mark.parametrize("nc", [4, 81])
+def test_train_step_matches_oracle(nc, fp32_matmul):
+    """One step against the float64 oracle.  The oracle takes the trunk's activation decisions (ReLU masks, max-pool argmax) from the GPU's
+    forward: every ReLU is a hard branch on an activation with ~1e-5 fp32 noise, and at 128^2 stage 5 normalises 32 rows per channel, so a
+    single branch taken the other way behind one BatchNorm moves every gradient below it by a few percent (measured: 1.5-2.9 % relative L2 from
+    one flip behind bn5c_branch2a).  Screening the case for trunk margins is no way out: stages 4-5 alone hold ~1.5 M pre-ReLU values, ~10 of
+    them within fp32 noise of 0 in any batch.  With the decisions shared, the backward's arithmetic is held to the 2 % bound."""
+    step_against_oracle(resnet_case(nc), fp32_matmul)
 
 
 def test_adam_update_and_moving_statistics_match_oracle():
