@@ -289,6 +289,19 @@ int myolo_residual_fwd(const float* y, const float* scale, const float* shift, c
                        float* out, int64_t M, int C, void* stream);
 int myolo_residual_bwd(const float* dout, const float* out, float* g, int64_t n, void* stream);
 
+/* ---- evaluation (myolo/evaluate.py): pixel overlaps between the PASTED masks of selected detections and ground-truth planes, counted on the
+ * device -- the paste of myolo_unmold_masks (same device function, same pixels) without writing or downloading a full-size mask.  Declared here
+ * rather than in the operator API (myolo_hip.h, held to 70 entries).
+ * masks [B,R,mh,mw,C] and det [B,R,6] as the inference graph returns them; sel [B,K] int32 (device) = the rows of det chosen per image, < 0 = empty
+ * slot, K <= 16; sel_host = the same [B,K] values in host memory, read before anything is launched (a value >= R is refused: the selection is made
+ * on the host from the downloaded detections, so the caller has them); gt_masks [B,H,W,T] uint8 0 / 1, T <= 32.
+ * inter [B,K,T] = pixels set in both pasted mask k and plane t; area_pred [B,K], area_gt [B,T] = pixels set in each; win [B,K,4] = the clamped
+ * pixel window [x1,y1,x2,y2) of the paste; all int32, zeros for an empty slot.  Integer atomics only: bit-identical from run to run.
+ * ws: B * K int32. */
+int myolo_mask_overlap_counts(const float* masks, const float* det, const int32_t* sel, const int32_t* sel_host, const uint8_t* gt_masks,
+                              int32_t* inter, int32_t* area_pred, int32_t* area_gt, int32_t* win, int B, int R, int K, int T, int mh, int mw,
+                              int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -366,21 +366,71 @@ __global__ __launch_bounds__(256) void yolo_loss_kernel(LossArgs a)
 // skimage.transform.resize(..., clip=True) clips its output to the value range of the INPUT mask.  With the zero border of
 // mode='constant' that matters in exactly one case for the 0.5 threshold: a mask whose minimum is already >= 0.5 keeps its rim
 // (the fade towards 0 is clipped back up to the minimum).  allhigh[n] = 1 for such a detection (its class channel).
+// sel (NULL: block n reads row n): block n = slot (image n / K, slot n % K) reads row sel[n] of that image's R rows; an empty slot (sel < 0) gets 0
 __global__ __launch_bounds__(256) void unmold_allhigh_kernel(const float* __restrict__ masks, const float* __restrict__ det,
-                                                             int32_t* __restrict__ allhigh, int mh, int mw, int C)
+                                                             int32_t* __restrict__ allhigh, int mh, int mw, int C,
+                                                             const int32_t* __restrict__ sel, int K, int R)
 {
     __shared__ int low;
-    const int n = blockIdx.x;
+    long long n = blockIdx.x;
+    if (sel) {
+        const int s = sel[blockIdx.x];
+        if (s < 0 || s >= R) {
+            if (threadIdx.x == 0) allhigh[blockIdx.x] = 0;
+            return;
+        }
+        n = (long long)(blockIdx.x / K) * R + s;
+    }
     if (threadIdx.x == 0) low = 0;
     __syncthreads();
-    const int cls = (int)det[(long long)n * 6 + 5];
-    const float* m = masks + (long long)n * mh * mw * C + cls;
+    const int cls = (int)det[n * 6 + 5];
+    const float* m = masks + n * mh * mw * C + cls;
     int mine = 0;
     for (int i = threadIdx.x; i < mh * mw; i += blockDim.x)
         if (!(m[(long long)i * C] >= 0.5f)) mine = 1;
     if (mine) low = 1;
     __syncthreads();
-    if (threadIdx.x == 0) allhigh[n] = low ? 0 : 1;
+    if (threadIdx.x == 0) allhigh[blockIdx.x] = low ? 0 : 1;
+}
+
+// the clamped pixel window of one detection d = [x1, y1, x2, y2, score, class] (normalised corners)
+__device__ __forceinline__ void unmold_window(const float* __restrict__ d, int H, int W, int& x1, int& y1, int& x2, int& y2)
+{
+    // image_shape[0] is used for x and [1] for y (myolo_utils.py:892); square images here
+    x1 = min(max(0, (int)(d[0] * (float)W)), W), x2 = min(max(1, (int)(d[2] * (float)W)), W);
+    y1 = min(max(0, (int)(d[1] * (float)H)), H), y2 = min(max(1, (int)(d[3] * (float)H)), H);
+}
+
+// the pasted pixel (x, y) of one detection: d its row, m0 its [mh][mw][C] mask block, allhigh its flag.  The ONE statement of the paste:
+// unmold_kernel writes this byte, mask_overlap_kernel counts it.
+__device__ __forceinline__ uint8_t unmold_pixel(const float* __restrict__ d, const float* __restrict__ m0, int allhigh, int x, int y, int mh,
+                                                int mw, int C, int H, int W)
+{
+    int x1, y1, x2, y2;
+    unmold_window(d, H, W, x1, y1, x2, y2);
+    uint8_t v = 0;
+    if (y >= y1 && y < y2 && x >= x1 && x < x2) {
+        const int oh = max(1, y2 - y1), ow = max(1, x2 - x1);
+        const int cls = (int)d[5];
+        const float sy = (float)mh / (float)oh, sx = (float)mw / (float)ow;
+        float fy = ((float)(y - y1) + 0.5f) * sy - 0.5f;
+        float fx = ((float)(x - x1) + 0.5f) * sx - 0.5f;
+        // skimage.transform.resize(order=1, mode='constant', cval=0) as the reference calls it (myolo_utils.py:433-447, 903):
+        // samples outside the 28x28 mask read 0 (NOT the edge value), so an up-scaled mask fades to 0 over the outermost
+        // half source pixel -- pinned against scikit-image 0.18.3 in tests/golden/skimage_resize_fixture.npz
+        const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
+        const int yb = y0 + 1, xb = x0 + 1;
+        const float wy = fy - (float)y0, wx = fx - (float)x0;
+        const float* m = m0 + cls;
+        const bool y0in = (unsigned)y0 < (unsigned)mh, ybin = (unsigned)yb < (unsigned)mh;
+        const bool x0in = (unsigned)x0 < (unsigned)mw, xbin = (unsigned)xb < (unsigned)mw;
+        const float tl = (y0in && x0in) ? m[((long long)y0 * mw + x0) * C] : 0.f, tr = (y0in && xbin) ? m[((long long)y0 * mw + xb) * C] : 0.f;
+        const float bl = (ybin && x0in) ? m[((long long)yb * mw + x0) * C] : 0.f, br = (ybin && xbin) ? m[((long long)yb * mw + xb) * C] : 0.f;
+        const float top = tl + (tr - tl) * wx;
+        const float bot = bl + (br - bl) * wx;
+        v = ((top + (bot - top) * wy) >= 0.5f || allhigh) ? 1 : 0;        // clip=True: see unmold_allhigh_kernel
+    }
+    return v;
 }
 
 __global__ __launch_bounds__(256) void unmold_kernel(const float* __restrict__ masks, const float* __restrict__ det,
@@ -394,33 +444,113 @@ __global__ __launch_bounds__(256) void unmold_kernel(const float* __restrict__ m
         const int n = (int)(i % N);
         const int pix = (int)(i / N);
         const int y = pix / W, x = pix - y * W;
-        const float* d = det + (long long)n * 6;
-        // image_shape[0] is used for x and [1] for y (myolo_utils.py:892); square images here
-        int x1 = min(max(0, (int)(d[0] * (float)W)), W), x2 = min(max(1, (int)(d[2] * (float)W)), W);
-        int y1 = min(max(0, (int)(d[1] * (float)H)), H), y2 = min(max(1, (int)(d[3] * (float)H)), H);
-        uint8_t v = 0;
-        if (y >= y1 && y < y2 && x >= x1 && x < x2) {
-            const int oh = max(1, y2 - y1), ow = max(1, x2 - x1);
-            const int cls = (int)d[5];
-            const float sy = (float)mh / (float)oh, sx = (float)mw / (float)ow;
-            float fy = ((float)(y - y1) + 0.5f) * sy - 0.5f;
-            float fx = ((float)(x - x1) + 0.5f) * sx - 0.5f;
-            // skimage.transform.resize(order=1, mode='constant', cval=0) as the reference calls it (myolo_utils.py:433-447, 903):
-            // samples outside the 28x28 mask read 0 (NOT the edge value), so an up-scaled mask fades to 0 over the outermost
-            // half source pixel -- pinned against scikit-image 0.18.3 in tests/golden/skimage_resize_fixture.npz
-            const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-            const int yb = y0 + 1, xb = x0 + 1;
-            const float wy = fy - (float)y0, wx = fx - (float)x0;
-            const float* m = masks + (long long)n * mh * mw * C + cls;
-            const bool y0in = (unsigned)y0 < (unsigned)mh, ybin = (unsigned)yb < (unsigned)mh;
-            const bool x0in = (unsigned)x0 < (unsigned)mw, xbin = (unsigned)xb < (unsigned)mw;
-            const float tl = (y0in && x0in) ? m[((long long)y0 * mw + x0) * C] : 0.f, tr = (y0in && xbin) ? m[((long long)y0 * mw + xb) * C] : 0.f;
-            const float bl = (ybin && x0in) ? m[((long long)yb * mw + x0) * C] : 0.f, br = (ybin && xbin) ? m[((long long)yb * mw + xb) * C] : 0.f;
-            const float top = tl + (tr - tl) * wx;
-            const float bot = bl + (br - bl) * wx;
-            v = ((top + (bot - top) * wy) >= 0.5f || allhigh[n]) ? 1 : 0;        // clip=True: see unmold_allhigh_kernel
+        out[i] = unmold_pixel(det + (long long)n * 6, masks + (long long)n * mh * mw * C, allhigh[n], x, y, mh, mw, C, H, W);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Overlap counts for evaluation (myolo/evaluate.py): for every image b, selected detection k (row sel[b][k] of the image's R
+// rows, < 0 = empty slot) and ground-truth plane t of gt [B][H][W][T] (0 / 1 bytes), the number of pixels set in both the
+// PASTED mask of k -- unmold_pixel, the byte unmold_kernel would write -- and plane t; plus each pasted mask's and each plane's
+// own pixel count and the paste window.  No full-size mask is written.
+// One workgroup = OV_GROUPS consecutive groups of 64 pixels (row-major) of one image, a wave per group: a ballot turns each of
+// the K paste decisions and each of the T ground-truth bytes of the group's 64 pixels into one 64-bit word, the K x T
+// intersections are popcounts of ANDs spread over the lanes (pair q = lane + 64 j; the words go through LDS), accumulated in
+// registers over the wave's groups, summed over the four waves and added into the zeroed outputs with integer atomics
+// (integer sums: the order cannot matter).  A group's 64 T ground-truth bytes are contiguous and 64-byte aligned relative to
+// the buffer: 16-byte loads, transposed through LDS (gt_vec: the buffer itself is 16-byte aligned; the last, partial group
+// of an image reads bytes).
+// ---------------------------------------------------------------------------------------
+#define OV_MAXK 16
+#define OV_MAXT 32
+#define OV_GROUPS 16
+#define OV_PAIRS ((OV_MAXK * OV_MAXT) / 64)
+
+__global__ __launch_bounds__(256) void mask_overlap_kernel(const float* __restrict__ masks, const float* __restrict__ det,
+                                                           const int32_t* __restrict__ sel, const int32_t* __restrict__ allhigh,
+                                                           const uint8_t* __restrict__ gt, int32_t* __restrict__ inter,
+                                                           int32_t* __restrict__ area_pred, int32_t* __restrict__ area_gt,
+                                                           int32_t* __restrict__ win, int R, int K, int T, int mh, int mw, int C, int H, int W,
+                                                           int gt_vec)
+{
+    __shared__ uint4 gtL[4][OV_MAXT * 4];                          // one group's 64 x T bytes per wave
+    __shared__ unsigned long long pwL[4][OV_MAXK], gwL[4][OV_MAXT];
+    __shared__ int red[4][OV_PAIRS + 2][64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.y;
+    const int P = H * W, ngroups = (P + 63) / 64, KT = K * T;
+    int acc[OV_PAIRS], accP = 0, accG = 0;
+#pragma unroll
+    for (int j = 0; j < OV_PAIRS; ++j) acc[j] = 0;
+
+    for (int it = 0; it < OV_GROUPS / 4; ++it) {
+        const int g = blockIdx.x * OV_GROUPS + it * 4 + wave;
+        const bool live = g < ngroups;                             // the same for the whole wave
+        const int p = g * 64 + lane;
+        const bool inimg = live && p < P;
+        if (live) {
+            const long long byte0 = ((long long)b * P + (long long)g * 64) * T;
+            if (gt_vec && g * 64 + 64 <= P) {
+                const uint4* src = (const uint4*)(gt + byte0);
+                for (int j = lane; j < 4 * T; j += 64) gtL[wave][j] = src[j];
+            } else {
+                uint8_t* dst = (uint8_t*)gtL[wave] + lane * T;
+                for (int t = 0; t < T; ++t) dst[t] = inimg ? gt[byte0 + (long long)lane * T + t] : (uint8_t)0;
+            }
         }
-        out[i] = v;
+        __syncthreads();
+        if (live) {
+            const uint8_t* mine = (const uint8_t*)gtL[wave] + lane * T;
+            for (int t = 0; t < T; ++t) {
+                const unsigned long long w = __ballot(mine[t] != 0);
+                if (lane == 0) gwL[wave][t] = w;
+            }
+            const int y = p / W, x = p - y * W;
+            for (int k = 0; k < K; ++k) {
+                const int s = sel[b * K + k];
+                int v = 0;
+                if (s >= 0 && s < R && inimg) {
+                    const long long row = (long long)b * R + s;
+                    v = unmold_pixel(det + row * 6, masks + row * mh * mw * C, allhigh[b * K + k], x, y, mh, mw, C, H, W);
+                }
+                const unsigned long long w = __ballot(v);
+                if (lane == 0) pwL[wave][k] = w;
+            }
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < OV_PAIRS; ++j) {
+                const int q = lane + 64 * j;
+                if (q < KT) acc[j] += __popcll(pwL[wave][q / T] & gwL[wave][q % T]);
+            }
+            if (lane < K) accP += __popcll(pwL[wave][lane]);
+            if (lane < T) accG += __popcll(gwL[wave][lane]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < OV_PAIRS; ++j) red[wave][j][lane] = acc[j];
+    red[wave][OV_PAIRS][lane] = accP;
+    red[wave][OV_PAIRS + 1][lane] = accG;
+    __syncthreads();
+    for (int q = tid; q < KT; q += 256) {
+        const int s = red[0][q >> 6][q & 63] + red[1][q >> 6][q & 63] + red[2][q >> 6][q & 63] + red[3][q >> 6][q & 63];
+        if (s) atomicAdd(inter + (long long)b * KT + q, s);
+    }
+    if (tid < K) {
+        const int s = red[0][OV_PAIRS][tid] + red[1][OV_PAIRS][tid] + red[2][OV_PAIRS][tid] + red[3][OV_PAIRS][tid];
+        if (s) atomicAdd(area_pred + (long long)b * K + tid, s);
+    }
+    if (tid < T) {
+        const int s = red[0][OV_PAIRS + 1][tid] + red[1][OV_PAIRS + 1][tid] + red[2][OV_PAIRS + 1][tid] + red[3][OV_PAIRS + 1][tid];
+        if (s) atomicAdd(area_gt + (long long)b * T + tid, s);
+    }
+    if (blockIdx.x == 0 && tid < K) {
+        const int s = sel[b * K + tid];
+        int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+        if (s >= 0 && s < R) unmold_window(det + ((long long)b * R + s) * 6, H, W, x1, y1, x2, y2);
+        int32_t* o = win + ((long long)b * K + tid) * 4;
+        o[0] = x1, o[1] = y1, o[2] = x2, o[3] = y2;
     }
 }
 
@@ -606,12 +736,40 @@ int myolo_unmold_masks(const float* masks, const float* detections, uint8_t* ful
     MYOLO_REQUIRE(masks && detections && full_masks && N > 0 && mh > 0 && mw > 0 && C > 0 && H > 0 && W > 0, "unmold_masks: bad arguments");
     MYOLO_NEED_WS((size_t)N * sizeof(int32_t));
     int32_t* allhigh = (int32_t*)ws;
-    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, masks, detections, allhigh, mh, mw, C);
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, masks, detections, allhigh, mh, mw, C,
+                       (const int32_t*)nullptr, 1, N);
     const long long total = (long long)H * W * N;
     long long blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(unmold_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, masks, detections, allhigh, full_masks, N,
                        mh, mw, C, H, W);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+int myolo_mask_overlap_counts(const float* masks, const float* det, const int32_t* sel, const int32_t* sel_host, const uint8_t* gt_masks,
+                              int32_t* inter, int32_t* area_pred, int32_t* area_gt, int32_t* win, int B, int R, int K, int T, int mh, int mw,
+                              int C, int H, int W, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(masks && det && sel && sel_host && gt_masks && inter && area_pred && area_gt && win, "mask_overlap_counts: null pointer");
+    MYOLO_REQUIRE(B > 0 && R > 0 && mh > 0 && mw > 0 && C > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 31) - 64,
+                  "mask_overlap_counts: bad sizes");
+    MYOLO_REQUIRE(K > 0 && K <= OV_MAXK && T > 0 && T <= OV_MAXT, "mask_overlap_counts: need 1 <= K <= %d and 1 <= T <= %d (got K=%d, T=%d)",
+                  OV_MAXK, OV_MAXT, K, T);
+    for (long long i = 0; i < (long long)B * K; ++i)
+        MYOLO_REQUIRE(sel_host[i] < R, "mask_overlap_counts: sel[%lld] = %d is not a row of the %d detections", i, sel_host[i], R);
+    MYOLO_REQUIRE(ws && ws_bytes >= (size_t)B * K * sizeof(int32_t), "mask_overlap_counts: workspace too small (%zu needed, %zu given)",
+                  (size_t)B * K * sizeof(int32_t), ws_bytes);
+    int32_t* allhigh = (int32_t*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipMemsetAsync(inter, 0, (size_t)B * K * T * sizeof(int32_t), s);
+    (void)hipMemsetAsync(area_pred, 0, (size_t)B * K * sizeof(int32_t), s);
+    (void)hipMemsetAsync(area_gt, 0, (size_t)B * T * sizeof(int32_t), s);
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(B * K), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
+    const int ngroups = (H * W + 63) / 64;
+    hipLaunchKernelGGL(mask_overlap_kernel, dim3((ngroups + OV_GROUPS - 1) / OV_GROUPS, B), dim3(256), 0, s, masks, det, sel,
+                       (const int32_t*)allhigh, gt_masks, inter, area_pred, area_gt, win, R, K, T, mh, mw, C, H, W,
+                       ((uintptr_t)gt_masks & 15) == 0 ? 1 : 0);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -59,6 +59,7 @@ SIGS = {
     "myolo_shapes_batch": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, Z, P],
     "myolo_unmold_masks": [P, P, P, I, I, I, I, I, I, P, Z, P],
     "myolo_mask_targets": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "myolo_mask_overlap_counts": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, Z, P],
     "myolo_mask_head_out_fwd": [P, P, P, P, L, I, I, P],
     "myolo_conv3x3_wino_fwd": [P, P, P, P, P, P, I, I, I, I, I, I, P, P, Z, P],
     "myolo_wino63_weight_transform": [P, P, I, I, P],

@@ -13,6 +13,7 @@ yolo_branch_graph :249-278; feature_map :848; DecodeYOLOLayer :1442-1473; Detect
 compile :1062-1094 (loss sum + Adam).
 """
 import contextlib
+import gc
 import os
 import threading
 import time
@@ -2466,6 +2467,11 @@ class Net(object):
                 self.predict(static_in)
         cur.wait_stream(side)
         torch.cuda.synchronize()
+        # the cyclic collector is parked while the stream captures (torch.cuda.graph collects once on entry): a collection that starts in the
+        # middle of the capture runs the destructors of whatever garbage it finds -- an earlier model's graphs, pinned buffers, events -- and
+        # the HIP calls those make are not permitted in a capturing process (the runtime aborts)
+        gc_was = gc.isenabled()
+        gc.disable()
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
@@ -2476,6 +2482,9 @@ class Net(object):
             warnings.warn("hipGraph capture of the inference forward failed (%s: %s); launching eagerly" % (type(e).__name__, e))
             torch.cuda.synchronize()
             return (None, None, None)
+        finally:
+            if gc_was:
+                gc.enable()
 
     def predict_stream(self, batches, in_flight=2):
         """Throughput form of the inference forward: a generator over `batches` (an iterable of [B,H,W,3] device tensors of one shape)
@@ -2510,6 +2519,34 @@ class Net(object):
             pending.append((ev, outs))
         while pending:
             yield hand_out()
+
+    def overlap_counts(self, det_d, mask_d, sel, gt_masks):
+        """Pixel overlaps of the pasted masks of selected detections with ground-truth planes, counted on the device
+        (myolo_mask_overlap_counts, include/myolo_hip_internal.h): det_d [B,R,6], mask_d [B,R,mh,mw,C] as predict returns them,
+        sel [B,K] int32 in HOST memory (a numpy array or a CPU tensor; a pinned tensor goes up without blocking) = rows of det_d per image,
+        -1 = empty slot, K <= 16; gt_masks [B,H,W,T] uint8 0 / 1 device tensor, T <= 32.
+        -> device int32 tensors inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4] ([x1,y1,x2,y2) of the paste)."""
+        sel_h = sel if torch.is_tensor(sel) else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32))
+        if sel_h.is_cuda or sel_h.dtype != torch.int32 or sel_h.dim() != 2:
+            raise ValueError("overlap_counts: sel must be a [B,K] int32 array in host memory")
+        sel_h = sel_h.contiguous()
+        det_d, mask_d, gt_masks = det_d.contiguous(), mask_d.contiguous(), gt_masks.contiguous()
+        B, R = int(det_d.shape[0]), int(det_d.shape[1])
+        K = int(sel_h.shape[1])
+        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
+        H, W, T = int(gt_masks.shape[1]), int(gt_masks.shape[2]), int(gt_masks.shape[3])
+        if (det_d.dtype != torch.float32 or mask_d.dtype != torch.float32 or gt_masks.dtype != torch.uint8 or tuple(mask_d.shape[:2]) != (B, R)
+                or int(det_d.shape[2]) != 6 or int(gt_masks.shape[0]) != B or int(sel_h.shape[0]) != B):
+            raise ValueError("overlap_counts: det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, gt_masks [B,H,W,T] u8 expected")
+        sel_d = sel_h.to(self.dev, non_blocking=True)
+        # one buffer: [inter | area_pred | area_gt | win | allhigh scratch]
+        n = (B * K * T, B * K, B * T, B * K * 4, B * K)
+        buf = torch.empty(sum(n), dtype=torch.int32, device=self.dev)
+        inter, area_pred, area_gt, win, scratch = torch.split(buf, list(n))
+        X.call("myolo_mask_overlap_counts", X.ptr(mask_d), X.ptr(det_d), X.ptr(sel_d), sel_h.data_ptr(), X.ptr(gt_masks), inter.data_ptr(),
+               area_pred.data_ptr(), area_gt.data_ptr(), win.data_ptr(), B, R, K, T, mh, mw, C, H, W, scratch.data_ptr(), scratch.numel() * 4,
+               X.stream())
+        return inter.view(B, K, T), area_pred.view(B, K), area_gt.view(B, T), win.view(B, K, 4)
 
     def predict_yolo(self, images):
         """'yolo' mode forward (model.py:906-920)."""

@@ -591,20 +591,13 @@ class MaskYOLO(object):
 
     def _select_and_unmold(self, det_img, mask_img, image_shape, cs_threshold, feature=None, det_host=None):
         """detect()'s post-processing of ONE image: det_img [R,6], mask_img [R,mh,mw,C] (None: the mask head runs here, on the survivors) device tensors."""
-        cfg = self.config
         det_d, mask_d = det_img.unsqueeze(0), None if mask_img is None else mask_img.unsqueeze(0)
         selected_only = mask_img is None
         # decode_masks (model.py:1330-1391) unmolds every box and the caller then keeps <= 10 of them (model.py:1290-1304);
         # the selection needs only boxes / scores / classes, so it runs first and only the survivors are unmolded
         # (same output: full_masks[:, :, nmb] of the all-box result).
         det_h = det_d[0].cpu().numpy() if det_host is None else det_host          # (detect_many: one download per batch)
-        boxes, scores, class_ids = det_h[:, :4], det_h[:, 4], det_h[:, 5].astype(np.int32)
-        keep = np.where((boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) > 0)[0]     # model.py:1373-1380
-        boxes, scores, class_ids = boxes[keep], scores[keep], class_ids[keep]
-        top10 = np.argsort(scores)[::-1][:10]
-        kept = np.array([i for i in top10 if scores[i] >= cs_threshold], dtype=np.int64)
-        nmb = mutils.NMB(boxes[kept], class_ids[kept], kept, cfg.IMAGE_SHAPE, nms_threshold=0.7) if len(kept) else kept
-        nmb = np.asarray(nmb, dtype=np.int64)
+        keep, nmb, boxes, scores, class_ids = self._select(det_h, cs_threshold)
         if len(nmb):
             # (the few indices go up from a pinned buffer without blocking; the download of the pasted masks below ends every image with a
             # synchronisation, so the buffer is free again by the next one)
@@ -628,6 +621,130 @@ class MaskYOLO(object):
             "confidence_scores": scores[nmb],
             "full_masks": full_masks,
         }
+
+    def _select(self, det_h, cs_threshold):
+        """detect()'s selection on the host copy det_h [R,6] of one image's detections (model.py:1290-1304, 1373-1380): drop the zero-area boxes,
+        take the top 10 by score, drop those under cs_threshold, NMB at 0.7.  -> keep (rows of det_h with area), nmb (the survivors, indices
+        into keep, in the order detect() reports them), and boxes / scores / class_ids of the keep rows.  The selected rows of det_h are keep[nmb]."""
+        boxes, scores, class_ids = det_h[:, :4], det_h[:, 4], det_h[:, 5].astype(np.int32)
+        keep = np.where((boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) > 0)[0]     # model.py:1373-1380
+        boxes, scores, class_ids = boxes[keep], scores[keep], class_ids[keep]
+        top10 = np.argsort(scores)[::-1][:self.EVAL_SLOTS]
+        kept = np.array([i for i in top10 if scores[i] >= cs_threshold], dtype=np.int64)
+        nmb = mutils.NMB(boxes[kept], class_ids[kept], kept, self.config.IMAGE_SHAPE, nms_threshold=0.7) if len(kept) else kept
+        return keep, np.asarray(nmb, dtype=np.int64), boxes, scores, class_ids
+
+    # ------------------------------------------------------------------ evaluation
+    EVAL_SLOTS = 10            # detect() keeps at most the top 10 detections of an image
+
+    def evaluate(self, dataset, cs_threshold=0.35, max_samples=None, in_flight=3):
+        """Mask and box average precision of detect()'s output on a dataset (myolo/evaluate.py) -> Evaluator.result().
+        dataset: an object load_image_gt reads (as train() takes), or a sequence of (image, class_ids, boxes, masks) rows as load_image_gt
+        returns them.  The images stream through the inference graph exactly as in detect_many and every image gets detect()'s own selection;
+        the overlap of each selected detection's PASTED mask with each ground-truth mask is counted on the device (myolo_mask_overlap_counts:
+        the paste of myolo_unmold_masks, pixel for pixel) -- K x T integers come down per image, no full-size mask is written or downloaded.
+        An image's ground truth is its first MAX_GT_INSTANCES instances (what a training batch carries)."""
+        cfg = self.config
+        assert self.mode == 'inference'
+        if hasattr(dataset, "image_ids"):
+            ids = list(dataset.image_ids)
+            if max_samples is not None:
+                ids = ids[:max_samples]
+            info = [list(mutils.load_image_gt(dataset, cfg, i, use_mini_mask=cfg.USE_MINI_MASK)) for i in ids]
+        else:
+            info = list(dataset) if max_samples is None else list(dataset)[:max_samples]
+        for row in info:
+            assert list(row[0].shape) == list(cfg.IMAGE_SHAPE) and row[0].dtype == 'uint8'
+        B, T = int(cfg.BATCH_SIZE), int(cfg.MAX_GT_INSTANCES)
+        H, W = int(cfg.IMAGE_SHAPE[0]), int(cfg.IMAGE_SHAPE[1])
+        dev = self.net.dev
+
+        from . import _ext as X
+        nring = 2 * in_flight + 2
+        key = (B, tuple(cfg.IMAGE_SHAPE), nring)
+        if getattr(self, "_stage_ring_key", None) != key:            # detect_many's staging ring (the same key: the two share it)
+            self._stage_ring = [torch.empty((B,) + tuple(cfg.IMAGE_SHAPE), dtype=torch.uint8).pin_memory() for _ in range(nring)]
+            self._stage_ring_key = key
+        ring = self._stage_ring
+        gkey = (B, H, W, T, nring)
+        if getattr(self, "_gt_ring_key", None) != gkey:
+            self._gt_ring = [torch.empty((B, H, W, T), dtype=torch.uint8).pin_memory() for _ in range(nring)]
+            self._gt_ring_key = gkey
+        gt_ring = self._gt_ring
+        truth = collections.deque()
+
+        def batches():
+            for bi, lo in enumerate(range(0, len(info), B)):
+                grp = info[lo:lo + B]
+                n = len(grp)
+                grp = grp + [grp[-1]] * (B - n)                              # a short last batch is padded; its padding is ignored below
+                stage, gstage = ring[bi % nring], gt_ring[bi % nring]
+                np.stack([r[0] for r in grp], out=stage.numpy())
+                gm = gstage.numpy()
+                gm.fill(0)
+                gt_ids = np.zeros((B, T), np.int32)
+                gt_boxes = np.zeros((B, T, 4), np.int32)
+                for k, (_, class_ids, boxes, masks) in enumerate(grp):
+                    m = min(T, int(class_ids.shape[0]))                      # the first MAX_GT_INSTANCES, in order (BatchGenerator._encode's layout)
+                    gt_ids[k, :m] = class_ids[:m]
+                    gt_boxes[k, :m] = boxes[:m]
+                    for j in range(m):
+                        gm[k, :, :, j] = masks[:, :, j]
+                raw = stage.to(dev, non_blocking=True)
+                gt_d = gstage.to(dev, non_blocking=True)
+                x = torch.empty(raw.shape, dtype=torch.float32, device=dev)
+                X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
+                truth.append((n, gt_d, gt_ids, gt_boxes))
+                yield x
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+
+    def evaluate_shapes_stream(self, n_images, seed=0, start_index=0, cs_threshold=0.35, in_flight=3):
+        """evaluate() on images start_index .. start_index + n_images - 1 of the synthetic Shapes stream with the inputs AND the ground truth
+        produced on the device (myolo.shapes.ShapesProducer: bit-identical to ShapesDataset / load_image_gt): nothing but the detections' rows and
+        the overlap counts crosses PCIe, so this runs at the speed of the inference forward."""
+        from .shapes import ShapesProducer
+        cfg = self.config
+        assert self.mode == 'inference'
+        B = int(cfg.BATCH_SIZE)
+        prod = ShapesProducer(cfg, seed=seed, device=self._device)
+        truth = collections.deque()
+
+        def batches():
+            for lo in range(0, n_images, B):
+                d = prod.batch(list(range(start_index + lo, start_index + lo + B)))     # (a short last batch runs into the next images; ignored below)
+                truth.append((min(B, n_images - lo), d["gt_masks"], d["gt_ids"], d["gt_boxes"]))
+                yield d["images"]
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+
+    def _evaluate_stream(self, batches, truth, cs_threshold, in_flight):
+        """the common part of evaluate() / evaluate_shapes_stream(): `batches` yields [B,H,W,3] device images and appends each batch's
+        (images that count, gt_masks [B,H,W,T] device, gt_ids [B,T], gt_boxes [B,T,4] host or device) to the deque `truth`."""
+        from .evaluate import Evaluator
+        cfg = self.config
+        B, K = int(cfg.BATCH_SIZE), self.EVAL_SLOTS
+        ev = Evaluator()
+        if getattr(self, "_eval_sel_pin", None) is None or tuple(self._eval_sel_pin.shape) != (B, K):
+            self._eval_sel_pin = torch.empty((B, K), dtype=torch.int32).pin_memory()
+        sel = self._eval_sel_pin          # (free again by the next batch: the download of the counts below ends every batch with a synchronisation)
+        for _, det_d, mask_d in self.net.predict_stream(batches, in_flight=in_flight):
+            n, gt_d, gt_ids, gt_boxes = truth.popleft()
+            det_all = det_d.cpu().numpy()
+            picked = []
+            sel_h = sel.numpy()
+            sel_h.fill(-1)
+            for k in range(n):
+                keep, nmb, _, scores, class_ids = self._select(det_all[k], cs_threshold)
+                sel_h[k, :len(nmb)] = keep[nmb]
+                picked.append((scores[nmb], class_ids[nmb]))
+            counts = self.net.overlap_counts(det_d, mask_d, sel, gt_d)
+            inter, area_pred, area_gt, win = [t.cpu().numpy() for t in counts]
+            if torch.is_tensor(gt_ids):
+                gt_ids, gt_boxes = gt_ids.cpu().numpy(), gt_boxes.cpu().numpy()
+            for k in range(n):
+                scores, class_ids = picked[k]
+                m = len(scores)
+                ev.add_image(scores, class_ids, gt_ids[k], inter[k, :m], area_pred[k, :m], area_gt[k], win[k, :m], gt_boxes[k])
+        return ev.result()
 
     def _decode_masks_device(self, det, masks, image_shape, det_host=None):
         """decode_masks (model.py:1330-1391) with the unmold/paste of every detection on the GPU

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end learning check (no oracle involved): overfit ONE fixed batch of 8 Shapes images with the training step, then
-run detect() on those images with the trained weights.  Expected on an MI355X (25 s): the mask loss falls from 0.69 to about
+run detect() and evaluate() on those images with the trained weights.  Expected on an MI355X (25 s): the mask loss falls from 0.69 to about
 0.01, every detection has the class of a ground-truth instance and its pasted mask overlaps that instance with IoU > 0.8.
   python tools/overfit_check.py [WINOGRAD_TILES=f43|f63] [FP32_MATMUL=native|bf16x6] [SEED=n]       (config overrides; default: the config's)
 """
@@ -34,15 +34,12 @@ for i in range(1500):
 m.save_weights("/tmp/overfit.npz")
 inf = MaskYOLO(mode="inference", config=cfg)
 inf.load_weights("/tmp/overfit.npz")
-for k in range(3):
-    img = samples[k][0]
-    res = inf.detect(img.astype(np.uint8), cs_threshold=0.35)[0]
-    gt_cls = [int(c) for c in samples[k][1]]
-    gt_masks = samples[k][3]
-    ious = []
-    for j in range(res["full_masks"].shape[2]):
-        pm = res["full_masks"][:, :, j]
-        best = max((np.logical_and(pm, gt_masks[:, :, g]).sum() / max(1, np.logical_or(pm, gt_masks[:, :, g]).sum())) for g in range(gt_masks.shape[2]))
-        ious.append(round(float(best), 2))
-    print("image %d: GT classes %s | detected classes %s scores %s best mask IoU %s" % (k, gt_cls, [int(c) for c in res["class_ids"]],
-          ["%.2f" % s for s in res["confidence_scores"]], ious))
+for k in range(B):
+    res = inf.detect(samples[k][0].astype(np.uint8), cs_threshold=0.35)[0]
+    one = inf.evaluate([samples[k]], cs_threshold=0.35)          # this image alone: its matched-mask IoU
+    print("image %d: GT classes %s | detected classes %s scores %s mean matched mask IoU %.2f mask AP50 %.2f" % (
+          k, [int(c) for c in samples[k][1]], [int(c) for c in res["class_ids"]], ["%.2f" % s for s in res["confidence_scores"]],
+          one["mean_matched_mask_iou"], one["mask_ap50"]))
+r = inf.evaluate(samples, cs_threshold=0.35)
+print("all %d images: mask AP50 %.3f mask AP %.3f box AP50 %.3f box AP %.3f mean matched mask IoU %.3f (%d detections, %d instances)" % (
+      r["n_images"], r["mask_ap50"], r["mask_ap"], r["box_ap50"], r["box_ap"], r["mean_matched_mask_iou"], r["n_det"], r["n_gt"]))
