@@ -149,29 +149,22 @@ int myolo_wino63_multiply(const float* V, const float* U, float* M, int N, int C
 /* weight_transform + multiply in one call (w = the layer's [3,3,Cin,Cout] kernel): U_scratch (myolo_wino63_u_elems floats) is written only when the
  * transformed filters are not already prepared for this step (prepared-weights registry, myolo_wprep_* above) */
 int myolo_wino63_multiply_w(const float* V, const float* w, float* U_scratch, float* M, int N, int Cin, int Cout, void* stream);
-/* x [N,14,14,C] -> act(x*scale + shift) (scale NULL: identity) -> V; the activation also goes to y (NULL: nowhere) where flags[img] != 0
- * (flags NULL: everywhere) */
-int myolo_wino63_input_transform(const float* x, const float* scale, const float* shift, int act, float* y, const int32_t* flags, float* V,
-                                 int N, int C, void* stream);
-/* the flagged outputs of the three keeping calls (input_transform's y, *_keep_pre's ypre) written in COMPACT order for the sparse mask-head backward:
- * slots [N] = compact slot of an image or -1 (myolo_positive_index); image n's rows go to block slots[n] when 0 <= slots[n] < cap -- no gather later */
-int myolo_wino63_input_transform_slots(const float* x, const float* scale, const float* shift, int act, float* y_compact, const int32_t* slots, int cap,
-                                       float* V, int N, int C, void* stream);
-int myolo_wino63_output_input_transform_keep_pre_slots(const float* M, const float* bias, const float* scale, const float* shift, float* ypre_compact,
-                                                       const int32_t* slots, int cap, float* Vn, int N, int C, int act, void* stream);
-int myolo_wino63_output_transform_keep_pre_slots(const float* M, const float* bias, const float* scale, const float* shift, float* y, float* ypre_compact,
-                                                 const int32_t* slots, int cap, int N, int C, int act, void* stream);
-/* layer boundary in one kernel: M_i -> act((A^T m A + bias)*scale + shift) -> V_{i+1}; y / flags as above */
-int myolo_wino63_output_input_transform(const float* M, const float* bias, const float* scale, const float* shift, float* y,
-                                        const int32_t* flags, float* Vn, int N, int C, int act, void* stream);
-int myolo_wino63_output_transform(const float* M, const float* bias, const float* scale, const float* shift, float* y, int N, int C, int act,
-                                  void* stream);
-/* ... with the conv's PRE-BatchNorm output (A^T m A + bias) kept for the flagged ROIs (ypre written where flags[img] != 0, NULL: everywhere; y of
- * output_transform_keep_pre -- the activation -- written for every ROI, may be NULL): the exact-sparsity backward reads bn2-4's backward off it */
-int myolo_wino63_output_input_transform_keep_pre(const float* M, const float* bias, const float* scale, const float* shift, float* ypre,
-                                                 const int32_t* flags, float* Vn, int N, int C, int act, void* stream);
-int myolo_wino63_output_transform_keep_pre(const float* M, const float* bias, const float* scale, const float* shift, float* y, float* ypre,
-                                           const int32_t* flags, int N, int C, int act, void* stream);
+/* x [N,14,14,C] -> a = act(x*scale + shift) (scale NULL: identity) -> V.
+ * keep (NULL: nothing kept) receives a's rows of the selected images:
+ *   keep_cap == 0: keep_sel = flags [N] (NULL: every image); keep is dense, [N,14,14,C];
+ *   keep_cap  > 0: keep_sel = slots [N] (myolo_positive_index: compact slot of an image or -1), required; keep is compact -- the rows of image n sit at
+ *                  block slots[n] when 0 <= slots[n] < keep_cap, so the sparse mask-head backward needs no gather */
+int myolo_wino63_input_transform(const float* x, const float* scale, const float* shift, int act,
+                                 float* keep, const int32_t* keep_sel, int keep_cap,
+                                 float* V, int N, int C, void* stream);
+/* layer boundary in one kernel: M -> pre = A^T m A + bias -> a = act(pre*scale + shift) -> Vn (NULL: no next conv, a plain output transform).
+ * y (NULL: not written): a, every image.
+ * keep (NULL: nothing kept): rows of the selected images (keep_sel / keep_cap as above), pre if keep_pre else a.  pre is the conv's PRE-BatchNorm output:
+ * the exact-sparsity backward reads bn2-4's backward off it.  MYOLO_EINVAL for y && keep && !keep_pre (the kernel has a single activation output) and
+ * for a call with nothing to write */
+int myolo_wino63_boundary(const float* M, const float* bias, const float* scale, const float* shift, int act,
+                          float* y, float* keep, int keep_pre, const int32_t* keep_sel, int keep_cap,
+                          float* Vn, int N, int C, void* stream);
 /* conv1 of the mask head on this tiling: ROIAlign fused into the input transform (myolo_wino_input_transform_roialign), the output
  * transform that also yields the training-mode BatchNorm statistics (myolo_wino_output_transform_bn_stats), and the weight gradient
  * from the kept V planes and the lazily formed output gradient (myolo_conv3x3_wino_bwd_weight_lazybn) */

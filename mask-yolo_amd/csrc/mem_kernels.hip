@@ -26,7 +26,7 @@ extern "C" void myolo_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* myolo_last_error_string(void) { return g_err; }
-extern "C" int myolo_version(void) { return 212; }
+extern "C" int myolo_version(void) { return 213; }
 
 // ---------------------------------------------------------------------------------------
 // tuning switches (myolo_set_option): plain process-wide ints, no environment reads anywhere

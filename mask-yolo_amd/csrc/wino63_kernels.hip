@@ -1002,6 +1002,15 @@ static int w63_launch(const W63Args& a, hipStream_t s)
     else w63_launch_act<FRONT, BACK, MYOLO_ACT_RELU6>(a, (unsigned)grid, lds, s);
     return MYOLO_OK;
 }
+// w63_launch from an entry point: its refusal (a unit count outside 1 .. 2^31 - 1) is the entry's error, not a silent no-op
+#define W63_LAUNCH(FRONT, BACK, a, s)                                                                     \
+    do {                                                                                                  \
+        const int rc__ = w63_launch<FRONT, BACK>(a, s);                                                   \
+        if (rc__ != MYOLO_OK) {                                                                           \
+            myolo_set_error("%s: %lld x %d channels is outside the launchable range", __func__, (long long)(a).NR, (a).C); \
+            return rc__;                                                                                  \
+        }                                                                                                 \
+    } while (0)
 
 extern "C" {
 
@@ -1059,94 +1068,37 @@ int myolo_wino63_multiply(const float* V, const float* U, float* M, int N, int C
     return MYOLO_OK;
 }
 
-/* x [N,14,14,C] -> act(x * scale + shift) (scale NULL: identity) -> V; the activation is also written to y where flags allow */
-int myolo_wino63_input_transform(const float* x, const float* scale, const float* shift, int act, float* y, const int32_t* flags, float* V,
-                                 int N, int C, void* stream)
+/* x [N,14,14,C] -> a = act(x * scale + shift) (scale NULL: identity) -> V.  keep (NULL: nothing kept) receives a's rows of the selected images:
+ * keep_cap == 0: keep_sel = flags [N] (NULL: every image), keep dense [N,14,14,C];  keep_cap > 0: keep_sel = slots [N] (myolo_positive_index), keep
+ * compact -- the rows of image n at block slots[n] when 0 <= slots[n] < keep_cap */
+int myolo_wino63_input_transform(const float* x, const float* scale, const float* shift, int act, float* keep, const int32_t* keep_sel, int keep_cap,
+                                 float* V, int N, int C, void* stream)
 {
     MYOLO_REQUIRE(x && V && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_input_transform: bad arguments (C %% 64 == 0)");
-    W63Args a{x, V, y, flags, nullptr, scale, shift, N, C, act};
-    w63_launch<W63_FROM_ACT, W63_TO_V>(a, (hipStream_t)stream);
+    MYOLO_REQUIRE(keep_cap >= 0 && (keep_cap == 0 || keep_sel), "wino63_input_transform: compact kept rows (keep_cap %d) need their slots", keep_cap);
+    W63Args a{x, V, keep, keep ? keep_sel : nullptr, nullptr, scale, shift, N, C, act};
+    a.keep_cap = keep ? keep_cap : 0;
+    W63_LAUNCH(W63_FROM_ACT, W63_TO_V, a, (hipStream_t)stream);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
 
-/* layer boundary: M_i -> act((A^T m A + bias) * scale + shift) -> V_{i+1}; y (NULL: never) written where flags[img] != 0 (NULL: always) */
-int myolo_wino63_output_input_transform(const float* M, const float* bias, const float* scale, const float* shift, float* y,
-                                        const int32_t* flags, float* Vn, int N, int C, int act, void* stream)
+/* layer boundary: M -> pre = A^T m A + bias -> a = act(pre * scale + shift) -> Vn (NULL: no next conv).  y (NULL: not written): a, every image.
+ * keep (NULL: nothing kept): the rows of the selected images (keep_sel / keep_cap as above), pre if keep_pre else a.  The kernel has ONE activation
+ * output, so y and a kept activation exclude each other.  The exact-sparsity backward reads the frozen BatchNorms' backward off the kept pre rows
+ * of the positive ROIs: no (a - beta) / gamma reconstruction from the post-activation value */
+int myolo_wino63_boundary(const float* M, const float* bias, const float* scale, const float* shift, int act, float* y, float* keep, int keep_pre,
+                          const int32_t* keep_sel, int keep_cap, float* Vn, int N, int C, void* stream)
 {
-    MYOLO_REQUIRE(M && Vn && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_output_input_transform: bad arguments (C %% 64 == 0)");
-    W63Args a{M, Vn, y, flags, bias, scale, shift, N, C, act};
-    w63_launch<W63_FROM_M, W63_TO_V>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-
-/* the two calls above with the conv's PRE-BatchNorm output (A^T m A + bias) kept for the flagged ROIs: ypre written where flags[img] != 0 (NULL:
- * everywhere); y (output_transform_keep_pre: the activation every ROI's consumer reads; may be NULL) is written everywhere */
-int myolo_wino63_output_input_transform_keep_pre(const float* M, const float* bias, const float* scale, const float* shift, float* ypre,
-                                                 const int32_t* flags, float* Vn, int N, int C, int act, void* stream)
-{
-    MYOLO_REQUIRE(M && Vn && ypre && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_output_input_transform_keep_pre: bad arguments (C %% 64 == 0)");
-    W63Args a{M, Vn, nullptr, flags, bias, scale, shift, N, C, act};
-    a.ypre = ypre;
-    w63_launch<W63_FROM_M, W63_TO_V>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-
-int myolo_wino63_output_transform_keep_pre(const float* M, const float* bias, const float* scale, const float* shift, float* y, float* ypre,
-                                           const int32_t* flags, int N, int C, int act, void* stream)
-{
-    MYOLO_REQUIRE(M && ypre && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_output_transform_keep_pre: bad arguments (C %% 64 == 0)");
-    W63Args a{M, nullptr, y, flags, bias, scale, shift, N, C, act};
-    a.ypre = ypre;
-    w63_launch<W63_FROM_M, W63_TO_NONE>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-
-/* ---- the three calls above with the kept tensor written in COMPACT order: slots [N] = compact slot of an image or -1 (myolo_positive_index), rows of
- * image n at block slots[n] when 0 <= slots[n] < cap.  input_transform_slots: y_compact = the activation act(x * scale + shift) of the kept images;
- * the *_keep_pre_slots pair: ypre_compact = the conv's pre-BatchNorm output of the kept images (y of output_transform stays dense). ---- */
-int myolo_wino63_input_transform_slots(const float* x, const float* scale, const float* shift, int act, float* y_compact, const int32_t* slots, int cap,
-                                       float* V, int N, int C, void* stream)
-{
-    MYOLO_REQUIRE(x && V && y_compact && slots && cap > 0 && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_input_transform_slots: bad arguments (C %% 64 == 0)");
-    W63Args a{x, V, y_compact, slots, nullptr, scale, shift, N, C, act};
-    a.keep_cap = cap;
-    w63_launch<W63_FROM_ACT, W63_TO_V>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-int myolo_wino63_output_input_transform_keep_pre_slots(const float* M, const float* bias, const float* scale, const float* shift, float* ypre_compact,
-                                                       const int32_t* slots, int cap, float* Vn, int N, int C, int act, void* stream)
-{
-    MYOLO_REQUIRE(M && Vn && ypre_compact && slots && cap > 0 && N > 0 && (C % W63_CS) == 0 && !scale == !shift,
-                  "wino63_output_input_transform_keep_pre_slots: bad arguments (C %% 64 == 0)");
-    W63Args a{M, Vn, nullptr, slots, bias, scale, shift, N, C, act};
-    a.ypre = ypre_compact; a.keep_cap = cap;
-    w63_launch<W63_FROM_M, W63_TO_V>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-int myolo_wino63_output_transform_keep_pre_slots(const float* M, const float* bias, const float* scale, const float* shift, float* y, float* ypre_compact,
-                                                 const int32_t* slots, int cap, int N, int C, int act, void* stream)
-{
-    MYOLO_REQUIRE(M && ypre_compact && slots && cap > 0 && N > 0 && (C % W63_CS) == 0 && !scale == !shift,
-                  "wino63_output_transform_keep_pre_slots: bad arguments (C %% 64 == 0)");
-    W63Args a{M, nullptr, y, slots, bias, scale, shift, N, C, act};
-    a.ypre = ypre_compact; a.keep_cap = cap;
-    w63_launch<W63_FROM_M, W63_TO_NONE>(a, (hipStream_t)stream);
-    MYOLO_CHECK_LAUNCH();
-    return MYOLO_OK;
-}
-
-int myolo_wino63_output_transform(const float* M, const float* bias, const float* scale, const float* shift, float* y, int N, int C, int act,
-                                  void* stream)
-{
-    MYOLO_REQUIRE(M && y && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_output_transform: bad arguments (C %% 64 == 0)");
-    W63Args a{M, nullptr, y, nullptr, bias, scale, shift, N, C, act};
-    w63_launch<W63_FROM_M, W63_TO_NONE>(a, (hipStream_t)stream);
+    MYOLO_REQUIRE(M && N > 0 && (C % W63_CS) == 0 && !scale == !shift, "wino63_boundary: bad arguments (C %% 64 == 0)");
+    MYOLO_REQUIRE(Vn || y || keep, "wino63_boundary: nothing to write (Vn, y and keep are all NULL)");
+    MYOLO_REQUIRE(!(y && keep && !keep_pre), "wino63_boundary: y and a kept activation at once (one activation output: keep the pre-BatchNorm rows, or drop y)");
+    MYOLO_REQUIRE(keep_cap >= 0 && (keep_cap == 0 || keep_sel), "wino63_boundary: compact kept rows (keep_cap %d) need their slots", keep_cap);
+    W63Args a{M, Vn, (keep && !keep_pre) ? keep : y, keep ? keep_sel : nullptr, bias, scale, shift, N, C, act};
+    a.ypre = keep_pre ? keep : nullptr;
+    a.keep_cap = keep ? keep_cap : 0;
+    if (Vn) W63_LAUNCH(W63_FROM_M, W63_TO_V, a, (hipStream_t)stream);
+    else W63_LAUNCH(W63_FROM_M, W63_TO_NONE, a, (hipStream_t)stream);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
@@ -1160,7 +1112,7 @@ int myolo_wino63_input_transform_roialign(const float* feature, const float* box
                   "wino63_input_transform_roialign: bad arguments (C %% 64 == 0)");
     W63Args a{};
     a.src = feature; a.Vn = V; a.NR = nb; a.C = C; a.act = MYOLO_ACT_NONE; a.boxes = boxes; a.bind = box_ind; a.FH = FH; a.FW = FW;
-    w63_launch<W63_FROM_CROP, W63_TO_V>(a, (hipStream_t)stream);
+    W63_LAUNCH(W63_FROM_CROP, W63_TO_V, a, (hipStream_t)stream);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
@@ -1180,7 +1132,7 @@ int myolo_wino63_output_transform_bn_stats(const float* M, const float* bias, fl
     double* tot = (double*)((char*)ws + align256((size_t)N * 2 * C * sizeof(double)));
     W63Args a{};
     a.src = M; a.y = y; a.bias = bias; a.NR = N; a.C = C; a.act = MYOLO_ACT_NONE; a.stats = part;
-    w63_launch<W63_FROM_M, W63_TO_NONE>(a, s);
+    W63_LAUNCH(W63_FROM_M, W63_TO_NONE, a, s);
     myolo_bn_stats_from_partials(part, tot, N, C, (double)N * W63_HW * W63_HW, gamma, beta, mean, var, scale, shift, moving_mean, moving_var, s);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
@@ -1246,7 +1198,7 @@ int myolo_wino63_bwd_weight_lazybn(const float* v_saved, const float* y_pre, con
     const size_t part_bytes = ws_bytes - (size_t)((char*)part - (char*)ws);
     W63Args a{};
     a.src = y_pre; a.Vn = Q; a.scale = scale; a.shift = shift; a.NR = N; a.C = Cout; a.act = act; a.dyc = dy_compact; a.inv = inv; a.ka = ka; a.kb = kb;
-    w63_launch<W63_FROM_LAZY, W63_TO_Q>(a, s);
+    W63_LAUNCH(W63_FROM_LAZY, W63_TO_Q, a, s);
     const int rc = w63_tn_and_dw(v_saved, Q, dU, dw, N, Cin, Cout, part, part_bytes, s);
     if (rc != MYOLO_OK) return rc;
     MYOLO_CHECK_LAUNCH();
@@ -1275,11 +1227,11 @@ int myolo_wino63_bwd_data_lazybn(const float* y_pre, const float* dy_compact, co
     float* Mp = (float*)((char*)V + align256(myolo_wino63_plane_elems(N, Cout) * sizeof(float)));
     const float* U = w63_filters(w, (float*)ws, Cin, Cout, 1, s);
     W63Args a{y_pre, V, nullptr, nullptr, nullptr, scale, shift, N, Cout, act, dy_compact, inv, ka, kb};
-    w63_launch<W63_FROM_LAZY, W63_TO_V>(a, s);
+    W63_LAUNCH(W63_FROM_LAZY, W63_TO_V, a, s);
     const int rc = myolo_wino63_multiply(V, U, Mp, N, Cout, Cin, stream);
     if (rc != MYOLO_OK) return rc;
     W63Args b{Mp, nullptr, dx, nullptr, nullptr, nullptr, nullptr, N, Cin, MYOLO_ACT_NONE};
-    w63_launch<W63_FROM_M, W63_TO_NONE>(b, s);
+    W63_LAUNCH(W63_FROM_M, W63_TO_NONE, b, s);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
@@ -1293,7 +1245,7 @@ int myolo_wino63_lazybn_transforms(const float* y_pre, const float* dy_compact, 
     MYOLO_REQUIRE(y_pre && inv && scale && shift && ka && kb && V && Q && N > 0 && (C % W63_CS) == 0, "wino63_lazybn_transforms: bad arguments");
     W63Args a{y_pre, V, nullptr, nullptr, nullptr, scale, shift, N, C, act, dy_compact, inv, ka, kb};
     a.Qn = Q;
-    w63_launch<W63_FROM_LAZY, W63_TO_VQ>(a, (hipStream_t)stream);
+    W63_LAUNCH(W63_FROM_LAZY, W63_TO_VQ, a, (hipStream_t)stream);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
@@ -1315,7 +1267,7 @@ int myolo_wino63_bwd_data_from_v(const float* V, const float* w, float* dx, int 
     const int rc = myolo_wino63_multiply(V, U, Mp, N, Cout, Cin, stream);
     if (rc != MYOLO_OK) return rc;
     W63Args b{Mp, nullptr, dx, nullptr, nullptr, nullptr, nullptr, N, Cin, MYOLO_ACT_NONE};
-    w63_launch<W63_FROM_M, W63_TO_NONE>(b, s);
+    W63_LAUNCH(W63_FROM_M, W63_TO_NONE, b, s);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }
@@ -1367,9 +1319,9 @@ int myolo_conv3x3_wino63_fwd(const float* x, const float* w, const float* bias, 
     MYOLO_REQUIRE(w && myolo_wino63_ok(W63_HW, W63_HW, Cin, Cout), "conv3x3_wino63_fwd: unsupported channel counts (%d -> %d)", Cin, Cout);
     const float* U = w63_filters(w, (float*)ws, Cin, Cout, 0, (hipStream_t)stream);
     int rc = MYOLO_OK;
-    if (rc == MYOLO_OK) rc = myolo_wino63_input_transform(x, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, V, N, Cin, stream);
+    if (rc == MYOLO_OK) rc = myolo_wino63_input_transform(x, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, 0, V, N, Cin, stream);
     if (rc == MYOLO_OK) rc = myolo_wino63_multiply(V, U, Mp, N, Cin, Cout, stream);
-    if (rc == MYOLO_OK) rc = myolo_wino63_output_transform(Mp, bias, scale, shift, y, N, Cout, act, stream);
+    if (rc == MYOLO_OK) rc = myolo_wino63_boundary(Mp, bias, scale, shift, act, y, nullptr, 0, nullptr, 0, nullptr, N, Cout, stream);
     return rc;
 }
 
@@ -1383,9 +1335,9 @@ int myolo_conv3x3_wino63_bwd_data(const float* dy, const float* w, float* dx, in
     float* V = (float*)((char*)ws + align256(myolo_wino63_u_elems(Cin, Cout) * sizeof(float)));
     float* Mp = (float*)((char*)V + align256(myolo_wino63_plane_elems(N, Cout) * sizeof(float)));
     const float* U = w63_filters(w, (float*)ws, Cin, Cout, 1, s);
-    int rc = myolo_wino63_input_transform(dy, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, V, N, Cout, stream);
+    int rc = myolo_wino63_input_transform(dy, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, 0, V, N, Cout, stream);
     if (rc == MYOLO_OK) rc = myolo_wino63_multiply(V, U, Mp, N, Cout, Cin, stream);
-    if (rc == MYOLO_OK) rc = myolo_wino63_output_transform(Mp, nullptr, nullptr, nullptr, dx, N, Cin, MYOLO_ACT_NONE, stream);
+    if (rc == MYOLO_OK) rc = myolo_wino63_boundary(Mp, nullptr, nullptr, nullptr, MYOLO_ACT_NONE, dx, nullptr, 0, nullptr, 0, nullptr, N, Cin, stream);
     return rc;
 }
 
@@ -1404,12 +1356,12 @@ int myolo_conv3x3_wino63_bwd_weight(const float* x, const float* v_saved, const 
     void* part = v_saved ? (void*)after_q : (void*)(after_q + align256(myolo_wino63_plane_elems(N, Cin) * sizeof(float)));
     const size_t part_bytes = ws_bytes - (size_t)((char*)part - (char*)ws);
     if (!v_saved) {
-        const int rc = myolo_wino63_input_transform(x, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, V, N, Cin, stream);
+        const int rc = myolo_wino63_input_transform(x, nullptr, nullptr, MYOLO_ACT_NONE, nullptr, nullptr, 0, V, N, Cin, stream);
         if (rc != MYOLO_OK) return rc;
     }
     W63Args a{};
     a.src = dy; a.Vn = Q; a.NR = N; a.C = Cout; a.act = MYOLO_ACT_NONE;
-    w63_launch<W63_FROM_ACT, W63_TO_Q>(a, s);
+    W63_LAUNCH(W63_FROM_ACT, W63_TO_Q, a, s);
     const int rc = w63_tn_and_dw(v_saved ? v_saved : V, Q, dU, dw, N, Cin, Cout, part, part_bytes, s);
     if (rc != MYOLO_OK) return rc;
     MYOLO_CHECK_LAUNCH();

@@ -901,7 +901,7 @@ int myolo_wino_output_input_transform(const float* M, const float* bias, const f
 }
 
 /* the same boundary with the conv's PRE-BatchNorm output (A^T m A + bias) written to ypre where flags[img] != 0 (NULL: everywhere) instead of the
- * activation: what the exact-sparsity backward reads bn2-4's backward off (csrc/wino63_kernels.hip: myolo_wino63_output_input_transform_keep_pre) */
+ * activation: what the exact-sparsity backward reads bn2-4's backward off (csrc/wino63_kernels.hip: myolo_wino63_boundary with keep_pre) */
 int myolo_wino_output_input_transform_keep_pre(const float* M, const float* bias, const float* scale, const float* shift, float* ypre,
                                                const int32_t* flags, float* V_next, int N, int H, int W, int C, int act, void* stream)
 {

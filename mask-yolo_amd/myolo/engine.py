@@ -227,6 +227,117 @@ class _Side(object):
         self.stream, self.ws, self.pending = stream, ws, False
 
 
+class _Wino43(object):
+    """The F(4,3)/F(2,3) Winograd tiling of an h x w map (csrc/wino_kernels.hip: the myolo_wino_* entries) behind the method set the engine's 3x3
+    convs are written against.  _Wino63 is the same set on the F(6,3)/F(4,3) tiling; what one tiling cannot do is a capability the caller asks."""
+    fmt = "f43"
+    slots = False              # kept rows only flagged-dense, never slot-compact
+    keep_beside_y = False      # a boundary that writes y has no flagged second output
+
+    def __init__(self, net, h, w):
+        self.net, self.h, self.w = net, h, w
+
+    def planes(self, N, C):
+        return self.net._new(36, N * ((self.h + 3) // 4) * ((self.w + 3) // 4), C)
+
+    def filters(self, cin, cout):
+        return self.net._new(X.wino_u_elems(cin, cout))
+
+    def input_transform(self, x, V, N, C, scale=None, shift=None, act=ACT_NONE, tag=None):
+        """x -> act(x * scale + shift) (scale None: identity) -> V"""
+        if scale is None:
+            self.net._call_timed(tag, "myolo_wino_input_transform", X.ptr(x), X.ptr(V), N, self.h, self.w, C, X.stream())
+        else:
+            self.net._call_timed(tag, "myolo_wino_input_transform_affine", X.ptr(x), X.ptr(scale), X.ptr(shift), act, X.ptr(V), N, self.h, self.w, C, X.stream())
+
+    def input_transform_roialign(self, Fm, boxes, bind, V, fn, fh, fw, C, nb):
+        """ROIAlign fused into the input transform: V straight from the feature map, the crops are never written"""
+        self.net._call_timed("roialign_fwd", "myolo_wino_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(V), fn, fh, fw, C, nb,
+                             self.h, self.w, X.stream())
+
+    def multiply(self, V, kern, U, M, N, cin, cout, tag=None):
+        """M = V x transformed filters, as the mask-head chain issues it: on this tiling the weight transform is a launch of its own"""
+        X.call("myolo_wino_weight_transform", X.ptr(kern), X.ptr(U), cin, cout, 0, X.stream())
+        self.net._call_timed(tag, "myolo_wino_multiply", X.ptr(V), X.ptr(U), X.ptr(M), N, self.h, self.w, cin, cout, X.stream())
+
+    def multiply_w(self, V, kern, U, M, N, cin, cout, tag=None):
+        """... in one call (U is written only when the filters are not already prepared for this step, X.WeightPrep)"""
+        self.net._call_timed(tag, "myolo_wino_multiply_w", X.ptr(V), X.ptr(kern), X.ptr(U), X.ptr(M), N, self.h, self.w, cin, cout, X.stream())
+
+    def boundary(self, M, bias, scale, shift, act, y, keep, keep_pre, sel, cap, Vn, N, C, tag=None):
+        """M -> pre = A^T m A + bias -> a = act(pre * scale + shift) -> Vn (None: no next conv); y (None: not written): a of every image; keep (None:
+        nothing kept): the rows of the images `sel` flags, pre if keep_pre else a"""
+        if Vn is None:
+            assert keep is None, "the F(4,3) output transform has one output"
+            self.net._call_timed(tag, "myolo_wino_output_transform", X.ptr(M), X.ptr(bias), X.ptr(scale), X.ptr(shift), X.ptr(y), N, self.h, self.w, C, act,
+                                 X.stream())
+        else:
+            assert y is None and cap == 0, "the F(4,3) layer boundary writes flagged-dense kept rows only"
+            self.net._call_timed(tag, "myolo_wino_output_input_transform_keep_pre" if keep_pre else "myolo_wino_output_input_transform", X.ptr(M), X.ptr(bias),
+                                 X.ptr(scale), X.ptr(shift), X.ptr(keep), X.ptr(sel), X.ptr(Vn), N, self.h, self.w, C, act, X.stream())
+
+    def output_bn_stats(self, M, bias, y, N, C, bn_args):
+        """conv + bias -> y and the training-mode BatchNorm statistics of y in the same pass"""
+        self.net.ws.ensure(X.wino_out_bn_ws_bytes(C))
+        X.call("myolo_wino_output_transform_bn_stats", X.ptr(M), X.ptr(bias), X.ptr(y), N, self.h, self.w, C, *bn_args, *self.net._wsargs(), X.stream())
+
+    def bwd_weight(self, x, v_saved, dy, dw, N, cin, cout):
+        self.net.ws.ensure(X.wino_ws_bytes(N, self.h, self.w, cin, cout, 2))
+        X.call("myolo_conv3x3_wino_bwd_weight", None if v_saved is not None else X.ptr(x), X.ptr(v_saved), X.ptr(dy), X.ptr(dw), N, self.h, self.w, cin, cout,
+               *self.net._wsargs(), X.stream())
+
+    def bwd_data(self, dy, kern, dx, N, cin, cout):
+        self.net.ws.ensure(X.wino_ws_bytes(N, self.h, self.w, cin, cout, 1))
+        X.call("myolo_conv3x3_wino_bwd_data", X.ptr(dy), X.ptr(kern), X.ptr(dx), N, self.h, self.w, cin, cout, *self.net._wsargs(), X.stream())
+
+
+class _Wino63(object):
+    """The F(6,3)/F(4,3) tiling of a 14 x 14 map (csrc/wino63_kernels.hip: 400 instead of 484 point-tiles per map); see _Wino43"""
+    fmt = "f63"
+    slots = True
+    keep_beside_y = True
+
+    def __init__(self, net):
+        self.net = net
+
+    def planes(self, N, C):
+        return self.net._new(X.wino63_plane_elems(N, C))
+
+    def filters(self, cin, cout):
+        return self.net._new(X.wino63_u_elems(cin, cout))
+
+    def input_transform(self, x, V, N, C, scale=None, shift=None, act=ACT_NONE, keep=None, sel=None, cap=0, tag=None):
+        """... keep (None: nothing kept): the activation's rows of the images `sel` selects -- flags (cap 0, dense) or slots (cap > 0, compact)"""
+        self.net._call_timed(tag, "myolo_wino63_input_transform", X.ptr(x), X.ptr(scale), X.ptr(shift), act, X.ptr(keep), X.ptr(sel), cap, X.ptr(V), N, C,
+                             X.stream())
+
+    def input_transform_roialign(self, Fm, boxes, bind, V, fn, fh, fw, C, nb):
+        self.net._call_timed("roialign_fwd", "myolo_wino63_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(V), fn, fh, fw, C, nb,
+                             X.stream())
+
+    def multiply_w(self, V, kern, U, M, N, cin, cout, tag=None):
+        self.net._call_timed(tag, "myolo_wino63_multiply_w", X.ptr(V), X.ptr(kern), X.ptr(U), X.ptr(M), N, cin, cout, X.stream())
+
+    multiply = multiply_w
+
+    def boundary(self, M, bias, scale, shift, act, y, keep, keep_pre, sel, cap, Vn, N, C, tag=None):
+        self.net._call_timed(tag, "myolo_wino63_boundary", X.ptr(M), X.ptr(bias), X.ptr(scale), X.ptr(shift), act, X.ptr(y), X.ptr(keep), int(keep_pre),
+                             X.ptr(sel), cap, X.ptr(Vn), N, C, X.stream())
+
+    def output_bn_stats(self, M, bias, y, N, C, bn_args):
+        self.net.ws.ensure(X.wino63_out_bn_ws_bytes(N, C))
+        X.call("myolo_wino63_output_transform_bn_stats", X.ptr(M), X.ptr(bias), X.ptr(y), N, C, *bn_args, *self.net._wsargs(), X.stream())
+
+    def bwd_weight(self, x, v_saved, dy, dw, N, cin, cout):
+        self.net.ws.ensure(X.wino63_ws_bytes(N, cin, cout, 2))
+        X.call("myolo_conv3x3_wino63_bwd_weight", None if v_saved is not None else X.ptr(x), X.ptr(v_saved), X.ptr(dy), X.ptr(dw), N, cin, cout,
+               *self.net._wsargs(), X.stream())
+
+    def bwd_data(self, dy, kern, dx, N, cin, cout):
+        self.net.ws.ensure(X.wino63_ws_bytes(N, cin, cout, 1))
+        X.call("myolo_conv3x3_wino63_bwd_data", X.ptr(dy), X.ptr(kern), X.ptr(dx), N, cin, cout, *self.net._wsargs(), X.stream())
+
+
 def _ensure_hw_queues(want=2):
     """HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues.  A side stream that lands on the COMPUTE stream's queue
     serialises against it in submission order (measured: +4 ... +8 ms per training step, profiles/r3_notes.md "hardware queues"; an extra
@@ -367,6 +478,7 @@ class Net(object):
         self._stage_lock = threading.Lock()
         self._stage = None                # to_device_batch: ring of pinned staging sets (created on first use); uploads go on _copy_stream
         self._bind_cache = {}
+        self._tilings = {}              # Winograd tiling adapters (_Wino43 per map size, _Wino63)
         self.timed_tags = set()           # bench.py: kernel tags to bracket with HIP events
         self.timings = {}                 # tag -> [(start_event, end_event), ...]
         self.host_wait_s = 0.0            # wall time the host spent blocked on the n_pos copy (bench.py reports it per step)
@@ -604,6 +716,20 @@ class Net(object):
             self.timings.setdefault(tag, []).append((e0, e1))
         return (lambda: e0.record(st)), stop
 
+    def _tiling(self, h, w, f63):
+        """the Winograd tiling adapter of an h x w map: F(6,3)/F(4,3) when f63, else F(4,3)/F(2,3)"""
+        key = "f63" if f63 else (h, w)
+        t = self._tilings.get(key)
+        if t is None:
+            t = self._tilings[key] = _Wino63(self) if f63 else _Wino43(self, h, w)
+        return t
+
+    def _conv_tiling(self, nimg, h, w, cin, cout, f63_too=True):
+        """the tiling a self-contained 3x3 conv op runs on, or None: the direct kernels (cfg.CONV3X3_ALGO, cfg.WINOGRAD_TILES)"""
+        if not self._wino_ok(nimg, h, w, cin, cout):
+            return None
+        return self._tiling(h, w, f63_too and self._wino63(h, w, cin, cout))
+
     def conv3x3_fwd(self, x, layer, y, nimg, h, w, cin, cout, scale=None, shift=None, act=ACT_NONE, keep_v=False, tag=None):
         """y = act(affine(conv3x3(x) + bias)) with the layer's kernel/bias; affine (scale, shift) optional.
         Returns the Winograd-transformed input when keep_v (for conv3x3_bwd_weight), else None."""
@@ -611,23 +737,13 @@ class Net(object):
         start, stop = self._timed(tag)
         start()
         v = None
-        if self._wino_ok(nimg, h, w, cin, cout) and not keep_v and self._wino63(h, w, cin, cout):
-            # F(6,3)/F(4,3) tiling of a 14x14 map (csrc/wino63_kernels.hip); a kept V stays in the F(4,3) layout its consumer expects
-            U = self._new(X.wino63_u_elems(cin, cout))
-            V, M = self._new(X.wino63_plane_elems(nimg, cin)), self._new(X.wino63_plane_elems(nimg, cout))
-            X.call("myolo_wino63_input_transform", X.ptr(x), None, None, ACT_NONE, None, None, X.ptr(V), nimg, cin, X.stream())
-            self._call_timed("wino_multiply" if tag == "mask_conv3x3_fwd" else None, "myolo_wino63_multiply_w", X.ptr(V), X.ptr(kern), X.ptr(U), X.ptr(M),
-                             nimg, cin, cout, X.stream())
-            X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(bias), X.ptr(scale), X.ptr(shift), X.ptr(y), nimg, cout, act, X.stream())
-        elif self._wino_ok(nimg, h, w, cin, cout):
-            T = nimg * ((h + 3) // 4) * ((w + 3) // 4)
-            U, V, M = self._new(X.wino_u_elems(cin, cout)), self._new(36, T, cin), self._new(36, T, cout)
-            X.call("myolo_wino_input_transform", X.ptr(x), X.ptr(V), nimg, h, w, cin, X.stream())
+        t = self._conv_tiling(nimg, h, w, cin, cout, f63_too=not keep_v)      # a kept V stays in the F(4,3) layout its consumer expects
+        if t is not None:
+            U, V, M = t.filters(cin, cout), t.planes(nimg, cin), t.planes(nimg, cout)
+            t.input_transform(x, V, nimg, cin)
             # only the dense mask-head launches (tag given) feed bench.py's roofline; feature_map / compacted ones do not
-            self._call_timed("wino_multiply" if tag == "mask_conv3x3_fwd" else None, "myolo_wino_multiply_w", X.ptr(V), X.ptr(kern), X.ptr(U), X.ptr(M),
-                             nimg, h, w, cin, cout, X.stream())
-            X.call("myolo_wino_output_transform", X.ptr(M), X.ptr(bias), X.ptr(scale), X.ptr(shift), X.ptr(y), nimg, h, w, cout, act,
-                   X.stream())
+            t.multiply_w(V, kern, U, M, nimg, cin, cout, tag="wino_multiply" if tag == "mask_conv3x3_fwd" else None)
+            t.boundary(M, bias, scale, shift, act, y, None, False, None, 0, None, nimg, cout)
             v = V if keep_v else None
         elif scale is not None or act != ACT_NONE:
             X.call("myolo_conv3x3_affine_act_fwd", X.ptr(x), X.ptr(kern), X.ptr(bias), X.ptr(scale), X.ptr(shift), X.ptr(y), nimg, h, w,
@@ -639,25 +755,16 @@ class Net(object):
 
     def conv3x3_bwd_weight(self, x, v_saved, dy, layer, nimg, h, w, cin, cout):
         dw = self.g[layer + "/kernel"]
-        if self._wino_ok(nimg, h, w, cin, cout) and v_saved is None and self._wino63(h, w, cin, cout):
-            self.ws.ensure(X.wino63_ws_bytes(nimg, cin, cout, 2))
-            X.call("myolo_conv3x3_wino63_bwd_weight", X.ptr(x), None, X.ptr(dy), X.ptr(dw), nimg, cin, cout, *self._wsargs(), X.stream())
-        elif self._wino_ok(nimg, h, w, cin, cout):
-            self.ws.ensure(X.wino_ws_bytes(nimg, h, w, cin, cout, 2))
-            X.call("myolo_conv3x3_wino_bwd_weight", None if v_saved is not None else X.ptr(x), X.ptr(v_saved), X.ptr(dy), X.ptr(dw),
-                   nimg, h, w, cin, cout, *self._wsargs(), X.stream())
+        t = self._conv_tiling(nimg, h, w, cin, cout, f63_too=v_saved is None)
+        if t is not None:
+            t.bwd_weight(x, v_saved, dy, dw, nimg, cin, cout)
         else:
             X.call("myolo_conv3x3_bwd_weight", X.ptr(x), X.ptr(dy), X.ptr(dw), nimg, h, w, cin, cout, *self._wsargs(), X.stream())
 
     def conv3x3_bwd_data(self, dy, layer, dx, nimg, h, w, cin, cout):
-        if self._wino_ok(nimg, h, w, cout, cin) and self._wino63(h, w, cout, cin):
-            self.ws.ensure(X.wino63_ws_bytes(nimg, cin, cout, 1))
-            X.call("myolo_conv3x3_wino63_bwd_data", X.ptr(dy), X.ptr(self.p[layer + "/kernel"]), X.ptr(dx), nimg, cin, cout,
-                   *self._wsargs(), X.stream())
-        elif self._wino_ok(nimg, h, w, cout, cin):
-            self.ws.ensure(X.wino_ws_bytes(nimg, h, w, cin, cout, 1))
-            X.call("myolo_conv3x3_wino_bwd_data", X.ptr(dy), X.ptr(self.p[layer + "/kernel"]), X.ptr(dx), nimg, h, w, cin, cout,
-                   *self._wsargs(), X.stream())
+        t = self._conv_tiling(nimg, h, w, cout, cin)
+        if t is not None:
+            t.bwd_data(dy, self.p[layer + "/kernel"], dx, nimg, cin, cout)
         else:
             X.call("myolo_conv3x3_bwd_data", X.ptr(dy), X.ptr(self.p[layer + "/kernel"]), X.ptr(dx), nimg, h, w, cin, cout,
                    *self._wsargs(), X.stream())
@@ -1275,156 +1382,92 @@ class Net(object):
         forward never materialised is recorded as ("lazy_bn", pre-BN tensor, bn layer)).  Returns conv4's activation.
         cfg.WINOGRAD_TILES = "f63": conv2-4 (whose inputs and outputs are MASK_FILTERS wide 14x14 maps) use the F(6,3)/F(4,3)
         tiling of csrc/wino63_kernels.hip (400 instead of 484 point-tiles per ROI); conv1 keeps the F(4,3)/F(2,3) tiling (its input
-        transform is fused with ROIAlign and its V planes feed the weight gradient)."""
+        transform is fused with ROIAlign and its V planes feed the weight gradient) unless its backward has the matching kernels.
+        Written once against the tiling adapters (_Wino43 / _Wino63); tests/mask_head_launches.py pins what it launches."""
         q = ps * ps
+        F = MASK_FILTERS
         Vcur = None
-        t63 = self.wino_tiles == "f63" and X.wino63_ok(ps, ps, MASK_FILTERS, MASK_FILTERS)
+        t63 = self.wino_tiles == "f63" and X.wino63_ok(ps, ps, F, F)
         # conv1 too, when its backward has the matching kernels (the lazy-BN gradients of the sparse backward) or there is none
-        c1_63 = (t63 and X.wino63_ok(ps, ps, cin, MASK_FILTERS) and X.wino63_ok(ps, ps, MASK_FILTERS, cin)
+        c1_63 = (t63 and X.wino63_ok(ps, ps, cin, F) and X.wino63_ok(ps, ps, F, cin)
                  and (not train or (self.lazy_bn1_bwd and self.sparse_mask_bwd)))
         for i in range(1, 5):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
             batch_stats = train and i == 1
             fold = not batch_stats
-            use63 = t63 and (i >= 2 or c1_63)          # this conv's V / M planes are in the F(6,3) layout
-            next63 = t63 and i < 4                     # ... and so are the next conv's
-            T = NR * ((ps + 3) // 4) ** 2
+            t = self._tiling(ps, ps, t63 and (i >= 2 or c1_63))          # the tiling of this conv's V / M planes
+            tn = self._tiling(ps, ps, t63) if i < 4 else None            # ... and of the next conv's
             start, stop = self._timed("mask_conv3x3_fwd")
             start()
             if Vcur is None:
-                if use63:
-                    Vcur = self._new(X.wino63_plane_elems(NR, cin))
-                    if x is None:                         # conv1: crops sampled from the feature map on the fly (roi)
-                        Fm, boxes, bind, fn, fh, fw = roi
-                        self._call_timed("roialign_fwd", "myolo_wino63_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind),
-                                         X.ptr(Vcur), fn, fh, fw, cin, NR, X.stream())
-                    else:
-                        self._call_timed("wino_in", "myolo_wino63_input_transform", X.ptr(x), None, None, ACT_NONE, None, None, X.ptr(Vcur),
-                                         NR, cin, X.stream())
+                Vcur = t.planes(NR, cin)
+                if x is None:                         # conv1: crops sampled from the feature map on the fly (roi)
+                    Fm, boxes, bind, fn, fh, fw = roi
+                    t.input_transform_roialign(Fm, boxes, bind, Vcur, fn, fh, fw, cin, NR)
                 else:
-                    Vcur = self._new(36, T, cin)
-                    if x is None:                         # conv1: crops sampled from the feature map on the fly (roi)
-                        Fm, boxes, bind, fn, fh, fw = roi
-                        self._call_timed("roialign_fwd", "myolo_wino_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind),
-                                         X.ptr(Vcur), fn, fh, fw, cin, NR, ps, ps, X.stream())
-                    else:
-                        self._call_timed("wino_in", "myolo_wino_input_transform", X.ptr(x), X.ptr(Vcur), NR, ps, ps, cin, X.stream())
-            if use63:
-                U, M = self._new(X.wino63_u_elems(cin, MASK_FILTERS)), self._new(X.wino63_plane_elems(NR, MASK_FILTERS))
-                # (the transformed filters: prepared at the step's start in training, X.WeightPrep, else formed into U here)
-                self._call_timed("wino_multiply", "myolo_wino63_multiply_w", X.ptr(Vcur), X.ptr(self.p[cn + "/kernel"]), X.ptr(U), X.ptr(M), NR, cin,
-                                 MASK_FILTERS, X.stream())
-            else:
-                U, M = self._new(X.wino_u_elems(cin, MASK_FILTERS)), self._new(36, T, MASK_FILTERS)
-                X.call("myolo_wino_weight_transform", X.ptr(self.p[cn + "/kernel"]), X.ptr(U), cin, MASK_FILTERS, 0, X.stream())
-                self._call_timed("wino_multiply", "myolo_wino_multiply", X.ptr(Vcur), X.ptr(U), X.ptr(M), NR, ps, ps, cin, MASK_FILTERS,
-                                 X.stream())
+                    t.input_transform(x, Vcur, NR, cin, tag="wino_in")
+            U, M = t.filters(cin, F), t.planes(NR, F)
+            # (the transformed filters: prepared at the step's start in training, X.WeightPrep, else formed into U here)
+            t.multiply(Vcur, self.p[cn + "/kernel"], U, M, NR, cin, F, tag="wino_multiply")
             if i == 1 and train:
                 self.tape["conv1_V"] = Vcur          # reused by conv1's weight gradient
-                self.tape["conv1_V_fmt"] = "f63" if use63 else "f43"
+                self.tape["conv1_V_fmt"] = t.fmt
             convs.append(x)                          # for i >= 3 in training: valid only in the rows of flagged ROIs
             bias = self.p[cn + "/bias"]
             buf = self.bnbuf[bn]
             if fold:
                 X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
                        X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                       X.ptr(buf[2]), X.ptr(buf[3]), MASK_FILTERS, X.stream())
+                       X.ptr(buf[2]), X.ptr(buf[3]), F, X.stream())
                 self.tape[bn] = (None, ACT_RELU, False)       # pre-BN tensor never materialised
-            if fold and i < 4 and use63 == next63:
-                ykeep = self._new(NR * q, MASK_FILTERS) if train else None
-                keep_pre = bool(train)            # what is kept for the positive ROIs is the conv's PRE-BatchNorm output (exact backward, any gamma)
-                if use63:
-                    Vn = self._new(X.wino63_plane_elems(NR, MASK_FILTERS))
-                    if keep_pre and slots is not None:
-                        # the kept rows in COMPACT order (slot of each positive ROI, myolo_positive_index): the sparse backward reads them without a gather
-                        self._call_timed("wino_out_in", "myolo_wino63_output_input_transform_keep_pre_slots", X.ptr(M), X.ptr(bias), X.ptr(buf[2]),
-                                         X.ptr(buf[3]), X.ptr(ykeep), X.ptr(slots), NR, X.ptr(Vn), NR, MASK_FILTERS, ACT_RELU, X.stream())
-                        self.tape.setdefault("compact_rows", set()).add(id(ykeep))
-                    elif keep_pre:
-                        self._call_timed("wino_out_in", "myolo_wino63_output_input_transform_keep_pre", X.ptr(M), X.ptr(bias), X.ptr(buf[2]),
-                                         X.ptr(buf[3]), X.ptr(ykeep), X.ptr(pos_flags), X.ptr(Vn), NR, MASK_FILTERS, ACT_RELU, X.stream())
-                    else:
-                        self._call_timed("wino_out_in", "myolo_wino63_output_input_transform", X.ptr(M), X.ptr(bias), X.ptr(buf[2]),
-                                         X.ptr(buf[3]), X.ptr(ykeep), X.ptr(pos_flags) if train else None, X.ptr(Vn), NR, MASK_FILTERS,
-                                         ACT_RELU, X.stream())
+                # One boundary: M -> [kept rows] -> ReLU(frozen BN) -> the next conv's V planes, or y where the chain ends (conv4; a tiling change:
+                # the next conv transforms y itself).  Training keeps the conv's PRE-BatchNorm output of the positive ROIs (exact backward, any gamma):
+                # in COMPACT order where the tiling can (slot of each positive ROI, myolo_positive_index: the sparse backward reads the rows without a
+                # gather), else flagged-dense.  Inference keeps nothing.
+                chained = tn is t
+                y = None if chained else self._new(NR * q, F)
+                keep = self._new(NR * q, F) if train else None
+                Vn = tn.planes(NR, F) if chained else None
+                compact = keep is not None and slots is not None and t.slots
+                sel, cap = (None, 0) if keep is None else (slots, NR) if compact else (pos_flags, 0)
+                if keep is None or y is None or t.keep_beside_y:
+                    t.boundary(M, bias, buf[2], buf[3], ACT_RELU, y, keep, train, sel, cap, Vn, NR, F, tag="wino_out_in" if chained else None)
                 else:
-                    Vn = self._new(36, T, MASK_FILTERS)
-                    self._call_timed("wino_out_in", "myolo_wino_output_input_transform_keep_pre" if keep_pre else "myolo_wino_output_input_transform",
-                                     X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(ykeep), X.ptr(pos_flags) if train else None, X.ptr(Vn),
-                                     NR, ps, ps, MASK_FILTERS, ACT_RELU, X.stream())
-                if keep_pre:
+                    # (the F(4,3)-tiling output transform has no flagged second output: a second pass writes the pre-BatchNorm rows of every ROI.
+                    #  Non-default tiling; the F(6,3) boundary writes the flagged ROIs' rows in the same pass)
+                    t.boundary(M, bias, buf[2], buf[3], ACT_RELU, y, None, False, None, 0, None, NR, F)
+                    t.boundary(M, bias, None, None, ACT_NONE, keep, None, False, None, 0, None, NR, F)
+                if keep is not None:
                     # the next conv's input and this BatchNorm's backward are both formed from the kept pre-BN rows (mask_head_bwd_sparse: "lazy_bn")
-                    self.tape[bn] = (ykeep, ACT_RELU, False)
-                    x, Vcur = ("lazy_bn", ykeep, bn), Vn
+                    self.tape[bn] = (keep, ACT_RELU, False)
+                    if compact:
+                        self.tape.setdefault("compact_rows", set()).add(id(keep))
+                x = y if not chained else ("lazy_bn", keep, bn) if train else None
+                Vcur = Vn
+            elif 256 % (F // 4) == 0 and i < 4:
+                # training-mode BN behind this conv (bn1): its statistics come out of the output transform, and its
+                # apply + ReLU go into the next conv's input transform -- the normalised activation is never written
+                # (the sparse backward re-applies it to the positive ROIs' rows)
+                y = self._new(NR * q, F)
+                t.output_bn_stats(M, bias, y, NR, F, (X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
+                                                      X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"])))
+                self.tape[bn] = (y, ACT_RELU, True)
+                Vcur = tn.planes(NR, F)
+                if slots is not None and tn.slots:
+                    # ... and conv2's input (bn1's activation) of the positive ROIs in compact order: conv2's weight gradient reads it as it is
+                    a1k = self._new(NR * q, F)
+                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU, keep=a1k, sel=slots, cap=NR)
+                    self.tape["conv2_in_rows"] = a1k
                 else:
-                    x, Vcur = ykeep, Vn
+                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU)
+                x = ("lazy_bn", y, bn)
             else:
-                y = self._new(NR * q, MASK_FILTERS)
-                if fold:
-                    if use63 and train and pos_flags is not None:
-                        ypre = self._new(NR * q, MASK_FILTERS)
-                        if slots is not None:
-                            X.call("myolo_wino63_output_transform_keep_pre_slots", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), X.ptr(ypre),
-                                   X.ptr(slots), NR, NR, MASK_FILTERS, ACT_RELU, X.stream())
-                            self.tape.setdefault("compact_rows", set()).add(id(ypre))
-                        else:
-                            X.call("myolo_wino63_output_transform_keep_pre", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), X.ptr(ypre),
-                                   X.ptr(pos_flags), NR, MASK_FILTERS, ACT_RELU, X.stream())
-                        self.tape[bn] = (ypre, ACT_RELU, False)
-                    elif use63:
-                        X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), NR, MASK_FILTERS,
-                               ACT_RELU, X.stream())
-                    else:
-                        X.call("myolo_wino_output_transform", X.ptr(M), X.ptr(bias), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(y), NR, ps, ps,
-                               MASK_FILTERS, ACT_RELU, X.stream())
-                        if train and self.sparse_mask_bwd:
-                            # (the F(4,3)-tiling output transform has no flagged second output: a second pass writes the pre-BatchNorm rows of every ROI.
-                            #  Non-default tiling; the F(6,3) boundary above writes the flagged ROIs' rows in the same pass)
-                            ypre = self._new(NR * q, MASK_FILTERS)
-                            X.call("myolo_wino_output_transform", X.ptr(M), X.ptr(bias), None, None, X.ptr(ypre), NR, ps, ps, MASK_FILTERS, ACT_NONE, X.stream())
-                            self.tape[bn] = (ypre, ACT_RELU, False)
-                    x = y
-                    Vcur = None                      # (a tiling change at this boundary: the next conv transforms y itself)
-                elif 256 % (MASK_FILTERS // 4) == 0 and i < 4:
-                    # training-mode BN behind this conv (bn1): its statistics come out of the output transform, and its
-                    # apply + ReLU go into the next conv's input transform -- the normalised activation is never written
-                    # (the sparse backward re-applies it to the positive ROIs' rows)
-                    if use63:
-                        self.ws.ensure(X.wino63_out_bn_ws_bytes(NR, MASK_FILTERS))
-                        X.call("myolo_wino63_output_transform_bn_stats", X.ptr(M), X.ptr(bias), X.ptr(y), NR, MASK_FILTERS,
-                               X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
-                               X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                               *self._wsargs(), X.stream())
-                    else:
-                        self.ws.ensure(X.wino_out_bn_ws_bytes(MASK_FILTERS))
-                        X.call("myolo_wino_output_transform_bn_stats", X.ptr(M), X.ptr(bias), X.ptr(y), NR, ps, ps, MASK_FILTERS,
-                               X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
-                               X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                               *self._wsargs(), X.stream())
-                    self.tape[bn] = (y, ACT_RELU, True)
-                    if next63:
-                        Vcur = self._new(X.wino63_plane_elems(NR, MASK_FILTERS))
-                        if slots is not None and train:
-                            # ... and conv2's input (bn1's activation) of the positive ROIs in compact order: conv2's weight gradient reads it as it is
-                            a1k = self._new(NR * q, MASK_FILTERS)
-                            X.call("myolo_wino63_input_transform_slots", X.ptr(y), X.ptr(buf[2]), X.ptr(buf[3]), ACT_RELU, X.ptr(a1k), X.ptr(slots), NR,
-                                   X.ptr(Vcur), NR, MASK_FILTERS, X.stream())
-                            self.tape["conv2_in_rows"] = a1k
-                        else:
-                            X.call("myolo_wino63_input_transform", X.ptr(y), X.ptr(buf[2]), X.ptr(buf[3]), ACT_RELU, None, None, X.ptr(Vcur),
-                                   NR, MASK_FILTERS, X.stream())
-                    else:
-                        Vcur = self._new(36, T, MASK_FILTERS)
-                        X.call("myolo_wino_input_transform_affine", X.ptr(y), X.ptr(buf[2]), X.ptr(buf[3]), ACT_RELU, X.ptr(Vcur),
-                               NR, ps, ps, MASK_FILTERS, X.stream())
-                    x = ("lazy_bn", y, bn)
-                else:
-                    X.call("myolo_wino_output_transform", X.ptr(M), X.ptr(bias), None, None, X.ptr(y), NR, ps, ps, MASK_FILTERS,
-                           ACT_NONE, X.stream())
-                    x = self.bn_act_fwd(bn, y, ACT_RELU, batch_stats)
-                    Vcur = None
+                y = self._new(NR * q, F)
+                t.boundary(M, bias, None, None, ACT_NONE, y, None, False, None, 0, None, NR, F)
+                x = self.bn_act_fwd(bn, y, ACT_RELU, batch_stats)
+                Vcur = None
             stop()
-            cin = MASK_FILTERS
+            cin = F
         return x
 
     def _mask_convs_layerwise(self, x, convs, NR, ps, cin, train, fuse):
@@ -1614,33 +1657,18 @@ class Net(object):
         buf = self.bnbuf[bn]
         x = None
         if self._wino_ok(NR, ps, ps, cf, MASK_FILTERS) and 256 % (MASK_FILTERS // 4) == 0:
-            T = NR * ((ps + 3) // 4) ** 2
             start, stop = self._timed("mask_conv3x3_fwd")
             start()
             bn_args = (X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
                        X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]))
             c1_63 = (self.wino_tiles == "f63" and X.wino63_ok(ps, ps, cf, MASK_FILTERS) and X.wino63_ok(ps, ps, MASK_FILTERS, cf)
                      and self.lazy_bn1_bwd and self.sparse_mask_bwd)
-            if c1_63:          # the F(6,3)/F(4,3) tiling, as in _mask_convs_winograd_chain
-                V, U, M = (self._new(X.wino63_plane_elems(NR, cf)), self._new(X.wino63_u_elems(cf, MASK_FILTERS)),
-                           self._new(X.wino63_plane_elems(NR, MASK_FILTERS)))
-                self._call_timed("roialign_fwd", "myolo_wino63_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(V),
-                                 n, h, w, cf, NR, X.stream())
-                self._call_timed("wino_multiply", "myolo_wino63_multiply_w", X.ptr(V), X.ptr(self.p["myolo_mask_conv1/kernel"]), X.ptr(U), X.ptr(M), NR, cf,
-                                 MASK_FILTERS, X.stream())
-                self.ws.ensure(X.wino63_out_bn_ws_bytes(NR, MASK_FILTERS))
-                X.call("myolo_wino63_output_transform_bn_stats", X.ptr(M), X.ptr(self.p["myolo_mask_conv1/bias"]), X.ptr(y1), NR, MASK_FILTERS,
-                       *bn_args, *self._wsargs(), X.stream())
-            else:
-                V, U, M = self._new(36, T, cf), self._new(X.wino_u_elems(cf, MASK_FILTERS)), self._new(36, T, MASK_FILTERS)
-                self._call_timed("roialign_fwd", "myolo_wino_input_transform_roialign", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(V),
-                                 n, h, w, cf, NR, ps, ps, X.stream())        # ROIAlign fused into the input transform
-                X.call("myolo_wino_weight_transform", X.ptr(self.p["myolo_mask_conv1/kernel"]), X.ptr(U), cf, MASK_FILTERS, 0, X.stream())
-                self._call_timed("wino_multiply", "myolo_wino_multiply", X.ptr(V), X.ptr(U), X.ptr(M), NR, ps, ps, cf, MASK_FILTERS, X.stream())
-                self.ws.ensure(X.wino_out_bn_ws_bytes(MASK_FILTERS))
-                X.call("myolo_wino_output_transform_bn_stats", X.ptr(M), X.ptr(self.p["myolo_mask_conv1/bias"]), X.ptr(y1), NR, ps, ps,
-                       MASK_FILTERS, *bn_args, *self._wsargs(), X.stream())
-            self.tape["conv1_V_fmt"] = "f63" if c1_63 else "f43"
+            t = self._tiling(ps, ps, c1_63)          # the F(6,3)/F(4,3) tiling as in _mask_convs_winograd_chain, else F(4,3)/F(2,3)
+            V, U, M = t.planes(NR, cf), t.filters(cf, MASK_FILTERS), t.planes(NR, MASK_FILTERS)
+            t.input_transform_roialign(Fm, boxes, bind, V, n, h, w, cf, NR)        # ROIAlign fused into the input transform
+            t.multiply(V, self.p["myolo_mask_conv1/kernel"], U, M, NR, cf, MASK_FILTERS, tag="wino_multiply")
+            t.output_bn_stats(M, self.p["myolo_mask_conv1/bias"], y1, NR, MASK_FILTERS, bn_args)
+            self.tape["conv1_V_fmt"] = t.fmt
             stop()
             self.tape["conv1_V"] = V
         else:

@@ -908,11 +908,11 @@ def test_winograd_f63_tiling(N, Cin, Cout, x6, request):
     M = torch.full((X.wino63_plane_elems(N, Cout),), float("nan"), device=DEV)
     ya = new(N, H, W, Cin)
     xin_t, sc_t, sh_t, w_t, b_t = dt(xin), dt(sc), dt(sh), dt(w), dt(b)
-    X.call("myolo_wino63_input_transform", X.ptr(xin_t), X.ptr(sc_t), X.ptr(sh_t), 1, X.ptr(ya), None, X.ptr(V), N, Cin, st)
+    X.call("myolo_wino63_input_transform", X.ptr(xin_t), X.ptr(sc_t), X.ptr(sh_t), 1, X.ptr(ya), None, 0, X.ptr(V), N, Cin, st)
     X.call("myolo_wino63_weight_transform", X.ptr(w_t), X.ptr(U), Cin, Cout, st)
     X.call("myolo_wino63_multiply", X.ptr(V), X.ptr(U), X.ptr(M), N, Cin, Cout, st)
     y = new(N, H, W, Cout)
-    X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(b_t), None, None, X.ptr(y), N, Cout, 0, st)
+    X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(b_t), None, None, 0, X.ptr(y), None, 0, None, 0, None, N, Cout, st)
     torch.cuda.synchronize()
     assert not bool(torch.isnan(V).any()) and not bool(torch.isnan(M).any()), "every plane row must be written"
     a0 = ya.cpu().numpy()                                                       # what the input transform formed on load (one fma)
@@ -935,11 +935,11 @@ def test_winograd_f63_tiling(N, Cin, Cout, x6, request):
         flags[::2] = 1
         yk = torch.full((N, H, W, Cout), float("nan"), device=DEV)
         V2 = torch.full((X.wino63_plane_elems(N, Cout),), float("nan"), device=DEV)
-        X.call("myolo_wino63_output_input_transform", X.ptr(M), X.ptr(b_t), X.ptr(s2), X.ptr(t2), X.ptr(yk), X.ptr(flags), X.ptr(V2), N, Cout, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(b_t), X.ptr(s2), X.ptr(t2), 1, None, X.ptr(yk), 0, X.ptr(flags), 0, X.ptr(V2), N, Cout, st)
         y2 = new(N, H, W, Cout)
-        X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(b_t), X.ptr(s2), X.ptr(t2), X.ptr(y2), N, Cout, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(b_t), X.ptr(s2), X.ptr(t2), 1, X.ptr(y2), None, 0, None, 0, None, N, Cout, st)
         V3 = torch.full((X.wino63_plane_elems(N, Cout),), float("nan"), device=DEV)
-        X.call("myolo_wino63_input_transform", X.ptr(y2), None, None, 0, None, None, X.ptr(V3), N, Cout, st)
+        X.call("myolo_wino63_input_transform", X.ptr(y2), None, None, 0, None, None, 0, X.ptr(V3), N, Cout, st)
         torch.cuda.synchronize()
         assert torch.equal(V2, V3), "fused boundary differs from output transform + input transform"
         assert torch.equal(yk[::2], y2[::2]) and bool(torch.isnan(yk[1::2]).all()), "activation must be written for flagged images only"
@@ -977,34 +977,34 @@ def test_wino63_boundary_packed_equals_legacy(N, C):
         out = {}
         for act in (0, 1, 2):
             V, y = nan(pe), nan(N, 14, 14, C)
-            X.call("myolo_wino63_output_input_transform", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(y), X.ptr(flags), X.ptr(V), N, C, act, st)
+            X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), act, None, X.ptr(y), 0, X.ptr(flags), 0, X.ptr(V), N, C, st)
             out["M->V act%d" % act] = (V, y)
             y2 = nan(N, 14, 14, C)
-            X.call("myolo_wino63_output_transform", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(y2), N, C, act, st)
+            X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), act, X.ptr(y2), None, 0, None, 0, None, N, C, st)
             out["M->y act%d" % act] = (y2,)
             V3, y3 = nan(pe), nan(N, 14, 14, C)
-            X.call("myolo_wino63_input_transform", X.ptr(x), X.ptr(sc), X.ptr(sh), act, X.ptr(y3), X.ptr(flags), X.ptr(V3), N, C, st)
+            X.call("myolo_wino63_input_transform", X.ptr(x), X.ptr(sc), X.ptr(sh), act, X.ptr(y3), X.ptr(flags), 0, X.ptr(V3), N, C, st)
             out["x->V act%d" % act] = (V3, y3)
             V4, Q4 = nan(pe), nan(pe)
             X.call("myolo_wino63_lazybn_transforms", X.ptr(x), X.ptr(dyc), X.ptr(inv), X.ptr(sc), X.ptr(sh), X.ptr(ka), X.ptr(kb), act, X.ptr(V4), X.ptr(Q4), N, C, st)
             out["lazy->VQ act%d" % act] = (V4, Q4)
         V, yp = nan(pe), nan(N, 14, 14, C)
-        X.call("myolo_wino63_output_input_transform", X.ptr(Mp), None, None, None, None, None, X.ptr(V), N, C, 0, st)
+        X.call("myolo_wino63_boundary", X.ptr(Mp), None, None, None, 0, None, None, 0, None, 0, X.ptr(V), N, C, st)
         out["M->V plain"] = (V,)
         V = nan(pe)
-        X.call("myolo_wino63_output_input_transform_keep_pre", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(yp), X.ptr(flags), X.ptr(V), N, C, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, None, X.ptr(yp), 1, X.ptr(flags), 0, X.ptr(V), N, C, st)
         out["M->V keep_pre"] = (V, yp)
         V, ypc = nan(pe), nan(cap, 14, 14, C)
-        X.call("myolo_wino63_output_input_transform_keep_pre_slots", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(ypc), X.ptr(slots), cap, X.ptr(V), N, C, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, None, X.ptr(ypc), 1, X.ptr(slots), cap, X.ptr(V), N, C, st)
         out["M->V keep_pre slots"] = (V, ypc)
         y, yp = nan(N, 14, 14, C), nan(N, 14, 14, C)
-        X.call("myolo_wino63_output_transform_keep_pre", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(y), X.ptr(yp), X.ptr(flags), N, C, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, X.ptr(y), X.ptr(yp), 1, X.ptr(flags), 0, None, N, C, st)
         out["M->y keep_pre"] = (y, yp)
         y, ypc = nan(N, 14, 14, C), nan(cap, 14, 14, C)
-        X.call("myolo_wino63_output_transform_keep_pre_slots", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(y), X.ptr(ypc), X.ptr(slots), cap, N, C, 1, st)
+        X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, X.ptr(y), X.ptr(ypc), 1, X.ptr(slots), cap, None, N, C, st)
         out["M->y keep_pre slots"] = (y, ypc)
         V, yc = nan(pe), nan(cap, 14, 14, C)
-        X.call("myolo_wino63_input_transform_slots", X.ptr(x), X.ptr(sc), X.ptr(sh), 1, X.ptr(yc), X.ptr(slots), cap, X.ptr(V), N, C, st)
+        X.call("myolo_wino63_input_transform", X.ptr(x), X.ptr(sc), X.ptr(sh), 1, X.ptr(yc), X.ptr(slots), cap, X.ptr(V), N, C, st)
         out["x->V slots"] = (V, yc)
         V = nan(pe)
         X.call("myolo_wino63_input_transform_roialign", X.ptr(feat), X.ptr(boxes_t), X.ptr(bind), X.ptr(V), B, FH, FW, C, nb, st)
@@ -1063,7 +1063,7 @@ def test_winograd_f63_conv1_pieces():
     n63 = X.wino63_plane_elems(nb, C)
     V1, V2 = torch.full((n63,), float("nan"), device=DEV), torch.full((n63,), float("nan"), device=DEV)
     X.call("myolo_crop_and_resize_fwd", *a, X.ptr(x), B, FH, FW, C, nb, 14, 14, st)
-    X.call("myolo_wino63_input_transform", X.ptr(x), None, None, 0, None, None, X.ptr(V1), nb, C, st)
+    X.call("myolo_wino63_input_transform", X.ptr(x), None, None, 0, None, None, 0, X.ptr(V1), nb, C, st)
     X.call("myolo_wino63_input_transform_roialign", *a, X.ptr(V2), B, FH, FW, C, nb, st)
     torch.cuda.synchronize()
     assert not bool(torch.isnan(V2).any()) and float((V1 - V2).abs().max()) <= 1e-5 * float(V1.abs().max())
@@ -1085,7 +1085,7 @@ def test_winograd_f63_conv1_pieces():
             X.call("myolo_wino63_output_transform_bn_stats", X.ptr(M), X.ptr(b_t), X.ptr(y), nb, Co, X.ptr(gamma), X.ptr(beta), X.ptr(mean),
                    X.ptr(var), X.ptr(sc), X.ptr(sh), X.ptr(mm), X.ptr(mv), wsb.data_ptr(), wsb.numel(), st)
         else:
-            X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(b_t), None, None, X.ptr(y), nb, Co, 0, st)
+            X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(b_t), None, None, 0, X.ptr(y), None, 0, None, 0, None, nb, Co, st)
             X.call("myolo_bn_stats", X.ptr(y), X.ptr(gamma), X.ptr(beta), X.ptr(mean), X.ptr(var), X.ptr(sc), X.ptr(sh), X.ptr(mm), X.ptr(mv),
                    nb * 196, Co, *ws(), st)
         torch.cuda.synchronize()

@@ -1426,3 +1426,38 @@ def test_step_result_is_lazy_and_train_equals_a_hand_loop():
     mm = out["myolo_mask"]
     assert isinstance(mm, np.ndarray) and mm.shape[:2] == (8, cfg.TRAIN_ROIS_PER_IMAGE) and out["myolo_mask"] is mm
     assert out.device("myolo_mask").is_cuda and dict(out)["loss"] == out["loss"]
+
+
+@pytest.mark.parametrize("tiles,rois", [("f63", "all"), ("f63", "positives"), ("f43", "all"), ("f43", "positives")])
+def test_mask_head_launch_sequence(tiles, rois, monkeypatch):
+    """The ordered list of (C-ABI entry point, integer arguments) the mask head issues over two training steps and one inference forward is
+    exactly tests/mask_head_launches.LAUNCHES -- recorded at the commit before the chain was written against the tiling adapters, the folded
+    F(6,3) entries renamed.  CONV3X3_ALGO='winograd' takes the Winograd chain at this ROI count, ROIAlign fused into conv1's input transform."""
+    import mask_head_launches as L
+    _, P, batch, _ = make_case(ShapesConfig, 128, 0.5, 4)
+    model = MaskYOLO(mode="training", config=L.config(tiles, rois))
+    model.load_state_dict(P)
+    seen = L.run(model, batch, monkeypatch)
+    want = L.LAUNCHES[L.key(tiles, rois)]
+    assert len(seen) == len(want), (len(seen), len(want))
+    for k, (a, b) in enumerate(zip(seen, want)):
+        assert a == b, (k, a, b, seen[max(0, k - 3):k])
+    assert any(n.endswith("_input_transform_roialign") for n, _ in seen)
+
+
+def test_mask_head_launch_table_is_not_hollow():
+    """every form the chain picks occurs in some variant of the table: both F(6,3) entry points, pre-BatchNorm rows (keep_pre) kept by slots
+    (capacity > 0: whenever the step keeps deconv rows, Net.keep_deconv_rows, the F(6,3) tiling is handed slots) and by flags (the F(4,3) tiling
+    has no other form), boundaries that keep nothing (inference), input transforms with and without compact kept rows, ROIAlign fused into both"""
+    import mask_head_launches as L
+    from myolo import _ext as X
+    assert set(L.LAUNCHES) == {L.key(t, r) for t, r in L.VARIANTS}
+    rows = [r for v in L.LAUNCHES.values() for r in v]
+    assert all(n in X.SIGS and len(a) == sum(t in (X.I, X.L) for t in X.SIGS[n]) for n, a in rows)
+    bnd = [a for n, a in rows if n == "myolo_wino63_boundary"]                  # (act, keep_pre, keep_cap, N, C)
+    itr = [a for n, a in rows if n == "myolo_wino63_input_transform"]           # (act, keep_cap, N, C)
+    assert any(a[1] == 1 and a[2] > 0 for a in bnd) and any(a[1] == 0 and a[2] == 0 for a in bnd)
+    assert any(a[1] > 0 for a in itr) and any(a[1] == 0 for a in itr)
+    names = {n for n, _ in rows}
+    assert {"myolo_wino_output_input_transform_keep_pre", "myolo_wino_output_input_transform", "myolo_wino63_input_transform_roialign",
+            "myolo_wino_input_transform_roialign"} <= names

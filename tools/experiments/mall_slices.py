@@ -40,15 +40,15 @@ def chain(n, lo, V, M, tick=None):
             e.record()
             ev.append(e)
     mark()
-    X.call("myolo_wino63_input_transform", X.ptr(yo), X.ptr(sc), X.ptr(sh), 1, None, None, X.ptr(V), n, C, st)
+    X.call("myolo_wino63_input_transform", X.ptr(yo), X.ptr(sc), X.ptr(sh), 1, None, None, 0, X.ptr(V), n, C, st)
     mark()
     for i in range(3):
         X.call("myolo_wino63_multiply_w", X.ptr(V), X.ptr(w[i]), X.ptr(U[i]), X.ptr(M), n, C, C, st)
         mark()
         if i < 2:
-            X.call("myolo_wino63_output_input_transform", X.ptr(M), X.ptr(bias), X.ptr(sc), X.ptr(sh), None, None, X.ptr(V), n, C, 1, st)
+            X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(bias), X.ptr(sc), X.ptr(sh), 1, None, None, 0, None, 0, X.ptr(V), n, C, st)
         else:
-            X.call("myolo_wino63_output_transform", X.ptr(M), X.ptr(bias), X.ptr(sc), X.ptr(sh), X.ptr(y4[lo * q:(lo + n) * q]), n, C, 1, st)
+            X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(bias), X.ptr(sc), X.ptr(sh), 1, X.ptr(y4[lo * q:(lo + n) * q]), None, 0, None, 0, None, n, C, st)
         mark()
     X.call("myolo_deconv2x2s2_mask_fwd", X.ptr(y4[lo * q:(lo + n) * q]), X.ptr(wd), X.ptr(bd), X.ptr(w2), X.ptr(b2), X.ptr(p[lo * 4 * q:(lo + n) * 4 * q]),
            n, 14, 14, C, C, ncls, ws.data_ptr(), ws.numel(), st)

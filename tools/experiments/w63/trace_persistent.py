@@ -15,7 +15,7 @@ pe = X.wino63_plane_elems(NR, C)
 Mp, Vn, b, sc, sh = torch.randn(pe, device=dev), torch.empty(pe, device=dev), torch.randn(C, device=dev), torch.randn(C, device=dev), torch.randn(C, device=dev)
 st = X.stream()
 for _ in range(3):
-    X.call("myolo_wino63_output_input_transform", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), None, None, X.ptr(Vn), NR, C, 1, st)
+    X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, None, None, 0, None, 0, X.ptr(Vn), NR, C, st)
 torch.cuda.synchronize()
 lib = ctypes.CDLL(os.environ["MYOLO_LIB"])
 n = 8192 * 9 * 8

@@ -87,14 +87,14 @@ def main():
         # the layer boundary M_i -> (output transform, bias, affine, ReLU) -> LDS -> input transform -> V_{i+1}: reads and writes one plane set each
         pe = X.wino63_plane_elems(NR, C)
         Mp, Vn, b, sc, sh = rn(pe), torch.empty(pe, device=dev), rn(C), rn(C), rn(C)
-        fn = lambda: X.call("myolo_wino63_output_input_transform", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), None, None, X.ptr(Vn), NR, C, 1, st)   # noqa: E731
+        fn = lambda: X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, None, None, 0, None, 0, X.ptr(Vn), NR, C, st)   # noqa: E731
         ms = timeit(fn, a.iters)
         print("wino63_boundary<M,V> NR=%d: %.3f ms  %.0f GB/s (%.2f GB read + written)" % (NR, ms, 2 * pe * 4 / ms / 1e6, 2 * pe * 4 / 1e9))
         y = torch.empty(M, C, device=dev)
-        fn = lambda: X.call("myolo_wino63_output_transform", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), X.ptr(y), NR, C, 1, st)   # noqa: E731
+        fn = lambda: X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), X.ptr(sc), X.ptr(sh), 1, X.ptr(y), None, 0, None, 0, None, NR, C, st)   # noqa: E731
         ms = timeit(fn, a.iters)
         print("wino63_boundary<M,none> NR=%d: %.3f ms  %.0f GB/s" % (NR, ms, (pe + M * C) * 4 / ms / 1e6))
-        fn = lambda: X.call("myolo_wino63_input_transform", X.ptr(y), X.ptr(sc), X.ptr(sh), 1, None, None, X.ptr(Vn), NR, C, st)   # noqa: E731
+        fn = lambda: X.call("myolo_wino63_input_transform", X.ptr(y), X.ptr(sc), X.ptr(sh), 1, None, None, 0, X.ptr(Vn), NR, C, st)   # noqa: E731
         ms = timeit(fn, a.iters)
         print("wino63_boundary<act,V> NR=%d: %.3f ms  %.0f GB/s" % (NR, ms, (pe + M * C) * 4 / ms / 1e6))
     elif a.which == "wino63_lazy":
@@ -158,9 +158,9 @@ def main():
 
         def fn():
             X.call("myolo_wino63_weight_transform", X.ptr(w), X.ptr(U), C, C, st)
-            X.call("myolo_wino63_input_transform", X.ptr(x), None, None, 0, None, None, X.ptr(V), NR, C, st)
+            X.call("myolo_wino63_input_transform", X.ptr(x), None, None, 0, None, None, 0, X.ptr(V), NR, C, st)
             X.call("myolo_wino63_multiply", X.ptr(V), X.ptr(U), X.ptr(Mp), NR, C, C, st)
-            X.call("myolo_wino63_output_transform", X.ptr(Mp), X.ptr(b), None, None, X.ptr(y), NR, C, 0, st)
+            X.call("myolo_wino63_boundary", X.ptr(Mp), X.ptr(b), None, None, 0, X.ptr(y), None, 0, None, 0, None, NR, C, st)
         ms = timeit(fn, a.iters)
         flop = 2.0 * M * 9 * C * C
         print("wino63_fwd M=%d: %.3f ms  %.1f direct-equivalent TFLOP/s (direct-conv FLOPs / time)" % (M, ms, flop / ms / 1e9))

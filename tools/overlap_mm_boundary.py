@@ -25,7 +25,7 @@ s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
 X.call("myolo_wino63_weight_transform", X.ptr(w), X.ptr(U), C, C, torch.cuda.current_stream().cuda_stream)
 torch.cuda.synchronize()
 def mm(V, M, st): X.call("myolo_wino63_multiply", X.ptr(V), X.ptr(U), X.ptr(M), NR, C, C, st.cuda_stream)
-def bnd(M, V, st): X.call("myolo_wino63_output_input_transform", X.ptr(M), X.ptr(b), None, None, None, None, X.ptr(V), NR, C, 1, st.cuda_stream)
+def bnd(M, V, st): X.call("myolo_wino63_boundary", X.ptr(M), X.ptr(b), None, None, 1, None, None, 0, None, 0, X.ptr(V), NR, C, st.cuda_stream)
 def timed(fn, iters=30):
     for _ in range(30): fn()          # steady state: the first ~25 launches after idle run through a clock transient (profiles/r3_notes.md)
     torch.cuda.synchronize()
