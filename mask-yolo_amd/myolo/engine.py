@@ -227,6 +227,67 @@ class _Side(object):
         self.stream, self.ws, self.pending = stream, ws, False
 
 
+ROWS_ALL, ROWS_SLOTS, ROWS_POS = "all", "slots", "positives"
+
+
+class _Saved(object):
+    """One tensor the mask head's forward keeps for its backward, and how to read the positive ROIs' part of it.  order -- ROWS_ALL: one block of
+    rows per ROI, over all NR ROIs; ROWS_SLOTS: compact, block k = positive k, `cap` blocks (fewer than positives: nothing usable);
+    ROWS_POS: the positives only, the forward ran on them alone.  bn -- None: the rows are an activation; else the BatchNorm layer (frozen, or
+    bn1 on its batch statistics) whose PRE-BatchNorm input they are: the activation is relu(rows * bnbuf[bn][2] + bnbuf[bn][3])."""
+    __slots__ = ("t", "order", "bn", "cap", "_rows")
+
+    def __init__(self, t, order, bn=None, cap=None):
+        self.t, self.order, self.bn, self.cap, self._rows = t, order, bn, cap, None
+
+    def rows(self, net, pos, group_rows):
+        """the positives' rows: the tensor itself, a view of its first NP blocks, or a myolo_gather_groups launch -- issued once (a conv's input the
+        forward normalised on load and the kept input of the BatchNorm in front of it are one value)"""
+        if self._rows is None:
+            assert self.order != ROWS_SLOTS or pos.NP <= self.cap
+            self._rows = (self.t if self.order == ROWS_POS else self.t[:pos.NP * group_rows] if self.order == ROWS_SLOTS
+                          else net._gather(self.t, pos.idx, pos.NP, group_rows))
+        return self._rows
+
+    def act(self, net, pos, group_rows):
+        """the positives' activation: their rows, or ReLU(BatchNorm) of those -- from a ROI-ordered tensor not gathered yet in ONE launch that
+        leaves the gathered pre-BatchNorm rows too (the BatchNorm's backward reads them)"""
+        if self.bn is None:
+            return self.rows(net, pos, group_rows)
+        n, C = pos.NP * group_rows, self.t.shape[1]
+        a = net._new(n, C)
+        if self.order == ROWS_ALL and self._rows is None:
+            buf = net.bnbuf[self.bn]
+            self._rows = net._new(n, C)
+            X.call("myolo_gather_groups_affine_act", X.ptr(self.t), X.ptr(pos.idx), X.ptr(buf[2]), X.ptr(buf[3]), ACT_RELU,
+                   X.ptr(self._rows), X.ptr(a), pos.NP, group_rows, C, X.stream())
+        else:
+            net._bn_relu(self.bn, self.rows(net, pos, group_rows), a)
+        return a
+
+
+class _Positives(object):
+    """The positive ROIs of a training step (the first n_pos ROIs of each image, model.py:593): idx [NP] their flat ROI indices, inv [NR] ROI ->
+    compact slot or -1, NP their number -- None until the host has read the counts (Net._positive_index); only: the forward ran on them alone."""
+    __slots__ = ("NP", "idx", "inv", "only")
+
+    def __init__(self, NP, idx, inv, only=False):
+        self.NP, self.idx, self.inv, self.only = NP, idx, inv, only
+
+
+class _MaskTape(object):
+    """tape["mask"]: what a mask-head forward leaves for the backward.  boxes / bind / fshape / NR: the ROI geometry; pos: the _Positives (set by
+    whoever knows them first: the step in front of an all-ROI forward, the positives-only forward, else the sparse backward); xin[i], pre[i]
+    (i = 1..4): conv i's input and bn i's kept pre-BatchNorm input as _Saved (None or no entry: never materialised); a4: conv4's activation;
+    deconv: the ReLU'd deconv output -- whole, the positives' rows in slot order with their capacity, or None; conv1_V / conv1_V_tiling: conv1's
+    Winograd-transformed input for its weight gradient and its tiling.  tape[<bn layer>] = (y, act, batch_stats) stays beside it, as in the trunk."""
+    __slots__ = ("boxes", "bind", "fshape", "NR", "pos", "xin", "pre", "a4", "deconv", "conv1_V", "conv1_V_tiling")
+
+    def __init__(self, pos=None):
+        self.pos, self.a4, self.deconv, self.conv1_V, self.conv1_V_tiling = pos, None, None, None, "f43"
+        self.xin, self.pre = {}, {}
+
+
 class _Wino43(object):
     """The F(4,3)/F(2,3) Winograd tiling of an h x w map (csrc/wino_kernels.hip: the myolo_wino_* entries) behind the method set the engine's 3x3
     convs are written against.  _Wino63 is the same set on the F(6,3)/F(4,3) tiling; what one tiling cannot do is a capability the caller asks."""
@@ -637,27 +698,19 @@ class Net(object):
     def bn_act_fwd(self, name, y, act, batch_stats):
         """y [M,C] pre-BN conv output.  Returns act(BN(y)); saves what backward needs."""
         M, C = y.shape
-        buf = self.bnbuf[name]
-        mean, var, scale, shift = buf[0], buf[1], buf[2], buf[3]
+        scale, shift = self.bnbuf[name][2:4]
+        self.tape[name] = (y, act, batch_stats)
+        a = self._new(M, C)
         if batch_stats:
-            X.call("myolo_bn_stats", X.ptr(y), X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]),
-                   X.ptr(mean), X.ptr(var), X.ptr(scale), X.ptr(shift),
-                   X.ptr(self.s[name + "/moving_mean"]), X.ptr(self.s[name + "/moving_variance"]),
-                   M, C, *self._wsargs(), X.stream())
+            X.call("myolo_bn_stats", X.ptr(y), *self._bn_args(name), M, C, *self._wsargs(), X.stream())
         elif C % 4 == 0 and 256 % (C // 4) == 0:       # frozen BN: coefficients + apply + activation in one launch
-            a = self._new(M, C)
             X.call("myolo_bn_frozen_apply_act", X.ptr(y), X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]),
                    X.ptr(self.s[name + "/moving_mean"]), X.ptr(self.s[name + "/moving_variance"]), X.ptr(scale), X.ptr(shift), X.ptr(a),
                    M, C, act, X.stream())
-            self.tape[name] = (y, act, batch_stats)
             return a
         else:
-            X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]),
-                   X.ptr(self.s[name + "/moving_mean"]), X.ptr(self.s[name + "/moving_variance"]),
-                   X.ptr(scale), X.ptr(shift), C, X.stream())
-        a = self._new(M, C)
+            self._bn_frozen_coeffs(name)
         X.call("myolo_bn_apply_act", X.ptr(y), X.ptr(scale), X.ptr(shift), X.ptr(a), M, C, act, X.stream())
-        self.tape[name] = (y, act, batch_stats)
         return a
 
     def bn_act_bwd(self, name, da, y_override=None):
@@ -1102,17 +1155,13 @@ class Net(object):
         """BatchNorm coefficients of y [M,C] -> (scale, shift) device pointers; tapes (y, act, train) for bn_act_bwd"""
         M, C = y.shape
         if train:
-            buf = self.bnbuf[name]
-            X.call("myolo_bn_stats", X.ptr(y), *[X.ptr(t) for t in (self.p[name + "/gamma"], self.p[name + "/beta"], buf[0], buf[1], buf[2], buf[3],
-                   self.s[name + "/moving_mean"], self.s[name + "/moving_variance"])], M, C, *self._wsargs(), X.stream())
+            X.call("myolo_bn_stats", X.ptr(y), *self._bn_args(name), M, C, *self._wsargs(), X.stream())
             self.tape[name] = (y, act, True)
-            return X.ptr(buf[2]), X.ptr(buf[3])
-        if self.fold_frozen_bn:
+        elif self.fold_frozen_bn:
             return self._frozen_affine(name)              # (computed for every trunk BatchNorm at the start of the forward)
-        buf = self.bnbuf[name]
-        X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[name + "/gamma"]), X.ptr(self.p[name + "/beta"]), X.ptr(self.s[name + "/moving_mean"]),
-               X.ptr(self.s[name + "/moving_variance"]), X.ptr(buf[2]), X.ptr(buf[3]), C, X.stream())
-        return X.ptr(buf[2]), X.ptr(buf[3])
+        else:
+            self._bn_frozen_coeffs(name)
+        return X.ptr(self.bnbuf[name][2]), X.ptr(self.bnbuf[name][3])
 
     def _rn_bn_relu(self, name, y, train):
         sc, sh = self._rn_bn(name, y, ACT_RELU, train)
@@ -1317,109 +1366,150 @@ class Net(object):
         return t
 
     # ---- mask head -----------------------------------------------------------
+    def _mask_rois(self, rois, fshape, taped=True):
+        """every mask-head forward's prelude: the record with the geometry of rois [B,R,4] (x1,y1,x2,y2); taped: the step's tape["mask"]"""
+        B, R = rois.shape[:2]
+        rec = self.tape.setdefault("mask", _MaskTape()) if taped else _MaskTape()
+        boxes = rois.reshape(B * R, 4)                            # model.py:385-387: read as (y1,x1,y2,x2)
+        rec.boxes = boxes if self.cfg.ROI_BOX_ORDER == "xyxy_as_yxyx" else boxes[:, [1, 0, 3, 2]].contiguous()
+        rec.bind, rec.fshape, rec.NR = self._box_image_index(B, R), fshape, B * R
+        return rec
+
     def mask_head_fwd(self, Fm, fshape, rois, train, pos_flags=None, keep=None):
         """rois [B,R,4] (x1,y1,x2,y2).  Returns pred masks [B*R, mh*mw, C] (post-sigmoid).  keep = (inv_d, cap): the fused deconv + mask pass
         also writes the ReLU'd deconv output of the ROIs with a compact slot < cap (the sparse backward reads it instead of re-running the deconv)."""
-        cfg = self.cfg
-        B, R = rois.shape[:2]
         n, h, w, cf = fshape
-        ps = cfg.MASK_POOL_SIZE
-        if cfg.ROI_BOX_ORDER == "xyxy_as_yxyx":
-            boxes = rois.reshape(B * R, 4)                    # model.py:385-387: read as (y1,x1,y2,x2)
-        else:
-            boxes = rois.reshape(B * R, 4)[:, [1, 0, 3, 2]].contiguous()
-        bind = self._box_image_index(B, R)
-        NR = B * R
-        self.tape["roi"] = (boxes, bind, fshape, NR)
-        cin = cf
-        convs = []
+        ps, C = self.cfg.MASK_POOL_SIZE, self.cfg.NUM_CLASSES
+        rec = self._mask_rois(rois, fshape)
+        NR, q = rec.NR, ps * ps
         fuse = self.sparse_mask_bwd or not train     # frozen BN + ReLU folded into the conv epilogue
-        q = ps * ps
         # Winograd chain: where conv_i's epilogue is foldable (frozen BN) and conv_{i+1} is a Winograd conv too, the layer
         # boundary is ONE pass per ROI through LDS (M_i -> V_{i+1}); the activation in between is written only for the ROIs
         # the sparse backward will gather (pos_flags), and not at all in inference.
         chain = (fuse and self._wino_ok(NR, ps, ps, cf, MASK_FILTERS) and self._wino_ok(NR, ps, ps, MASK_FILTERS, MASK_FILTERS)
-                 and MASK_FILTERS % 32 == 0 and ((ps + 3) // 4) ** 2 <= 32 and q * 128 <= 65536
+                 and MASK_FILTERS % 32 == 0 and 256 % (MASK_FILTERS // 4) == 0 and ((ps + 3) // 4) ** 2 <= 32 and q * 128 <= 65536
                  and (not train or pos_flags is not None))
         if chain:
             # ROIAlign is fused into conv1's input transform: the [NR,14,14,256] crops are never written
-            x = self._mask_convs_winograd_chain(None, convs, NR, ps, cf, train, pos_flags, roi=(Fm, boxes, bind, n, h, w),
-                                                slots=keep[0] if keep is not None else None)
+            rec.a4 = self._mask_convs_winograd_chain(rec, Fm, ps, cf, train, pos_flags, slots=keep[0] if keep is not None else None)
         else:
             x = self._new(NR * ps * ps, cf)
-            self._call_timed("roialign_fwd", "myolo_crop_and_resize_fwd", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(x),
+            self._call_timed("roialign_fwd", "myolo_crop_and_resize_fwd", X.ptr(Fm), X.ptr(rec.boxes), X.ptr(rec.bind), X.ptr(x),
                              n, h, w, cf, NR, ps, ps, X.stream())
-            x = self._mask_convs_layerwise(x, convs, NR, ps, cf, train, fuse)
-        C = cfg.NUM_CLASSES
-        p = self._new(NR * 4 * ps * ps, C)
-        if fuse and C <= 4 and MASK_FILTERS % 128 == 0:
-            # deconv + ReLU + 1x1 + sigmoid in one pass; the 28x28x256 tensor is never written.  The sparse backward
-            # recomputes it for the positive ROIs (mask_head_bwd_sparse); the dense backward needs it whole.
-            self.ws.ensure(X.deconv_mask_ws_bytes(NR, ps, ps, MASK_FILTERS, MASK_FILTERS, C))
-            d = None
-            if keep is not None and MASK_FILTERS % 256 == 0:
-                inv_d, cap = keep
-                dk = self._new(cap * 4 * q, MASK_FILTERS)
-                X.call("myolo_deconv2x2s2_mask_fwd_keep", X.ptr(x), X.ptr(self.p["myolo_mask_deconv/kernel"]),
-                       X.ptr(self.p["myolo_mask_deconv/bias"]), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(self.p["myolo_mask/bias"]),
-                       X.ptr(p), NR, ps, ps, MASK_FILTERS, MASK_FILTERS, C, X.ptr(inv_d), X.ptr(dk), cap, *self._wsargs(), X.stream())
-                d = ("kept", dk, cap)
-            else:
-                X.call("myolo_deconv2x2s2_mask_fwd", X.ptr(x), X.ptr(self.p["myolo_mask_deconv/kernel"]),
-                       X.ptr(self.p["myolo_mask_deconv/bias"]), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(self.p["myolo_mask/bias"]),
-                       X.ptr(p), NR, ps, ps, MASK_FILTERS, MASK_FILTERS, C, *self._wsargs(), X.stream())
-        else:
-            d = self._new(NR * 4 * ps * ps, MASK_FILTERS)
-            X.call("myolo_deconv2x2s2_fwd", X.ptr(x), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(self.p["myolo_mask_deconv/bias"]),
-                   X.ptr(d), NR, ps, ps, MASK_FILTERS, MASK_FILTERS, ACT_RELU, *self._wsargs(), X.stream())
-            X.call("myolo_mask_head_out_fwd", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(self.p["myolo_mask/bias"]), X.ptr(p),
-                   NR * 4 * ps * ps, MASK_FILTERS, C, X.stream())
-        self.tape["mask"] = (convs, x, d)
+            rec.a4 = self._mask_convs_layerwise(rec, x, ps, cf, train, fuse)
+        x = rec.a4.t
+        if not (fuse and C <= 4 and MASK_FILTERS % 128 == 0):
+            return self._mask_deconv_out_fwd(rec, x, NR, ROWS_ALL)
+        # deconv + ReLU + 1x1 + sigmoid in one pass; the 28x28x256 tensor is never written.  The sparse backward
+        # recomputes it for the positive ROIs (_mask_out_deconv_bwd_pos); the dense backward needs it whole.
+        p = self._new(NR * 4 * q, C)
+        self.ws.ensure(X.deconv_mask_ws_bytes(NR, ps, ps, MASK_FILTERS, MASK_FILTERS, C))
+        entry, kept = "myolo_deconv2x2s2_mask_fwd", ()
+        if keep is not None and MASK_FILTERS % 256 == 0:
+            inv_d, cap = keep
+            rec.deconv = _Saved(self._new(cap * 4 * q, MASK_FILTERS), ROWS_SLOTS, cap=cap)
+            entry, kept = entry + "_keep", (X.ptr(inv_d), X.ptr(rec.deconv.t), cap)
+        X.call(entry, X.ptr(x), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(self.p["myolo_mask_deconv/bias"]), X.ptr(self.p["myolo_mask/kernel"]),
+               X.ptr(self.p["myolo_mask/bias"]), X.ptr(p), NR, ps, ps, MASK_FILTERS, MASK_FILTERS, C, *kept, *self._wsargs(), X.stream())
         return p
 
-    def _mask_convs_winograd_chain(self, x, convs, NR, ps, cin, train, pos_flags, roi=None, slots=None):
-        """myolo_mask_conv1-4 (+bn, ReLU) as a chain of Winograd stages; appends each conv's input to `convs` (an input the
-        forward never materialised is recorded as ("lazy_bn", pre-BN tensor, bn layer)).  Returns conv4's activation.
+    def _deconv_relu_fwd(self, a4, N):
+        """ReLU(deconv 2x2 / s2 + bias) of conv4's activation of N ROIs -> [N * 4 * ps^2, MASK_FILTERS]"""
+        ps = self.cfg.MASK_POOL_SIZE
+        d = self._new(N * 4 * ps * ps, MASK_FILTERS)
+        X.call("myolo_deconv2x2s2_fwd", X.ptr(a4), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(self.p["myolo_mask_deconv/bias"]),
+               X.ptr(d), N, ps, ps, MASK_FILTERS, MASK_FILTERS, ACT_RELU, *self._wsargs(), X.stream())
+        return d
+
+    def _mask_deconv_out_fwd(self, rec, a4, N, order):
+        """the unfused end of the head over N ROIs: the deconv output, written whole and recorded, -> the masks, its 1x1 + sigmoid [N * 4 * ps^2, C]"""
+        rec.a4, rec.deconv = _Saved(a4, order), _Saved(self._deconv_relu_fwd(a4, N), order)
+        d = rec.deconv.t
+        p = self._new(d.shape[0], self.cfg.NUM_CLASSES)
+        X.call("myolo_mask_head_out_fwd", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(self.p["myolo_mask/bias"]), X.ptr(p),
+               d.shape[0], MASK_FILTERS, self.cfg.NUM_CLASSES, X.stream())
+        return p
+
+    def _bn_frozen_coeffs(self, bn):
+        """scale / shift of a BatchNorm on its moving statistics into bnbuf[bn][2:4]"""
+        buf = self.bnbuf[bn]
+        X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(self.s[bn + "/moving_mean"]),
+               X.ptr(self.s[bn + "/moving_variance"]), X.ptr(buf[2]), X.ptr(buf[3]), buf.shape[1], X.stream())
+
+    def _bn_relu(self, bn, rows, out):
+        """out = relu(rows * scale + shift) with the coefficients layer `bn`'s forward left in bnbuf"""
+        X.call("myolo_bn_apply_act", X.ptr(rows), X.ptr(self.bnbuf[bn][2]), X.ptr(self.bnbuf[bn][3]), X.ptr(out), rows.shape[0], rows.shape[1],
+               ACT_RELU, X.stream())
+
+    def _conv1_f63(self, ps, cin, train):
+        """conv1 on the F(6,3)/F(4,3) tiling: in training only where its backward has the matching kernels -- the lazy-BN gradients of the sparse
+        backward, the data gradient's included (_mask_conv1_bwd runs BOTH off one pass over conv1's output whenever V is in this layout)"""
+        return (self.wino_tiles == "f63" and X.wino63_ok(ps, ps, cin, MASK_FILTERS) and X.wino63_ok(ps, ps, MASK_FILTERS, cin)
+                and (not train or (self.lazy_bn1_bwd and self.sparse_mask_bwd)))
+
+    def _mask_conv1_stats_fwd(self, rec, Fm, t, cin):
+        """Training forward of conv1 over every ROI on the tiling t, ROIAlign fused into its input transform (the crops are never written), bn1's
+        batch statistics out of its output transform.  Returns the conv output y1 (bn1's input); the V planes stay for conv1's weight gradient."""
+        n, h, w, _ = rec.fshape
+        NR, F, bn = rec.NR, MASK_FILTERS, "myolo_mask_bn1"
+        V, U, M = t.planes(NR, cin), t.filters(cin, F), t.planes(NR, F)
+        t.input_transform_roialign(Fm, rec.boxes, rec.bind, V, n, h, w, cin, NR)
+        t.multiply(V, self.p["myolo_mask_conv1/kernel"], U, M, NR, cin, F, tag="wino_multiply")
+        y1 = self._new(NR * self.cfg.MASK_POOL_SIZE ** 2, F)
+        t.output_bn_stats(M, self.p["myolo_mask_conv1/bias"], y1, NR, F, self._bn_args(bn))
+        self.tape[bn] = (y1, ACT_RELU, True)
+        rec.pre[1] = _Saved(y1, ROWS_ALL, bn)
+        # the layout conv1's weight gradient finds V in.  "f63" promises the backward the F(6,3) data-gradient kernels too (_conv1_f63)
+        assert t.fmt == "f43" or self._wino63(self.cfg.MASK_POOL_SIZE, self.cfg.MASK_POOL_SIZE, F, cin)
+        rec.conv1_V, rec.conv1_V_tiling = V, t.fmt
+        return y1
+
+    def _mask_convs_winograd_chain(self, rec, Fm, ps, cin, train, pos_flags, slots=None):
+        """myolo_mask_conv1-4 (+bn, ReLU) as a chain of Winograd stages, conv1 reading its crops off the feature map Fm; records each conv's input and
+        each BatchNorm's kept input in rec (an input never materialised: the pre-BatchNorm rows and their layer).  Returns conv4's activation.
         cfg.WINOGRAD_TILES = "f63": conv2-4 (whose inputs and outputs are MASK_FILTERS wide 14x14 maps) use the F(6,3)/F(4,3)
         tiling of csrc/wino63_kernels.hip (400 instead of 484 point-tiles per ROI); conv1 keeps the F(4,3)/F(2,3) tiling (its input
         transform is fused with ROIAlign and its V planes feed the weight gradient) unless its backward has the matching kernels.
         Written once against the tiling adapters (_Wino43 / _Wino63); tests/mask_head_launches.py pins what it launches."""
-        q = ps * ps
-        F = MASK_FILTERS
-        Vcur = None
+        q, F, NR = ps * ps, MASK_FILTERS, rec.NR
+        n, h, w, _ = rec.fshape
+        x = Vcur = None
         t63 = self.wino_tiles == "f63" and X.wino63_ok(ps, ps, F, F)
-        # conv1 too, when its backward has the matching kernels (the lazy-BN gradients of the sparse backward) or there is none
-        c1_63 = (t63 and X.wino63_ok(ps, ps, cin, F) and X.wino63_ok(ps, ps, F, cin)
-                 and (not train or (self.lazy_bn1_bwd and self.sparse_mask_bwd)))
+        c1_63 = t63 and self._conv1_f63(ps, cin, train)
         for i in range(1, 5):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
-            batch_stats = train and i == 1
-            fold = not batch_stats
             t = self._tiling(ps, ps, t63 and (i >= 2 or c1_63))          # the tiling of this conv's V / M planes
             tn = self._tiling(ps, ps, t63) if i < 4 else None            # ... and of the next conv's
+            buf = self.bnbuf[bn]
             start, stop = self._timed("mask_conv3x3_fwd")
             start()
-            if Vcur is None:
-                Vcur = t.planes(NR, cin)
-                if x is None:                         # conv1: crops sampled from the feature map on the fly (roi)
-                    Fm, boxes, bind, fn, fh, fw = roi
-                    t.input_transform_roialign(Fm, boxes, bind, Vcur, fn, fh, fw, cin, NR)
+            if train and i == 1:
+                # training-mode BN behind this conv (bn1): its statistics come out of the output transform, and its
+                # apply + ReLU go into the next conv's input transform -- the normalised activation is never written
+                # (the sparse backward re-applies it to the positive ROIs' rows)
+                y = self._mask_conv1_stats_fwd(rec, Fm, t, cin)
+                Vcur = tn.planes(NR, F)
+                if slots is not None and tn.slots:
+                    # ... and conv2's input (bn1's activation) of the positive ROIs in compact order: conv2's weight gradient reads it as it is
+                    a1k = self._new(NR * q, F)
+                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU, keep=a1k, sel=slots, cap=NR)
+                    x = _Saved(a1k, ROWS_SLOTS, cap=NR)
                 else:
-                    t.input_transform(x, Vcur, NR, cin, tag="wino_in")
-            U, M = t.filters(cin, F), t.planes(NR, F)
-            # (the transformed filters: prepared at the step's start in training, X.WeightPrep, else formed into U here)
-            t.multiply(Vcur, self.p[cn + "/kernel"], U, M, NR, cin, F, tag="wino_multiply")
-            if i == 1 and train:
-                self.tape["conv1_V"] = Vcur          # reused by conv1's weight gradient
-                self.tape["conv1_V_fmt"] = t.fmt
-            convs.append(x)                          # for i >= 3 in training: valid only in the rows of flagged ROIs
-            bias = self.p[cn + "/bias"]
-            buf = self.bnbuf[bn]
-            if fold:
-                X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
-                       X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                       X.ptr(buf[2]), X.ptr(buf[3]), F, X.stream())
-                self.tape[bn] = (None, ACT_RELU, False)       # pre-BN tensor never materialised
+                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU)
+                    x = rec.pre[1]
+            else:
+                if Vcur is None:
+                    Vcur = t.planes(NR, cin)
+                    if x is None:                         # conv1: crops sampled from the feature map on the fly
+                        t.input_transform_roialign(Fm, rec.boxes, rec.bind, Vcur, n, h, w, cin, NR)
+                    else:
+                        t.input_transform(x.t, Vcur, NR, cin, tag="wino_in")
+                U, M = t.filters(cin, F), t.planes(NR, F)
+                # (the transformed filters: prepared at the step's start in training, X.WeightPrep, else formed into U here)
+                t.multiply(Vcur, self.p[cn + "/kernel"], U, M, NR, cin, F, tag="wino_multiply")
+                rec.xin[i] = x                           # for i >= 3 in training: valid only in the rows of the positive ROIs
+                bias = self.p[cn + "/bias"]
+                self._bn_frozen_coeffs(bn)
                 # One boundary: M -> [kept rows] -> ReLU(frozen BN) -> the next conv's V planes, or y where the chain ends (conv4; a tiling change:
                 # the next conv transforms y itself).  Training keeps the conv's PRE-BatchNorm output of the positive ROIs (exact backward, any gamma):
                 # in COMPACT order where the tiling can (slot of each positive ROI, myolo_positive_index: the sparse backward reads the rows without a
@@ -1437,84 +1527,55 @@ class Net(object):
                     #  Non-default tiling; the F(6,3) boundary writes the flagged ROIs' rows in the same pass)
                     t.boundary(M, bias, buf[2], buf[3], ACT_RELU, y, None, False, None, 0, None, NR, F)
                     t.boundary(M, bias, None, None, ACT_NONE, keep, None, False, None, 0, None, NR, F)
-                if keep is not None:
-                    # the next conv's input and this BatchNorm's backward are both formed from the kept pre-BN rows (mask_head_bwd_sparse: "lazy_bn")
-                    self.tape[bn] = (keep, ACT_RELU, False)
-                    if compact:
-                        self.tape.setdefault("compact_rows", set()).add(id(keep))
-                x = y if not chained else ("lazy_bn", keep, bn) if train else None
+                # the next conv's input and this BatchNorm's backward are both formed from the kept pre-BN rows: ONE saved value (inference: none)
+                self.tape[bn] = (keep, ACT_RELU, False)
+                kept = rec.pre[i] = _Saved(keep, ROWS_SLOTS if compact else ROWS_ALL, bn, cap=NR) if train else None
+                x = _Saved(y, ROWS_ALL) if y is not None else kept
                 Vcur = Vn
-            elif 256 % (F // 4) == 0 and i < 4:
-                # training-mode BN behind this conv (bn1): its statistics come out of the output transform, and its
-                # apply + ReLU go into the next conv's input transform -- the normalised activation is never written
-                # (the sparse backward re-applies it to the positive ROIs' rows)
-                y = self._new(NR * q, F)
-                t.output_bn_stats(M, bias, y, NR, F, (X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
-                                                      X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"])))
-                self.tape[bn] = (y, ACT_RELU, True)
-                Vcur = tn.planes(NR, F)
-                if slots is not None and tn.slots:
-                    # ... and conv2's input (bn1's activation) of the positive ROIs in compact order: conv2's weight gradient reads it as it is
-                    a1k = self._new(NR * q, F)
-                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU, keep=a1k, sel=slots, cap=NR)
-                    self.tape["conv2_in_rows"] = a1k
-                else:
-                    tn.input_transform(y, Vcur, NR, F, buf[2], buf[3], ACT_RELU)
-                x = ("lazy_bn", y, bn)
-            else:
-                y = self._new(NR * q, F)
-                t.boundary(M, bias, None, None, ACT_NONE, y, None, False, None, 0, None, NR, F)
-                x = self.bn_act_fwd(bn, y, ACT_RELU, batch_stats)
-                Vcur = None
             stop()
             cin = F
         return x
 
-    def _mask_convs_layerwise(self, x, convs, NR, ps, cin, train, fuse):
-        """myolo_mask_conv1-4 one self-contained conv op at a time (direct kernels or un-chained Winograd)."""
+    def _mask_convs_layerwise(self, rec, x, ps, cin, train, fuse):
+        """myolo_mask_conv1-4 one self-contained conv op at a time (direct kernels or un-chained Winograd) from the crops x, recorded as the chain's"""
+        NR = rec.NR
         for i in range(1, 5):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
             y = self._new(NR * ps * ps, MASK_FILTERS)
-            convs.append(x)
+            rec.xin[i] = _Saved(x, ROWS_ALL)
             # bn1 uses batch statistics in training (model.py:690 has no training= argument);
             # bn2-4 are called with training=False (model.py:696,702,708) -> moving statistics
             batch_stats = train and i == 1
             if fuse and not batch_stats:
                 buf = self.bnbuf[bn]
-                X.call("myolo_bn_frozen_coeffs", X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
-                       X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                       X.ptr(buf[2]), X.ptr(buf[3]), MASK_FILTERS, X.stream())
+                self._bn_frozen_coeffs(bn)
                 self.conv3x3_fwd(x, cn, y, NR, ps, ps, cin, MASK_FILTERS, scale=buf[2], shift=buf[3], act=ACT_RELU,
                                  tag="mask_conv3x3_fwd")
                 self.tape[bn] = (None, ACT_RELU, False)       # pre-BN tensor never materialised
                 x = y
             else:
-                # conv1 in training: its transformed input is kept for the dense weight gradient
+                # conv1 in training: its transformed input is kept for the dense weight gradient (in the F(4,3) layout, conv3x3_fwd)
                 v = self.conv3x3_fwd(x, cn, y, NR, ps, ps, cin, MASK_FILTERS, keep_v=train and i == 1 and self.sparse_mask_bwd,
                                      tag="mask_conv3x3_fwd")
                 if v is not None:
-                    self.tape["conv1_V"] = v
+                    rec.conv1_V = v
                 x = self.bn_act_fwd(bn, y, ACT_RELU, batch_stats)
+                rec.pre[i] = _Saved(y, ROWS_ALL, bn)
             cin = MASK_FILTERS
-        return x
+        return _Saved(x, ROWS_ALL)
 
     def mask_head_fwd_bf16(self, Fm, fshape, rois):
         """Inference-only mask head with bf16 activations / fp32 accumulation (cfg.INFERENCE_DTYPE == "bf16").
         Same graph as mask_head_fwd(train=False) (model.py:680-714); the frozen BN of each conv is folded
         into bf16 weights -- packed once per weight version into persistent buffers (_bf16_operand / _infer_prep_sync)."""
         cfg = self.cfg
-        B, R = rois.shape[:2]
         n, h, w, cf = fshape
         ps = cfg.MASK_POOL_SIZE
-        if cfg.ROI_BOX_ORDER == "xyxy_as_yxyx":
-            boxes = rois.reshape(B * R, 4)
-        else:
-            boxes = rois.reshape(B * R, 4)[:, [1, 0, 3, 2]].contiguous()
-        bind = self._box_image_index(B, R)
-        NR = B * R
+        roi = self._mask_rois(rois, fshape, taped=False)
+        NR = roi.NR
         bf = torch.bfloat16
         x = self._new(NR * ps * ps, cf, dtype=bf)
-        self._call_timed("roialign_fwd", "myolo_crop_and_resize_bf16_fwd", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(x),
+        self._call_timed("roialign_fwd", "myolo_crop_and_resize_bf16_fwd", X.ptr(Fm), X.ptr(roi.boxes), X.ptr(roi.bind), X.ptr(x),
                          n, h, w, cf, NR, ps, ps, X.stream())
         cin = cf
         for i in range(1, 5):
@@ -1542,15 +1603,12 @@ class Net(object):
     def mask_head_bwd(self, dz, ids=None):
         """dz [NR*mh*mw, C] gradient wrt the pre-sigmoid mask logits (C > MASK_DENSE_MAX_CLASSES: the selected channel's
         gradient [NR*mh*mw, 1] of myolo_mask_bce_sel, and ids [NR] the class id per ROI).  Returns dF."""
-        cfg = self.cfg
-        convs, a4, d = self.tape["mask"]
-        boxes, bind, fshape, NR = self.tape["roi"]
-        ps = cfg.MASK_POOL_SIZE
-        C = cfg.NUM_CLASSES
+        rec = self.tape["mask"]
+        ps, C, NR = self.cfg.MASK_POOL_SIZE, self.cfg.NUM_CLASSES, rec.NR
         Md = NR * 4 * ps * ps
         dd = self._new(Md, MASK_FILTERS)
-        self._mask_out_bwd(d, dz, ids, dd, Md, C)
-        X.call("myolo_deconv2x2s2_bwd_weight", X.ptr(a4), X.ptr(dd), X.ptr(self.g["myolo_mask_deconv/kernel"]), NR, ps, ps,
+        self._mask_out_bwd(rec.deconv.t, dz, ids, dd, Md, C)
+        X.call("myolo_deconv2x2s2_bwd_weight", X.ptr(rec.a4.t), X.ptr(dd), X.ptr(self.g["myolo_mask_deconv/kernel"]), NR, ps, ps,
                MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
         self.colsum(dd, self.g["myolo_mask_deconv/bias"])
         da = self._new(NR * ps * ps, MASK_FILTERS)
@@ -1560,18 +1618,23 @@ class Net(object):
         for i in range(4, 0, -1):
             cn = "myolo_mask_conv%d" % i
             dy = self.bn_act_bwd("myolo_mask_bn%d" % i, da)
-            xin = convs[i - 1]
+            xin = rec.xin[i].t
             cin = xin.shape[1]
             self.conv3x3_bwd_weight(xin, None, dy, cn, NR, ps, ps, cin, MASK_FILTERS)
             self.colsum(dy, self.g[cn + "/bias"])
             da = self._new(NR * ps * ps, cin)
             self.conv3x3_bwd_data(dy, cn, da, NR, ps, ps, cin, MASK_FILTERS)
-        n, h, w, cf = fshape
-        dF = self._new(n * h * w, cf)
-        X.call("myolo_roialign_bwd_grouped", X.ptr(da), X.ptr(boxes), X.ptr(dF), n, h, w, cf, NR // n, ps, ps, X.stream())
+        dF = self._roialign_bwd(rec, da)
         if self.on_bucket_ready:
             self.on_bucket_ready(BUCKET_MASK_REST)
             self.on_bucket_ready(BUCKET_MASK_CONV1)
+        return dF
+
+    def _roialign_bwd(self, rec, dcrops):
+        """the gradient of every ROI's crop -> dF, the feature map's"""
+        (n, h, w, cf), ps = rec.fshape, self.cfg.MASK_POOL_SIZE
+        dF = self._new(n * h * w, cf)
+        X.call("myolo_roialign_bwd_grouped", X.ptr(dcrops), X.ptr(rec.boxes), X.ptr(dF), n, h, w, cf, rec.NR // n, ps, ps, X.stream())
         return dF
 
     def _mask_out_bwd(self, d, dz, ids, dd, Md, C):
@@ -1615,24 +1678,26 @@ class Net(object):
             self._npos_pinned.copy_(npos, non_blocking=True)
             self._npos_ready.record(self._copy_stream)
 
-    def _positive_index(self, B, R):
-        """(NP, idx_d, inv_d): flat ROI indices of the positives (the first n_pos rows of each image,
-        model.py:593) and the inverse map, from the async copy started by _start_npos_copy."""
+    def _positive_index(self, rec, B, R, only=False):
+        """rec.pos with its count: the flat ROI indices of the positives (the first n_pos rows of each image, model.py:593) and the inverse
+        map, from the async copy started by _start_npos_copy.  only: the caller is the forward that runs on the positives alone."""
+        pos = rec.pos
+        if pos is not None and pos.NP is not None:
+            return pos
         t0 = time.perf_counter()
         self._npos_ready.synchronize()          # the step's one host wait: the per-image positive counts (32 ints) from mid-forward
         self.host_wait_s += time.perf_counter() - t0
         npos_h = self._npos_pinned.numpy()
-        if "pos_index" in self.tape:            # built on the device in front of the forward (myolo_positive_index): only the total is needed here
-            NP = int(np.clip(npos_h[:B], 0, R).sum())
-            self._np_seen = NP
-            return (NP,) + (self.tape["pos_index"] if NP else (None, None))
-        pos = np.concatenate([np.arange(b * R, b * R + int(npos_h[b]), dtype=np.int32) for b in range(B)]) if B else np.zeros(0, np.int32)
-        NP = int(pos.shape[0])
-        if NP == 0:
-            return 0, None, None
-        inv = np.full(B * R, -1, np.int32)
-        inv[pos] = np.arange(NP, dtype=np.int32)
-        return NP, torch.from_numpy(pos).to(self.dev, non_blocking=True), torch.from_numpy(inv).to(self.dev, non_blocking=True)
+        if pos is not None:                     # built on the device in front of the forward (myolo_positive_index): only the total is needed here
+            pos.NP = self._np_seen = int(np.clip(npos_h[:B], 0, R).sum())
+            return pos
+        idx = np.concatenate([np.arange(b * R, b * R + int(npos_h[b]), dtype=np.int32) for b in range(B)]) if B else np.zeros(0, np.int32)
+        pos = rec.pos = _Positives(int(idx.shape[0]), None, None, only)
+        if pos.NP:
+            inv = np.full(B * R, -1, np.int32)
+            inv[idx] = np.arange(pos.NP, dtype=np.int32)
+            pos.idx, pos.inv = torch.from_numpy(idx).to(self.dev, non_blocking=True), torch.from_numpy(inv).to(self.dev, non_blocking=True)
+        return pos
 
     def mask_head_fwd_positives(self, Fm, fshape, rois, tmask, tcls):
         """Training forward of the mask head that spends conv2-4 / deconv / myolo_mask on the positive ROIs only.
@@ -1640,76 +1705,45 @@ class Net(object):
         (model.py:696,702,708: no batch statistics, no moving-average update), so nothing downstream of bn1 in a
         non-positive ROI reaches the loss, a gradient or any state.  ROIAlign, conv1 and bn1's batch statistics
         (model.py:690) still cover every ROI.  Returns (pred_p [NP*mh*mw, C] | None, tmask_p, tcls_p)."""
-        cfg = self.cfg
         B, R = rois.shape[:2]
         n, h, w, cf = fshape
-        ps = cfg.MASK_POOL_SIZE
-        q = ps * ps
-        if cfg.ROI_BOX_ORDER == "xyxy_as_yxyx":
-            boxes = rois.reshape(B * R, 4)
-        else:
-            boxes = rois.reshape(B * R, 4)[:, [1, 0, 3, 2]].contiguous()
-        bind = self._box_image_index(B, R)
-        NR = B * R
-        self.tape["roi"] = (boxes, bind, fshape, NR)
-        y1 = self._new(NR * q, MASK_FILTERS)
-        bn = "myolo_mask_bn1"
-        buf = self.bnbuf[bn]
-        x = None
+        ps = self.cfg.MASK_POOL_SIZE
+        rec = self._mask_rois(rois, fshape)
+        NR, q, bn = rec.NR, ps * ps, "myolo_mask_bn1"
         if self._wino_ok(NR, ps, ps, cf, MASK_FILTERS) and 256 % (MASK_FILTERS // 4) == 0:
             start, stop = self._timed("mask_conv3x3_fwd")
             start()
-            bn_args = (X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
-                       X.ptr(buf[3]), X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]))
-            c1_63 = (self.wino_tiles == "f63" and X.wino63_ok(ps, ps, cf, MASK_FILTERS) and X.wino63_ok(ps, ps, MASK_FILTERS, cf)
-                     and self.lazy_bn1_bwd and self.sparse_mask_bwd)
-            t = self._tiling(ps, ps, c1_63)          # the F(6,3)/F(4,3) tiling as in _mask_convs_winograd_chain, else F(4,3)/F(2,3)
-            V, U, M = t.planes(NR, cf), t.filters(cf, MASK_FILTERS), t.planes(NR, MASK_FILTERS)
-            t.input_transform_roialign(Fm, boxes, bind, V, n, h, w, cf, NR)        # ROIAlign fused into the input transform
-            t.multiply(V, self.p["myolo_mask_conv1/kernel"], U, M, NR, cf, MASK_FILTERS, tag="wino_multiply")
-            t.output_bn_stats(M, self.p["myolo_mask_conv1/bias"], y1, NR, MASK_FILTERS, bn_args)
-            self.tape["conv1_V_fmt"] = t.fmt
+            # the F(6,3)/F(4,3) tiling as in _mask_convs_winograd_chain, else F(4,3)/F(2,3)
+            y1 = self._mask_conv1_stats_fwd(rec, Fm, self._tiling(ps, ps, self._conv1_f63(ps, cf, True)), cf)
             stop()
-            self.tape["conv1_V"] = V
         else:
+            y1 = self._new(NR * q, MASK_FILTERS)
             x = self._new(NR * q, cf)
-            self._call_timed("roialign_fwd", "myolo_crop_and_resize_fwd", X.ptr(Fm), X.ptr(boxes), X.ptr(bind), X.ptr(x),
+            self._call_timed("roialign_fwd", "myolo_crop_and_resize_fwd", X.ptr(Fm), X.ptr(rec.boxes), X.ptr(rec.bind), X.ptr(x),
                              n, h, w, cf, NR, ps, ps, X.stream())
-            v = self.conv3x3_fwd(x, "myolo_mask_conv1", y1, NR, ps, ps, cf, MASK_FILTERS, keep_v=True, tag="mask_conv3x3_fwd")
-            if v is not None:
-                self.tape["conv1_V"] = v
-            X.call("myolo_bn_stats", X.ptr(y1), X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
-                   X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]), X.ptr(buf[3]),
-                   X.ptr(self.s[bn + "/moving_mean"]), X.ptr(self.s[bn + "/moving_variance"]),
-                   NR * q, MASK_FILTERS, *self._wsargs(), X.stream())
-        self.tape[bn] = (y1, ACT_RELU, True)
-        NP, idx_d, inv_d = self._positive_index(B, R)
-        self.tape["compact"] = (NP, idx_d, inv_d)
-        if NP == 0:
-            self.tape["mask"] = ([x], None, None)
+            rec.xin[1] = _Saved(x, ROWS_ALL)
+            rec.conv1_V = self.conv3x3_fwd(x, "myolo_mask_conv1", y1, NR, ps, ps, cf, MASK_FILTERS, keep_v=True, tag="mask_conv3x3_fwd")
+            X.call("myolo_bn_stats", X.ptr(y1), *self._bn_args(bn), NR * q, MASK_FILTERS, *self._wsargs(), X.stream())
+            self.tape[bn] = (y1, ACT_RELU, True)
+            rec.pre[1] = _Saved(y1, ROWS_ALL, bn)
+        pos = self._positive_index(rec, B, R, only=True)
+        NP = pos.NP
+        if NP == 0:                       # (model.py:750-752)
             return None, None, None
-        c1_p = self._gather(y1, idx_d, NP, q)
         a = self._new(NP * q, MASK_FILTERS)
-        X.call("myolo_bn_apply_act", X.ptr(c1_p), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(a), NP * q, MASK_FILTERS, ACT_RELU, X.stream())
-        convs = [x]
+        self._bn_relu(bn, self._gather(y1, pos.idx, NP, q), a)
         for i in range(2, 5):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
-            convs.append(a)
+            rec.xin[i] = _Saved(a, ROWS_POS)
             y = self._new(NP * q, MASK_FILTERS)
             self.conv3x3_fwd(a, cn, y, NP, ps, ps, MASK_FILTERS, MASK_FILTERS)
             a = self.bn_act_fwd(bn, y, ACT_RELU, False)          # keeps the pre-BN tensor for backward
-        d = self._new(NP * 4 * q, MASK_FILTERS)
-        X.call("myolo_deconv2x2s2_fwd", X.ptr(a), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(self.p["myolo_mask_deconv/bias"]),
-               X.ptr(d), NP, ps, ps, MASK_FILTERS, MASK_FILTERS, ACT_RELU, *self._wsargs(), X.stream())
-        C = cfg.NUM_CLASSES
-        pred = self._new(NP * 4 * q, C)
-        X.call("myolo_mask_head_out_fwd", X.ptr(d), X.ptr(self.p["myolo_mask/kernel"]), X.ptr(self.p["myolo_mask/bias"]), X.ptr(pred),
-               NP * 4 * q, MASK_FILTERS, C, X.stream())
-        self.tape["mask"] = (convs, a, d)
+            rec.pre[i] = _Saved(y, ROWS_POS, bn)
+        pred = self._mask_deconv_out_fwd(rec, a, NP, ROWS_POS)
         tmask_p = self._new(NP, 4 * q)
-        X.call("myolo_gather_groups", X.ptr(tmask), X.ptr(idx_d), X.ptr(tmask_p), NP, 4 * q, X.stream())
+        X.call("myolo_gather_groups", X.ptr(tmask), X.ptr(pos.idx), X.ptr(tmask_p), NP, 4 * q, X.stream())
         tcls_p = self._new(NP, dtype=torch.int32)
-        X.call("myolo_gather_groups", X.ptr(tcls), X.ptr(idx_d), X.ptr(tcls_p), NP, 1, X.stream())
+        X.call("myolo_gather_groups", X.ptr(tcls), X.ptr(pos.idx), X.ptr(tcls_p), NP, 1, X.stream())
         return pred, tmask_p, tcls_p
 
     def mask_head_bwd_sparse(self, dz, B, R, ids=None):
@@ -1719,134 +1753,101 @@ class Net(object):
         on the positive ROIs only (compacted); bn1 (batch statistics, model.py:690) and conv1 stay dense,
         because bn1's backward spreads gradient to every ROI.  Positives are the first n_pos rows of each
         image (detect_mask_target_graph puts them first, model.py:593)."""
-        cfg = self.cfg
-        convs, a4, d = self.tape["mask"]
-        boxes, bind, fshape, NR = self.tape["roi"]
-        ps = cfg.MASK_POOL_SIZE
-        C = cfg.NUM_CLASSES
-        n, h, w, cf = fshape
-        compact = "compact" in self.tape          # forward already ran on the positives only
-        NP, idx_d, inv_d = self.tape["compact"] if compact else self._positive_index(B, R)
-        if NP == 0:                       # no positive ROI: mask loss is the constant 0 (model.py:750-752)
+        rec = self.tape["mask"]
+        pos = self._positive_index(rec, B, R)
+        if pos.NP == 0:                   # no positive ROI: mask loss is the constant 0 (model.py:750-752)
+            n, h, w, cf = rec.fshape
             self.flat_g[self.bucket_ranges[BUCKET_MASK_CONV1][0]:self.bucket_ranges[BUCKET_MASK_REST][1]].zero_()
             dF = torch.zeros(n * h * w, cf, dtype=torch.float32, device=self.dev)
             if self.on_bucket_ready:
                 self.on_bucket_ready(BUCKET_MASK_REST)
                 self.on_bucket_ready(BUCKET_MASK_CONV1)
             return dF
-        q = ps * ps
-        kept = self.tape.get("compact_rows", ())          # tensors the forward wrote in compact order (rows of positive k at block k)
-
-        def gather(t, rows):
-            if compact:
-                return t
-            if id(t) in kept:
-                return t[:NP * rows]
-            return self._gather(t, idx_d, NP, rows)
-        dz_p = gather(dz, 4 * q)
-        # conv4's activation on the positives: re-formed from its kept pre-BatchNorm rows where those are compact (only the deconv's weight gradient reads it
-        # then, off the chain), else gathered
-        pre4 = self.tape["myolo_mask_bn4"][0]
-        a4_lazy = (not compact and torch.is_tensor(pre4) and id(pre4) in kept and isinstance(d, tuple) and NP <= d[2])
-        a4_p = None if a4_lazy else gather(a4, q)
-        if isinstance(d, tuple):          # ("kept", rows, cap): the fused forward wrote the positives' deconv output in compact order
-            d_p = d[1] if NP <= d[2] else None
-            d = None
-        else:
-            d_p = None
-        if d_p is not None:
-            pass
-        elif d is None:          # fused forward (deconv + 1x1 in one pass): rebuild the deconv output of the positives
-            d_p = self._new(NP * 4 * q, MASK_FILTERS)
-            X.call("myolo_deconv2x2s2_fwd", X.ptr(a4_p), X.ptr(self.p["myolo_mask_deconv/kernel"]),
-                   X.ptr(self.p["myolo_mask_deconv/bias"]), X.ptr(d_p), NP, ps, ps, MASK_FILTERS, MASK_FILTERS, ACT_RELU,
-                   *self._wsargs(), X.stream())
-        else:
-            d_p = gather(d, 4 * q)
-        Md = NP * 4 * q
-        dd = self._new(Md, MASK_FILTERS)
-        ids_p = ids
-        if C > MASK_DENSE_MAX_CLASSES and not compact:          # the positives' class ids beside their dz_sel rows
-            ids_p = self._new(NP, dtype=torch.int32)
-            X.call("myolo_gather_groups", X.ptr(ids), X.ptr(idx_d), X.ptr(ids_p), NP, 1, X.stream())
-        self._mask_out_bwd(d_p, dz_p, ids_p, dd, Md, C)
         # The compacted part is a chain of data gradients (deconv -> conv4 -> conv3 -> conv2 -> bn1's coefficients) that conv1's dense backward
         # waits for; the weight / bias gradients hanging off it have no consumer before the bucket's all-reduce.  They go to the stream (and
         # scratch) conv1's weight gradient uses later: queued in front of it, finished before the bucket is released there.
-        a4_w = self._new(NP * q, MASK_FILTERS) if a4_lazy else a4_p
-        with self._on(self._wgrad_side, a4_w, dd, *((pre4,) if a4_lazy else ())):
-            if a4_lazy:
-                b4 = self.bnbuf["myolo_mask_bn4"]
-                X.call("myolo_bn_apply_act", X.ptr(pre4), X.ptr(b4[2]), X.ptr(b4[3]), X.ptr(a4_w), NP * q, MASK_FILTERS, ACT_RELU, X.stream())
+        da, a4_p = self._mask_out_deconv_bwd_pos(rec, pos, dz, ids)
+        da = self._mask_convs_bwd_pos(rec, pos, da, a4_p)
+        # bucket 4 (conv2-4, bn2-4, deconv, myolo_mask) is complete: its data-path gradients on this stream, the weight gradients hanging off the
+        # compact chain on the side stream -- in FRONT of conv1's dense weight gradient, i.e. several milliseconds before the step ends
+        self._release(BUCKET_MASK_REST, self._wgrad_side)
+        return self._mask_conv1_bwd(rec, pos, da)         # ... and BUCKET_MASK_CONV1 behind conv1's weight gradient, on that kernel's stream
+
+    def _mask_out_deconv_bwd_pos(self, rec, pos, dz, ids):
+        """myolo_mask 1x1 + deconv backward on the positive ROIs.  Returns (da: the gradient of conv4's activation, a4_p: that activation of the
+        positives, or None where only the deconv's weight gradient needed it and formed it on its own stream)"""
+        ps, C, NP = self.cfg.MASK_POOL_SIZE, self.cfg.NUM_CLASSES, pos.NP
+        q = ps * ps
+        dz_p = _Saved(dz, ROWS_POS if pos.only else ROWS_ALL).rows(self, pos, 4 * q)
+        pre4 = rec.pre.get(4)
+        d = rec.deconv if rec.deconv is not None and NP <= (rec.deconv.cap or NP) else None      # (kept rows short of the positives are as good as none)
+        # conv4's activation on the positives: with the deconv rows kept and bn4's kept input compact too, only the deconv's weight gradient reads
+        # it -- re-formed there, off the chain; else gathered here (the deconv re-run below reads it)
+        a4_late = all(s is not None and s.order == ROWS_SLOTS for s in (pre4, d))
+        a4_p = None if a4_late else rec.a4.rows(self, pos, q)
+        # the deconv output of the positives: kept by the fused forward in slot order, written whole by the unfused one, else rebuilt
+        d_p = d.rows(self, pos, 4 * q) if d is not None else self._deconv_relu_fwd(a4_p, NP)
+        Md = NP * 4 * q
+        dd = self._new(Md, MASK_FILTERS)
+        ids_p = ids
+        if C > MASK_DENSE_MAX_CLASSES and not pos.only:         # the positives' class ids beside their dz_sel rows
+            ids_p = self._new(NP, dtype=torch.int32)
+            X.call("myolo_gather_groups", X.ptr(ids), X.ptr(pos.idx), X.ptr(ids_p), NP, 1, X.stream())
+        self._mask_out_bwd(d_p, dz_p, ids_p, dd, Md, C)
+        a4_w = self._new(NP * q, MASK_FILTERS) if a4_late else a4_p
+        with self._on(self._wgrad_side, a4_w, dd, *((pre4.t,) if a4_late else ())):
+            if a4_late:
+                self._bn_relu(pre4.bn, pre4.rows(self, pos, q), a4_w)
             X.call("myolo_deconv2x2s2_bwd_weight", X.ptr(a4_w), X.ptr(dd), X.ptr(self.g["myolo_mask_deconv/kernel"]), NP, ps, ps,
                    MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
             self.colsum(dd, self.g["myolo_mask_deconv/bias"])
         da = self._new(NP * q, MASK_FILTERS)
         X.call("myolo_deconv2x2s2_bwd_data", X.ptr(dd), X.ptr(self.p["myolo_mask_deconv/kernel"]), X.ptr(da), NP, ps, ps,
                MASK_FILTERS, MASK_FILTERS, *self._wsargs(), X.stream())
-        pre_rows = {}                         # id(pre-BN tensor) -> its positive rows: layer i's input tensor is layer i-1's BatchNorm input, gathered ONCE
+        return da, a4_p
+
+    def _mask_convs_bwd_pos(self, rec, pos, da, a_out):
+        """conv4 -> conv2 (+ bn4 -> bn2) backward on the positive ROIs: the data gradients on this stream, each conv's weight / bias gradient on the
+        weight-gradient stream.  da, a_out: the gradient of conv4's activation on the positives and that activation.  Returns bn1's output gradient."""
+        ps, NP = self.cfg.MASK_POOL_SIZE, pos.NP
+        q = ps * ps
         for i in range(4, 1, -1):
             cn, bn = "myolo_mask_conv%d" % i, "myolo_mask_bn%d" % i
-            src = convs[i - 1]
-            lazy_xin = False
-            if isinstance(src, tuple) and not compact and id(src[1]) in kept:
-                # the forward kept this conv's input rows compact, as pre-BatchNorm values: the BatchNorm backward below reads them as they are, and the
-                # normalised form -- only this conv's WEIGHT gradient needs it -- is formed where that runs
-                _, ypre, bsrc = src
-                yp = ypre[:NP * q]
-                xin = self._new(NP * q, MASK_FILTERS)
-                lazy_xin = True
-                pre_rows[id(ypre)] = yp
-            elif isinstance(src, tuple) and not compact and src[2] == "myolo_mask_bn1" and "conv2_in_rows" in self.tape:
-                xin = self.tape["conv2_in_rows"][:NP * q]          # bn1's activation of the positives, written compact by conv2's input transform
-            elif isinstance(src, tuple):      # ("lazy_bn", pre-BN tensor, bn layer): the forward normalised on load
-                _, ypre, bsrc = src
-                xin = self._new(NP * q, MASK_FILTERS)
-                if compact:
-                    yp = gather(ypre, q)
-                    X.call("myolo_bn_apply_act", X.ptr(yp), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), X.ptr(xin), NP * q,
-                           MASK_FILTERS, ACT_RELU, X.stream())
-                else:                         # one kernel: the gathered pre-BN rows (kept for bn_{i-1}'s backward below) and their normalised form
-                    yp = self._new(NP * q, MASK_FILTERS)
-                    X.call("myolo_gather_groups_affine_act", X.ptr(ypre), X.ptr(idx_d), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), ACT_RELU,
-                           X.ptr(yp), X.ptr(xin), NP, q, MASK_FILTERS, X.stream())
-                pre_rows[id(ypre)] = yp
-            else:
-                xin = gather(src, q)
-            if self.tape[bn][0] is None:
+            src, pre = rec.xin[i], rec.pre.get(i)
+            # this conv's input on the positives.  Kept compact as pre-BatchNorm rows: the BatchNorm backward of the next iteration reads them as
+            # they are, and the normalised form -- only this conv's WEIGHT gradient needs it -- is formed where that runs
+            late = src.bn is not None and src.order == ROWS_SLOTS
+            xin = self._new(NP * q, MASK_FILTERS) if late else src.act(self, pos, q)
+            if pre is None:
                 # the fused forward never wrote the pre-BN tensor.  bn2-4 are frozen affine maps followed by a ReLU, so their
                 # backward can be read off the POST-activation tensor, which the forward did keep for the positive ROIs (it is the
                 # next layer's input): mask = a > 0, xhat = (a - beta) / gamma there -- no convolution is re-run
-                a_post = a4_p if i == 4 else a_next
                 buf = self.bnbuf[bn]
                 dy = self._new(NP * q, MASK_FILTERS)
-                X.call("myolo_bn_act_bwd_frozen_post", X.ptr(da), X.ptr(a_post), X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
+                X.call("myolo_bn_act_bwd_frozen_post", X.ptr(da), X.ptr(a_out), X.ptr(self.p[bn + "/gamma"]), X.ptr(self.p[bn + "/beta"]),
                        X.ptr(buf[2]), X.ptr(dy), X.ptr(self.g[bn + "/gamma"]), X.ptr(self.g[bn + "/beta"]), NP * q, MASK_FILTERS,
                        self.tape[bn][1], *self._wsargs(), X.stream())
             else:
-                c_p = pre_rows.get(id(self.tape[bn][0]))
-                if c_p is None:
-                    c_p = gather(self.tape[bn][0], q)          # (a view when the forward kept these rows compact)
-                dy = self.bn_act_bwd(bn, da, y_override=c_p)
-            a_next = xin                  # conv_i's input = post-activation of layer i-1
-            with self._on(self._wgrad_side, xin, dy, *((src[1],) if lazy_xin else ())):
-                if lazy_xin:
-                    X.call("myolo_bn_apply_act", X.ptr(yp), X.ptr(self.bnbuf[bsrc][2]), X.ptr(self.bnbuf[bsrc][3]), X.ptr(xin), NP * q, MASK_FILTERS,
-                           ACT_RELU, X.stream())
+                dy = self.bn_act_bwd(bn, da, y_override=pre.rows(self, pos, q))
+            with self._on(self._wgrad_side, xin, dy, *((src.t,) if late else ())):
+                if late:
+                    self._bn_relu(src.bn, src.rows(self, pos, q), xin)
                 self.conv3x3_bwd_weight(xin, None, dy, cn, NP, ps, ps, MASK_FILTERS, MASK_FILTERS)
                 self.colsum(dy, self.g[cn + "/bias"])
             da = self._new(NP * q, MASK_FILTERS)
             self.conv3x3_bwd_data(dy, cn, da, NP, ps, ps, MASK_FILTERS, MASK_FILTERS)
-        # bucket 4 (conv2-4, bn2-4, deconv, myolo_mask) is complete: its data-path gradients on this stream, the weight gradients hanging off the
-        # compact chain on the side stream -- in FRONT of conv1's dense weight gradient, i.e. several milliseconds before the step ends
-        self._release(BUCKET_MASK_REST, self._wgrad_side)
-        # bn1: batch statistics -> dense dx from the row-sparse upstream gradient
+            a_out = xin                   # conv_i's input = the activation of layer i-1
+        return da
+
+    def _mask_conv1_bwd(self, rec, pos, da):
+        """bn1 (batch statistics: a dense dx from the row-sparse upstream gradient da), conv1 and ROIAlign backward over every ROI -> dF.
+        Releases BUCKET_MASK_CONV1."""
+        ps, NR, NP, cin = self.cfg.MASK_POOL_SIZE, rec.NR, pos.NP, rec.fshape[3]
+        q = ps * ps
         c1, act, _ = self.tape["myolo_mask_bn1"]
         buf = self.bnbuf["myolo_mask_bn1"]
         M1 = NR * q
-        x0 = convs[0]                           # None when ROIAlign was fused into conv1's input transform (V is kept instead)
-        cin = cf
-        v1 = self.tape.pop("conv1_V", None)
+        v1, rec.conv1_V = rec.conv1_V, None          # (the V planes go with this call, not with the tape)
         dp0 = self._new(M1, cin)
         lazy1 = self.lazy_bn1_bwd and v1 is not None and self._wino_ok(NR, ps, ps, MASK_FILTERS, cin)
         if lazy1:
@@ -1855,18 +1856,17 @@ class Net(object):
             # (Winograd transforms with a lazy operand) and it is never written.  Its column sums -- conv1's bias gradient --
             # cancel exactly through the batch statistics (sum dz - M*(sum dz)/M + 0), so that gradient is set to 0.
             kab = self._new(2, MASK_FILTERS)
-            X.call("myolo_bn_bwd_rowsparse_coeffs", X.ptr(da), X.ptr(c1), X.ptr(idx_d), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
+            X.call("myolo_bn_bwd_rowsparse_coeffs", X.ptr(da), X.ptr(c1), X.ptr(pos.idx), X.ptr(buf[0]), X.ptr(buf[1]), X.ptr(buf[2]),
                    X.ptr(buf[3]), X.ptr(self.g["myolo_mask_bn1/gamma"]), X.ptr(self.g["myolo_mask_bn1/beta"]), X.ptr(kab[0]),
                    X.ptr(kab[1]), M1, MASK_FILTERS, NP, q, act, *self._wsargs(), X.stream())
-            lazy = (X.ptr(c1), X.ptr(da), X.ptr(inv_d), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(kab[0]), X.ptr(kab[1]), act)
+            lazy = (X.ptr(c1), X.ptr(da), X.ptr(pos.inv), X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(kab[0]), X.ptr(kab[1]), act)
             self.g["myolo_mask_conv1/bias"].zero_()
-            v63 = self.tape.pop("conv1_V_fmt", "f43") == "f63"      # the layout the forward left conv1's V planes in
-            d63 = self.wino_tiles == "f63" and X.wino63_ok(ps, ps, MASK_FILTERS, cin)
-            # (the forward takes the F(6,3) layout for conv1 only where the data gradient has its F(6,3) kernels too: v63 implies d63)
-            merged = v63 and d63
+            # V planes in the F(6,3) layout (the forward takes it only where the data gradient has its F(6,3) kernels too, _conv1_f63): ONE pass
+            # over conv1's output forms the lazily built gradient tile and sends it out both ways, V (data gradient) and Q (weight gradient); the
+            # two gradients then finish on their own streams
+            merged = rec.conv1_V_tiling == "f63"
+            d63 = self._wino63(ps, ps, MASK_FILTERS, cin)
             if merged:
-                # ONE pass over conv1's output forms the lazily built gradient tile and sends it out both ways: V (data gradient) and Q
-                # (weight gradient); the two gradients then finish on their own streams
                 pe = X.wino63_plane_elems(NR, MASK_FILTERS)
                 Vd, Qd = self._new(pe), self._new(pe)
                 X.call("myolo_wino63_lazybn_transforms", *lazy, X.ptr(Vd), X.ptr(Qd), NR, MASK_FILTERS, X.stream())
@@ -1874,12 +1874,10 @@ class Net(object):
             # are complete here, so the bucket is released there, behind that kernel
             self._wgrad_side.ws.ensure(X.wino63_bwd_weight_from_q_ws_bytes(NR, cin, MASK_FILTERS) if merged else
                                        X.wino_ws_bytes(NR, ps, ps, cin, MASK_FILTERS, 2))
-            with self._on(self._wgrad_side, v1, c1, da, inv_d, kab, *((Qd,) if merged else ())):
+            with self._on(self._wgrad_side, v1, c1, da, pos.inv, kab, *((Qd,) if merged else ())):
                 if merged:
                     X.call("myolo_wino63_bwd_weight_from_q", X.ptr(v1), X.ptr(Qd), X.ptr(self.g["myolo_mask_conv1/kernel"]), NR, cin, MASK_FILTERS,
                            *self._wsargs(), X.stream())
-                elif v63:
-                    raise AssertionError("conv1's V planes in the F(6,3) layout without the F(6,3) data-gradient kernels")
                 else:
                     X.call("myolo_conv3x3_wino_bwd_weight_lazybn", X.ptr(v1), *lazy, X.ptr(self.g["myolo_mask_conv1/kernel"]), NR, ps, ps,
                            cin, MASK_FILTERS, *self._wsargs(), X.stream())
@@ -1898,15 +1896,15 @@ class Net(object):
                 X.call("myolo_conv3x3_wino_bwd_data_lazybn", *lazy, X.ptr(self.p["myolo_mask_conv1/kernel"]), X.ptr(dp0), NR, ps, ps, cin,
                        MASK_FILTERS, *self._wsargs(), X.stream())
         else:
+            x0 = rec.xin[1].t if rec.xin.get(1) is not None else None          # None when ROIAlign was fused into conv1's input transform (V is kept instead)
             dc1 = self._new(M1, MASK_FILTERS)
-            X.call("myolo_bn_act_bwd_rowsparse", X.ptr(da), X.ptr(c1), X.ptr(idx_d), X.ptr(inv_d), X.ptr(buf[0]), X.ptr(buf[1]),
+            X.call("myolo_bn_act_bwd_rowsparse", X.ptr(da), X.ptr(c1), X.ptr(pos.idx), X.ptr(pos.inv), X.ptr(buf[0]), X.ptr(buf[1]),
                    X.ptr(buf[2]), X.ptr(buf[3]), X.ptr(dc1), X.ptr(self.g["myolo_mask_bn1/gamma"]), X.ptr(self.g["myolo_mask_bn1/beta"]),
                    M1, MASK_FILTERS, NP, q, act, *self._wsargs(), X.stream())
             self.conv3x3_bwd_weight(x0, v1, dc1, "myolo_mask_conv1", NR, ps, ps, cin, MASK_FILTERS)
             self.colsum(dc1, self.g["myolo_mask_conv1/bias"])
             self.conv3x3_bwd_data(dc1, "myolo_mask_conv1", dp0, NR, ps, ps, cin, MASK_FILTERS)
-        dF = self._new(n * h * w, cf)
-        X.call("myolo_roialign_bwd_grouped", X.ptr(dp0), X.ptr(boxes), X.ptr(dF), n, h, w, cf, NR // n, ps, ps, X.stream())
+        dF = self._roialign_bwd(rec, dp0)
         if self.on_bucket_ready and not lazy1:
             self.join_conv1_wgrad()       # the compacted weight gradients on the side stream
             self.on_bucket_ready(BUCKET_MASK_CONV1)       # (with lazy1 the bucket was released on the weight gradient's stream, behind that kernel)
@@ -2172,7 +2170,7 @@ class Net(object):
                 idx_d = self._new(B * R, dtype=torch.int32)
                 inv_d = self._new(B * R, dtype=torch.int32)
                 X.call("myolo_positive_index", X.ptr(npos), B, R, X.ptr(flags), X.ptr(idx_d), X.ptr(inv_d), None, X.stream())
-                self.tape["pos_index"] = (idx_d, inv_d)
+                self.tape["mask"] = _MaskTape(_Positives(None, idx_d, inv_d))
                 if self.keep_deconv_rows:
                     # capacity of the kept-rows buffer (803 KB per ROI): keep_deconv_rows per image at most, and no more than the high-water mark of
                     # what the steps whose counts the host has read really needed -- twice the positives + 64, rounded up to a power of two, never

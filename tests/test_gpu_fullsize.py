@@ -374,7 +374,7 @@ def test_config2_gradients_with_oracle_activation_masks_hold_maxnorm():
                     for k, v in enumerate((mean, var, sc, b64 - mean * sc)):
                         buf[k].copy_(torch.from_numpy(v.astype(np.float32)))
                 forced.append(name)
-        d = n.tape["mask"][2]
+        d = n.tape["mask"].deconv.t
         d.copy_(torch.from_numpy(cap["deconv/out"].reshape(d.shape)))
     net.tape_hook = hook
     # ... and the same ROIs: the oracle's decoded proposals replace the GPU's (they agree to ~1e-6, but an ROIAlign sample row within

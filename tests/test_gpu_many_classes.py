@@ -396,7 +396,7 @@ def test_four_class_step_still_uses_the_dense_mask_kernels():
     cap = {}
 
     def hook(n):
-        cap["d"] = n.tape["mask"][2].detach().clone()
+        cap["d"] = n.tape["mask"].deconv.t.detach().clone()
     net.tape_hook = hook
     out = model.train_on_batch(batch, learning_rate=0.0)
     grads = net.grads_dict()

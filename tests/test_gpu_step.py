@@ -324,9 +324,11 @@ def _capture_mask_tape(store):
     import torch
 
     def hook(net):
-        convs, a4, d = net.tape["mask"]
-        store.append(([t.detach().clone() if torch.is_tensor(t) else None for t in convs], a4.detach().clone(),
-                      d.detach().clone() if torch.is_tensor(d) else None))       # ("kept", rows, cap): the positives' rows, bit-identical to the rebuild (test_gpu_ops)
+        rec = net.tape["mask"]
+        convs = [rec.xin.get(i) for i in range(1, 5)]           # (an input the forward kept as pre-BatchNorm rows, or not at all: None)
+        d = rec.deconv
+        store.append(([s.t.detach().clone() if s is not None and s.bn is None else None for s in convs], rec.a4.t.detach().clone(),
+                      d.t.detach().clone() if d is not None and d.cap is None else None))       # kept rows with a capacity: the positives' rows, bit-identical to the rebuild (test_gpu_ops)
     return hook
 
 
@@ -1063,7 +1065,7 @@ def test_gradients_with_oracle_activation_masks_hold_maxnorm():
                         flips.append((((z_o > 0) & (z_o < hi)) != ((z_g > 0) & (z_g < hi))).reshape(yo.shape[0], -1).any(1))      # rows with a differing decision
                     y.copy_(torch.from_numpy(yo))
                     forced.append(name)
-            d = n.tape["mask"][2]
+            d = n.tape["mask"].deconv.t
             d.copy_(torch.from_numpy(np.ascontiguousarray(T.c["deconv/out"], np.float32).reshape(d.shape)))
         net.tape_hook = hook
         out = model.train_on_batch(batch, learning_rate=0.0)
@@ -1428,36 +1430,88 @@ def test_step_result_is_lazy_and_train_equals_a_hand_loop():
     assert out.device("myolo_mask").is_cuda and dict(out)["loss"] == out["loss"]
 
 
-@pytest.mark.parametrize("tiles,rois", [("f63", "all"), ("f63", "positives"), ("f43", "all"), ("f43", "positives")])
-def test_mask_head_launch_sequence(tiles, rois, monkeypatch):
-    """The ordered list of (C-ABI entry point, integer arguments) the mask head issues over two training steps and one inference forward is
-    exactly tests/mask_head_launches.LAUNCHES -- recorded at the commit before the chain was written against the tiling adapters, the folded
-    F(6,3) entries renamed.  CONV3X3_ALGO='winograd' takes the Winograd chain at this ROI count, ROIAlign fused into conv1's input transform."""
+def _launch_variants():
     import mask_head_launches as L
-    _, P, batch, _ = make_case(ShapesConfig, 128, 0.5, 4)
-    model = MaskYOLO(mode="training", config=L.config(tiles, rois))
+    return [pytest.param(k, id=k.replace("/", "-")) for k in L.CASES]
+
+
+@pytest.mark.parametrize("variant", _launch_variants())
+def test_mask_head_launch_sequence(variant, monkeypatch):
+    """The ordered list of (C-ABI entry point, integer arguments) the mask head issues over two training steps and one inference forward is
+    exactly tests/mask_head_launches.LAUNCHES -- the four CONV3X3_ALGO='winograd' variants recorded at the commit before the chain was written
+    against the tiling adapters, the folded F(6,3) entries renamed; the variants of the backward's other branches, the stream of every launch
+    (STREAMS) and the Net._on blocks with the number of tensors each hands to its side stream (ON_BLOCKS) at the commit before the backward
+    was split along the mask head's tape record.  A weight gradient moved off its stream, or a tensor dropped from a record_stream list,
+    computes the same numbers and races only under load: these two records see it."""
+    import mask_head_launches as L
+    if variant.endswith("/81"):
+        from test_gpu_many_classes import many_class_case
+        _, P, batch, _ = many_class_case()
+    else:
+        _, P, batch, _ = make_case(ShapesConfig, 128, 0.5, 4)
+    cfg = L.config(variant)
+    model = MaskYOLO(mode="training", config=cfg)
     model.load_state_dict(P)
-    seen = L.run(model, batch, monkeypatch)
-    want = L.LAUNCHES[L.key(tiles, rois)]
+    L.prepare(model.net, variant, lambda k: _force_first_proposals_onto_gt(model.net, cfg, k))
+    rec = L.run(model, batch, monkeypatch)
+    seen, want = rec.launches, L.LAUNCHES[variant]
     assert len(seen) == len(want), (len(seen), len(want))
     for k, (a, b) in enumerate(zip(seen, want)):
         assert a == b, (k, a, b, seen[max(0, k - 3):k])
-    assert any(n.endswith("_input_transform_roialign") for n, _ in seen)
+    streams = "".join(rec.streams)
+    assert len(streams) == len(seen)
+    for k, (a, b) in enumerate(zip(streams, L.STREAMS[variant])):
+        assert a == b, (k, seen[k], a, b)
+    assert rec.on_blocks == L.ON_BLOCKS[variant], (rec.on_blocks, L.ON_BLOCKS[variant])
+    if not variant.startswith("direct"):
+        assert any(n.endswith("_input_transform_roialign") for n, _ in seen)
 
 
 def test_mask_head_launch_table_is_not_hollow():
     """every form the chain picks occurs in some variant of the table: both F(6,3) entry points, pre-BatchNorm rows (keep_pre) kept by slots
     (capacity > 0: whenever the step keeps deconv rows, Net.keep_deconv_rows, the F(6,3) tiling is handed slots) and by flags (the F(4,3) tiling
-    has no other form), boundaries that keep nothing (inference), input transforms with and without compact kept rows, ROIAlign fused into both"""
+    has no other form), boundaries that keep nothing (inference), input transforms with and without compact kept rows, ROIAlign fused into both;
+    and every variant beyond the first four reaches the branch of the backward it is in the table for"""
     import mask_head_launches as L
     from myolo import _ext as X
-    assert set(L.LAUNCHES) == {L.key(t, r) for t, r in L.VARIANTS}
+    assert set(L.LAUNCHES) == set(L.CASES) == set(L.STREAMS) == set(L.ON_BLOCKS) and {L.key(t, r) for t, r in L.VARIANTS} <= set(L.CASES)
+    assert all(len(L.STREAMS[k]) == len(L.LAUNCHES[k]) and set(L.STREAMS[k]) <= set("cwyo") for k in L.CASES)
     rows = [r for v in L.LAUNCHES.values() for r in v]
     assert all(n in X.SIGS and len(a) == sum(t in (X.I, X.L) for t in X.SIGS[n]) for n, a in rows)
-    bnd = [a for n, a in rows if n == "myolo_wino63_boundary"]                  # (act, keep_pre, keep_cap, N, C)
-    itr = [a for n, a in rows if n == "myolo_wino63_input_transform"]           # (act, keep_cap, N, C)
+    first = [r for t, r_ in L.VARIANTS for r in L.LAUNCHES[L.key(t, r_)]]
+    bnd = [a for n, a in first if n == "myolo_wino63_boundary"]                  # (act, keep_pre, keep_cap, N, C)
+    itr = [a for n, a in first if n == "myolo_wino63_input_transform"]           # (act, keep_cap, N, C)
     assert any(a[1] == 1 and a[2] > 0 for a in bnd) and any(a[1] == 0 and a[2] == 0 for a in bnd)
     assert any(a[1] > 0 for a in itr) and any(a[1] == 0 for a in itr)
-    names = {n for n, _ in rows}
+    names = {n for n, _ in first}
     assert {"myolo_wino_output_input_transform_keep_pre", "myolo_wino_output_input_transform", "myolo_wino63_input_transform_roialign",
             "myolo_wino_input_transform_roialign"} <= names
+
+    def args(variant, entry):
+        return [a for n, a in L.LAUNCHES[variant] if n == entry]
+    NR, q = 4 * 48, 196
+    # the shipped default: the Winograd chain over every ROI, the compacted convs of the backward on the direct kernels, the lazy F(6,3) bn1 + conv1
+    assert args("auto/f63/all", "myolo_wino63_boundary") and args("auto/f63/all", "myolo_conv3x3_bwd_weight")
+    assert args("auto/f63/all", "myolo_wino63_lazybn_transforms")
+    # layer-wise direct forward: bn2-4 backward off the post-activation, bn1's input gradient materialised
+    assert args("direct/all", "myolo_bn_act_bwd_frozen_post") and args("direct/all", "myolo_bn_act_bwd_rowsparse")
+    assert not args("direct/all", "myolo_bn_bwd_rowsparse_coeffs") and args("direct/all", "myolo_conv3x3_affine_act_fwd")
+    for v in ("f63/all/dense", "f43/all/dense"):          # Net.mask_head_bwd: every ROI through the deconv's and bn1-4's backward, nothing on a side stream
+        assert any(a[0] == NR for a in args(v, "myolo_deconv2x2s2_bwd_weight")) and any(a[0] == NR * q for a in args(v, "myolo_bn_act_bwd"))
+        assert set(L.STREAMS[v]) == {"c"} and not L.ON_BLOCKS[v]
+    for v in ("f63/all/nolazy", "f43/all/nolazy"):        # bn1's input gradient materialised; conv1's forward on the F(4,3) tiling
+        assert args(v, "myolo_bn_act_bwd_rowsparse") and not args(v, "myolo_bn_bwd_rowsparse_coeffs")
+        assert len(args(v, "myolo_wino_input_transform_roialign")) >= 2 and len(args(v, "myolo_wino63_input_transform_roialign")) <= 1      # (the inference forward's)
+    # no kept deconv rows: the deconv re-run on the positives, conv4's activation gathered for it
+    NP = args("f63/all/nokeep", "myolo_deconv2x2s2_fwd")[0][0]
+    assert 0 < NP < NR and (NP, q * 256) in args("f63/all/nokeep", "myolo_gather_groups")
+    assert not args("f63/all/nokeep", "myolo_deconv2x2s2_mask_fwd_keep")
+    # kept rows short of the positives: written by the forward (capacity <= 4), refused by the backward, the deconv re-run for >= 12 positives
+    assert all(a[-1] <= 4 for a in args("f63/all/overflow", "myolo_deconv2x2s2_mask_fwd_keep"))
+    assert [a[0] >= 12 for a in args("f63/all/overflow", "myolo_deconv2x2s2_fwd")] == [True, True]
+    # 81 classes: the selected-channel 1x1 backward (the positives' class ids gathered beside their rows), the unfused deconv with d whole
+    for v in ("f63/all/81", "f63/positives/81"):
+        assert args(v, "myolo_mask_head_out_bwd_sel") and not args(v, "myolo_mask_head_out_bwd")
+    assert any(a[0] == NR for a in args("f63/all/81", "myolo_deconv2x2s2_fwd"))
+    NP = args("f63/all/81", "myolo_mask_head_out_bwd_sel")[0][0] // (4 * q)
+    assert (NP, 1) in args("f63/all/81", "myolo_gather_groups") and (NP, 4 * q * 256) in args("f63/all/81", "myolo_gather_groups")
