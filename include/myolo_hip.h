@@ -61,7 +61,8 @@ size_t      myolo_workspace_bytes(int64_t rows, int cin, int cout);
  *                     convs with few rows and K >= 256: the split-K pair of launches instead of the one-launch small-M kernel; another fp32
  *                     summation order), "deconv_mask_legacy" (myolo_deconv2x2s2_mask_fwd[_keep] under "wino_x6": 1 = the untransposed tile with
  *                     the per-class butterfly epilogue of rounds 3-5, 2 = the transposed tile with partial logits + the finish launch -- same
- *                     bits as 0), "tn_wgs" (wino_tn_x6_kernel: workgroups per launch, default 224, 0 = one launch);
+ *                     bits as 0), "tn_wgs" (wino_tn_x6_kernel: workgroups per launch, default 224, 0 = one launch), "tn_x6_legacy"
+ *                     (wino_tn_x6_kernel without the wave-uniform loader index: every operand load in a waterfall loop; same bits);
  *   Winograd:         "wino_no_bt" (gemm_nn_fast on [K][N] filters), "wino_no_mixed" (F(4,3) for every tile), "w63_legacy" (the one-unit
  *                     F(6,3) transform kernels of rounds 3-5 instead of the persistent ones; same bits);
  *   trunk:            "no_trunk_fusion" (the conv, then a separate BatchNorm statistics pass);

@@ -190,6 +190,17 @@ size_t myolo_wino63_bwd_weight_from_q_ws_bytes(int N, int Cin, int Cout);
 int myolo_wino63_bwd_weight_from_q(const float* v_saved, const float* Q, float* dw, int N, int Cin, int Cout, void* ws, size_t ws_bytes,
                                    void* stream);
 
+/* The plane-wise weight-gradient product behind myolo_wino63_bwd_weight_from_q and the F(4,3) chain under "wino_x6", by itself: for up to 4 runs of
+ * planes (run r: nq[r] planes of rows[r] rows each, packed one after another in run order in A [rows][Ka] and B [rows][N]), C[plane] (Ka x N) =
+ * A[plane]^T B[plane] with six exact bf16 piece products per fp32 product.  rows / nq are HOST arrays; runs with 0 rows or 0 planes are skipped.
+ * Ka, N multiples of 256.  MYOLO_EWORKSPACE when ws is smaller than the split plan's partial tiles. */
+int myolo_gemm_tn_bf16x6_planes(const float* A, const float* B, float* C, int nruns, const int64_t* rows, const int32_t* nq, int Ka, int N,
+                                void* ws, size_t ws_bytes, void* stream);
+/* myolo_deconv2x2s2_bwd_weight on the same product whatever the number of pixels (the public entry takes it from 4096 input pixels under "wino_x6"):
+ * the four taps of dy gathered into the A operand.  Cin and 4 Cout multiples of 256. */
+int myolo_deconv2x2s2_bwd_weight_bf16x6(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                                        void* stream);
+
 /* myolo_conv3x3_wino_bwd_data_lazybn on this tiling (same operands; needs myolo_wino63_ok(14, 14, Cout, Cin)) */
 size_t myolo_wino63_bwd_data_ws_bytes(int N, int Cin, int Cout);
 int myolo_wino63_bwd_data_lazybn(const float* y_pre, const float* dy_compact, const int32_t* inv, const float* scale, const float* shift,

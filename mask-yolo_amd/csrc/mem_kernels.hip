@@ -44,7 +44,7 @@ static int* option_slot(const char* name)
         {"wino_no_mixed", &MyoloOptions::wino_no_mixed}, {"x6_no_half_tiles", &MyoloOptions::x6_no_half_tiles},
         {"w63_legacy", &MyoloOptions::w63_legacy}, {"pw_x6_min_rows", &MyoloOptions::pw_x6_min_rows}, {"deconv_no_x6", &MyoloOptions::deconv_no_x6},
         {"pw_no_smallm", &MyoloOptions::pw_no_smallm}, {"pw_no_x6", &MyoloOptions::pw_no_x6}, {"tn_no_x6", &MyoloOptions::tn_no_x6},
-        {"tn_wgs", &MyoloOptions::tn_wgs}, {"no_trunk_fusion", &MyoloOptions::no_trunk_fusion},
+        {"tn_wgs", &MyoloOptions::tn_wgs}, {"tn_x6_legacy", &MyoloOptions::tn_x6_legacy}, {"no_trunk_fusion", &MyoloOptions::no_trunk_fusion},
         {"bn_fused_tf_variance", &MyoloOptions::bn_fused_tf_variance},
     };
     if (!name) return nullptr;

@@ -33,6 +33,7 @@ struct MyoloOptions {
     int pw_no_x6;         // pointwise convs with >= 256 channels: the fp32-MFMA kernels even when "wino_x6" is on (ablation)
     int tn_no_x6;         // winograd weight gradient: gemm_tn_fast (fp32 MFMA) even when "wino_x6" is on (ablation of wino_tn_x6_kernel)
     int tn_wgs;           // wino_tn_x6_kernel: its work units go out in launches of at most this many workgroups (default 224; 0 = one launch).  112 KB of LDS = one workgroup per CU, so 224 leave four CUs of every XCD to the chains of small kernels that run beside a weight gradient (profiles/r4_notes.md section 8)
+    int tn_x6_legacy;     // bf16x6 weight gradient: 1 = wino_tn_x6_kernel with its loader operand index in a vector register (every buffer load in a waterfall loop), as before the scalar index; same bits (test reference)
     int no_trunk_fusion;  // *_bnstats_fwd: the conv, then a separate statistics pass (ablation of the producer-fused BatchNorm statistics)
     // NOT a tuning switch -- which Keras/TF pair the BatchNorm moving-variance update restates (default 1):
     // 1 = Keras 2.2.x on TF-1.x through tf.nn.fused_batch_norm (Bessel-corrected batch variance, then Keras' n/(n-(1+eps)));

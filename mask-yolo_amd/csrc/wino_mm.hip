@@ -1158,7 +1158,8 @@ int myolo_matmul_f32_impl(const float* A, const float* B, float* C, int64_t M, i
 // of one operand and fetches its 16 rows of the chunk with 16 dword loads (every wave-level load is a contiguous 256-byte row segment),
 // splits them EXACTLY into three bf16 pieces (truncation: and / sub / perm) and writes them k-contiguous into the LDS row record of
 // its column -- the transposition happens in the register -> LDS step, no strided access anywhere.  256 x 256 tile per workgroup (each
-// plane element is read from HBM once: the kernel is bound by its 3.9 GB of operand traffic, not by the matrix pipe), 8 waves of
+// plane element is read from HBM once; what bounds the kernel is what its SIMDs issue around the MFMAs, neither the 3.9 GB of operand traffic nor
+// LDS bytes nor the barrier: profiles/tn_x6_rework_notes.md), 8 waves of
 // 128 x 64 (4 x 2 MFMA tiles x 6 piece products), M split over workgroups, fp32 partial tiles summed in a fixed order by
 // tn_x6_reduce_kernel (bit-reproducible).  One barrier per 16-deep chunk; chunk c+1 is split into the other LDS buffer behind the MFMAs
 // of chunk c, chunk c+2 is in flight from HBM meanwhile.
@@ -1190,7 +1191,13 @@ struct TNArgs {
     TNRun run[4];
 };
 
-template <bool AG = false>
+// UNI: the loader's operand index op = tid >> 8 is the same for all lanes of a wave, but the compiler cannot know: with op in a vector register the
+// row pitch and so the scalar-offset operand of every buffer load count as divergent, and each of the 16 loads of a chunk sits in a "waterfall" loop
+// (readfirstlane, compare, exec mask, load, branch: ~10 instructions and a branch that always run once).  UNI reads op through readfirstlane: the
+// offsets are scalar, the 16 loads are 16 instructions, and the `AG && op == 0` / on-load-affine branches are uniform.  Same loads, same arithmetic,
+// same bits; 1.58 -> 1.38 ms for conv1's weight gradient (profiles/tn_x6_rework_notes.md).  UNI = false is the kernel as it was (option
+// "tn_x6_legacy", the reference of tests/test_gpu_tn_x6_rework.py).
+template <bool AG = false, bool UNI = true>
 __global__ __launch_bounds__(512, 1) void wino_tn_x6_kernel(TNArgs p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char Ls[2][2][TN_T * X6_REC];      // [buffer][A | B][column record]: 112 KB
@@ -1221,7 +1228,7 @@ __global__ __launch_bounds__(512, 1) void wino_tn_x6_kernel(TNArgs p)
     const int nk = (int)((nrows + MM_BK - 1) / MM_BK);
 
     // loader role: thread = (operand tid >> 8, column tid & 255); 16 rows of the chunk
-    const int op = tid >> 8, col = tid & 255;
+    const int op = UNI ? __builtin_amdgcn_readfirstlane(tid >> 8) : tid >> 8, col = tid & 255;
     const int ld = op ? p.N : p.Ka;
     const float* base = op ? p.B + R.b_off + ((long long)z * R.rows + r0) * p.N + nt * TN_T
                            : p.A + R.a_off + ((long long)z * R.rows + r0) * p.Ka + kat * TN_T;
@@ -1444,6 +1451,18 @@ static long long tn_x6_plan(int nruns, const long long* rows, const int* nq, int
 
 static long long tn_x6_grid(long long nunits) { return g_myolo_opt.tn_wgs > 0 && nunits > g_myolo_opt.tn_wgs ? g_myolo_opt.tn_wgs : nunits; }
 
+// the units of a plan in launches of at most "tn_wgs" workgroups; option "tn_x6_legacy": the kernel without the uniform loader index (same bits)
+template <bool AG>
+static void tn_x6_launch(TNArgs& a, hipStream_t s)
+{
+    for (long long base = 0, g = tn_x6_grid(a.nunits); base < a.nunits; base += g) {
+        a.unit_base = base;
+        const unsigned n = (unsigned)(a.nunits - base < g ? a.nunits - base : g);
+        if (g_myolo_opt.tn_x6_legacy) hipLaunchKernelGGL((wino_tn_x6_kernel<AG, false>), dim3(n), dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((wino_tn_x6_kernel<AG, true>), dim3(n), dim3(512), 0, s, a);
+    }
+}
+
 size_t myolo_gemm_tn_x6_ws_bytes(int nruns, const long long* rows, const int* nq, int Ka, int N)
 {
     return align256((size_t)tn_x6_plan(nruns, rows, nq, Ka, N, nullptr) * Ka * N * sizeof(float));
@@ -1480,15 +1499,28 @@ int myolo_gemm_tn_x6_runs(const float* A, const float* B, float* C, int nruns, c
 #ifdef MM_X6_TUNE
     a.tune = g_myolo_opt.tune0;
 #endif
-    for (long long base = 0, g = tn_x6_grid(a.nunits); base < a.nunits; base += g) {
-        a.unit_base = base;
-        hipLaunchKernelGGL(wino_tn_x6_kernel<false>, dim3((unsigned)(a.nunits - base < g ? a.nunits - base : g)), dim3(512), 0, s, a);
-    }
+    tn_x6_launch<false>(a, s);
     const long long n4 = (long long)Ka * N / 4;
     hipLaunchKernelGGL(tn_x6_reduce_kernel, dim3((unsigned)((n4 + 255) / 256), planes), dim3(256), 0, s, a);
     return MYOLO_OK;
 }
 
+extern "C" int myolo_gemm_tn_bf16x6_planes(const float* A, const float* B, float* C, int nruns, const int64_t* rows, const int32_t* nq, int Ka, int N,
+                                           void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(A && B && C && rows && nq && nruns >= 0 && nruns <= 4 && Ka > 0 && N > 0, "gemm_tn_bf16x6_planes: bad arguments");
+    long long r[4], ao[4], bo[4], at = 0;
+    int q[4];
+    for (int k = 0; k < nruns; ++k) {
+        MYOLO_REQUIRE(rows[k] >= 0 && nq[k] >= 0, "gemm_tn_bf16x6_planes: negative run");
+        r[k] = rows[k]; q[k] = nq[k]; ao[k] = at * Ka; bo[k] = at * N;
+        at += rows[k] * nq[k];
+    }
+    const int rc = myolo_gemm_tn_x6_runs(A, B, C, nruns, r, ao, bo, q, Ka, N, ws, ws_bytes, (hipStream_t)stream);
+    if (rc) return rc;
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
 
 /* pointwise conv of the trunk on the bf16 matrix pipe with six exact piece products (FP32_MATMUL = "bf16x6", layers with Cout % 256 == 0):
  * y [M][N] = act_in(x * in_scale + in_shift) [M][K] * w [K][N], optional per-row-tile partial sums of y's columns (stat).
@@ -1581,11 +1613,19 @@ int myolo_deconv_x6_bwd_weight(const float* x, const float* dy, float* dw, long 
     }
     a.run[0].a_off = 0; a.run[0].b_off = 0;
     a.nunits = pairs * a.tiles_k * a.tiles_n;
-    for (long long base = 0, g = tn_x6_grid(a.nunits); base < a.nunits; base += g) {
-        a.unit_base = base;
-        hipLaunchKernelGGL(wino_tn_x6_kernel<true>, dim3((unsigned)(a.nunits - base < g ? a.nunits - base : g)), dim3(512), 0, s, a);
-    }
+    tn_x6_launch<true>(a, s);
     const long long n4 = (long long)Ka * N / 4;
     hipLaunchKernelGGL(tn_x6_reduce_kernel, dim3((unsigned)((n4 + 255) / 256), 1), dim3(256), 0, s, a);
+    return MYOLO_OK;
+}
+
+extern "C" int myolo_deconv2x2s2_bwd_weight_bf16x6(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                                                   void* stream)
+{
+    MYOLO_REQUIRE(x && dy && dw && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (Cin % TN_T) == 0 && ((4 * Cout) % TN_T) == 0 &&
+                  (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw) & 15) == 0, "deconv2x2s2_bwd_weight_bf16x6: needs Cin %% 256 == 0, 4 Cout %% 256 == 0, 16-byte aligned operands");
+    const int rc = myolo_deconv_x6_bwd_weight(x, dy, dw, (long long)N * H * W, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
+    if (rc) return rc;
+    MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -116,6 +116,8 @@ SIGS = {
     "myolo_dwconv3x3_bwd_weight_affine_in": [P, P, P, I, P, P, I, I, I, I, I, P, Z, P],
     "myolo_pwconv1x1_bnstats_fwd": [P, P, P, I, P, P, P, P, P, P, P, P, P, P, L, I, I, I, P, Z, P],
     "myolo_pwconv1x1_bwd_weight_affine_in": [P, P, P, I, P, P, L, I, I, P, Z, P],
+    "myolo_gemm_tn_bf16x6_planes": [P, P, P, I, P, P, I, I, P, Z, P],
+    "myolo_deconv2x2s2_bwd_weight_bf16x6": [P, P, P, I, I, I, I, I, P, Z, P],
     "myolo_gather_groups_affine_act": [P, P, P, P, I, P, P, I, L, I, P],
     "myolo_add_inplace": [P, P, L, P],
     "myolo_conv7x7s2_c3_fwd": [P, P, P, P, I, I, I, I, P, Z, P],
