@@ -306,6 +306,24 @@ int myolo_mask_overlap_counts(const float* masks, const float* det, const int32_
                               int32_t* inter, int32_t* area_pred, int32_t* area_gt, int32_t* win, int B, int R, int K, int T, int mh, int mw,
                               int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- on-device training augmentation (myolo/augment.py, csrc/augment_kernels.hip; arithmetic contract: DESIGN.md "On-device augmentation").
+ * Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).  Per image b one row of params: the INVERSE affine map
+ * (output pixel -> source position, pixel-centre convention baked into m02 / m12), then gain and bias of the byte values.  The image is sampled
+ * bilinearly (a tap outside the frame reads cval), the instance masks by nearest neighbour; a live source instance (class id != 0) whose warped
+ * mask is empty is dropped and the survivors are compacted in order; gt_boxes = extract_bboxes of the warped masks; y_true / true_boxes =
+ * BatchGenerator._encode of those boxes (both NULL: not written).  Every output element is written.  T <= 32.
+ * ws: myolo_augment_batch_ws_bytes(B, T). */
+size_t myolo_augment_batch_ws_bytes(int B, int T);
+int myolo_augment_batch(const uint8_t* src_images,   /* [B,H,W,3] */
+                        const uint8_t* src_masks,    /* [B,H,W,T] 0/1 */
+                        const int32_t* src_class_ids,/* [B,T], 0 = empty slot */
+                        const double*  params,       /* [B,8]: m00 m01 m02 m10 m11 m12 gain bias */
+                        double cval, const double* anchors /* [2A] */,
+                        float* images, uint8_t* gt_masks, int32_t* gt_boxes, int32_t* gt_class_ids,
+                        float* y_true /* [B,G,G,A,5+C], or NULL with true_boxes */, float* true_boxes /* [B,T,4] */,
+                        int B, int H, int W, int T, int G, int A, int C,
+                        void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

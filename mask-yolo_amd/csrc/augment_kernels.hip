@@ -1,0 +1,283 @@
+// On-device training augmentation (myolo/augment.py: DeviceAugmenter): one more producer of the six training inputs, beside the Shapes
+// producer of exact_kernels.hip.  It takes the resident bytes and instance masks of a batch plus one inverse affine map, gain and bias per
+// image, and writes the warped image (bilinear), the warped instance masks (nearest) with empty instances dropped and the survivors compacted,
+// their tight boxes (extract_bboxes) and BatchGenerator._encode's YOLO targets of those boxes.
+//
+// The arithmetic is a contract ("On-device augmentation"): every operation below is ONE IEEE binary64 operation in the order
+// written -- this unit is compiled with -ffp-contract=off and asks for it again here -- so a numpy restatement reproduces every output bit.
+#include "myolo_common.h"
+#pragma clang fp contract(off)
+
+#define AUG_MAXT 32          // instance slots: bounds the LDS arrays of the stats and render kernels
+#define AUG_THREADS 256
+#define AUG_WAVES (AUG_THREADS / 64)
+
+// stats[b][t] = {count, W - minx, maxx + 1, H - miny, maxy + 1}: a sum and four maxima, so that all-zero is the empty state (one memset)
+#define AUG_STAT_INTS 5
+
+__device__ __forceinline__ void aug_source(const double* __restrict__ p, int x, int y, double& sx, double& sy)
+{
+    sx = (p[0] * x + p[1] * y) + p[2];
+    sy = (p[3] * x + p[4] * y) + p[5];
+}
+
+// nearest source pixel of the masks: floor(s + 0.5) inside the frame, or false
+__device__ __forceinline__ bool aug_nearest(double sx, double sy, int H, int W, int& ix, int& iy)
+{
+    const double fx = floor(sx + 0.5), fy = floor(sy + 0.5);
+    if (!(fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H)) return false;      // (also refuses NaN before the conversion)
+    ix = (int)fx; iy = (int)fy;
+    return true;
+}
+
+__device__ __forceinline__ int aug_wave_max(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+// the T mask bytes of a pixel start at a multiple of T: when T and the base pointer are multiples of V they are read V bytes at a time
+template <int V> __device__ __forceinline__ uint32_t aug_load(const uint8_t* p)
+{
+    if (V == 4) return *(const uint32_t*)p;
+    if (V == 2) return *(const uint16_t*)p;
+    return *p;
+}
+
+#define AUG_SPT 4            // output pixels per thread of the stats kernel
+
+// pass 1: per (image, source instance) warped pixel count and extent.  A thread takes AUG_SPT output pixels (AUG_THREADS apart, so a wave's loads stay
+// neighbours); count / extent are reduced across the wave (ballot + popcount, shuffles), then across the workgroup in LDS, and reach memory as at
+// most one set of integer atomics per (workgroup, instance) -- none for an instance the workgroup did not see.
+template <int V>
+__global__ __launch_bounds__(AUG_THREADS) void augment_stats_kernel(const uint8_t* __restrict__ src_masks, const int32_t* __restrict__ src_ids,
+                                                                    const double* __restrict__ params, int* __restrict__ stats,
+                                                                    int H, int W, int T)
+{
+    __shared__ int red[AUG_WAVES][AUG_MAXT][AUG_STAT_INTS];
+    const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long long HW = (long long)H * W;
+    const uint8_t* mb = src_masks + (long long)b * HW * T;
+    int px[AUG_SPT], py[AUG_SPT];
+    long long off[AUG_SPT];                                    // byte offset of the source pixel's slots, or -1: no source pixel
+#pragma unroll
+    for (int j = 0; j < AUG_SPT; ++j) {
+        const long long pix = ((long long)blockIdx.x * AUG_SPT + j) * AUG_THREADS + tid;
+        py[j] = (int)(pix / W); px[j] = (int)(pix - (long long)py[j] * W);
+        off[j] = -1;
+        if (pix < HW) {                                        // (the ragged last workgroup keeps its lanes for the wave reductions)
+            double sx, sy;
+            int ix, iy;
+            aug_source(params + (long long)b * 8, px[j], py[j], sx, sy);
+            if (aug_nearest(sx, sy, H, W, ix, iy)) off[j] = ((long long)iy * W + ix) * T;
+        }
+    }
+    for (int w = 0; w < T; w += V) {
+        uint32_t word[AUG_SPT];
+#pragma unroll
+        for (int j = 0; j < AUG_SPT; ++j) word[j] = off[j] >= 0 ? aug_load<V>(mb + off[j] + w) : 0u;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int t = w + k;
+            const bool live = src_ids[b * T + t] != 0;
+            int cnt = 0, a = 0, c = 0, d = 0, e = 0;
+#pragma unroll
+            for (int j = 0; j < AUG_SPT; ++j) {
+                const bool in = live && ((word[j] >> (8 * k)) & 0xffu) != 0;
+                cnt += __popcll(__ballot(in));
+                if (in) { a = max(a, W - px[j]); c = max(c, px[j] + 1); d = max(d, H - py[j]); e = max(e, py[j] + 1); }
+            }
+            if (cnt) {                                         // wave-uniform: it comes from ballots
+                a = aug_wave_max(a); c = aug_wave_max(c); d = aug_wave_max(d); e = aug_wave_max(e);
+            }
+            if (lane == 0) { int* r = red[wave][t]; r[0] = cnt; r[1] = a; r[2] = c; r[3] = d; r[4] = e; }
+        }
+    }
+    __syncthreads();
+    if (tid < T) {
+        int cnt = 0, v[4] = {0, 0, 0, 0};
+        for (int w = 0; w < AUG_WAVES; ++w) {
+            cnt += red[w][tid][0];
+            for (int k = 0; k < 4; ++k) v[k] = max(v[k], red[w][tid][1 + k]);
+        }
+        if (cnt) {
+            int* st = stats + ((long long)b * T + tid) * AUG_STAT_INTS;
+            atomicAdd(st, cnt);
+            for (int k = 0; k < 4; ++k) atomicMax(st + 1 + k, v[k]);
+        }
+    }
+}
+
+// pass 2 (one workgroup per image): compaction of the surviving instances (load_image_gt's np.sum(mask) > 0 filter), boxes, class ids and
+// BatchGenerator._encode's targets -- the arithmetic of shapes_encode_kernel (exact_kernels.hip), in double: first-maximum anchor, a later box
+// overwrites a shared cell, true_boxes wraps modulo T.  The outputs were zeroed by the caller.
+__global__ void augment_encode_kernel(const int32_t* __restrict__ src_ids, const int* __restrict__ stats, int* __restrict__ slotmap,
+                                      int32_t* __restrict__ gt_ids, int32_t* __restrict__ gt_boxes, float* __restrict__ y_true,
+                                      float* __restrict__ true_boxes, const double* __restrict__ anchors, int H, int W, int T, int G, int A, int C)
+{
+    const int b = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    const double cell_w = (double)W / G, cell_h = (double)H / G;
+    int m = 0, tbi = 0;
+    for (int k = 0; k < T; ++k) {
+        const int* st = stats + ((long long)b * T + k) * AUG_STAT_INTS;
+        const int cls = src_ids[b * T + k];
+        if (cls == 0 || st[0] <= 0) { slotmap[b * T + k] = -1; continue; }
+        slotmap[b * T + k] = m;
+        const int x1 = W - st[1], x2 = st[2], y1 = H - st[3], y2 = st[4];     // extract_bboxes: x2, y2 exclusive
+        gt_ids[b * T + m] = cls;
+        int32_t* gb = gt_boxes + ((long long)b * T + m) * 4;
+        gb[0] = x1; gb[1] = y1; gb[2] = x2; gb[3] = y2;
+        if (y_true) {
+            const double cx = .5 * (x1 + x2) / cell_w, cy = .5 * (y1 + y2) / cell_h;
+            const int gx = (int)floor(cx), gy = (int)floor(cy);
+            if (gx < G && gy < G) {
+                const double bw = (x2 - x1) / cell_w, bh = (y2 - y1) / cell_h;
+                int best = 0;
+                double max_iou = -1;
+                for (int j = 0; j < A; ++j) {
+                    const double aw = anchors[2 * j], ah = anchors[2 * j + 1];
+                    const double iw = fmin(bw, aw), ih = fmin(bh, ah);
+                    const double inter = iw * ih;
+                    const double iou = inter / (bw * bh + aw * ah - inter);
+                    if (max_iou < iou) { best = j; max_iou = iou; }
+                }
+                float* yt = y_true + ((((long long)b * G + gy) * G + gx) * A + best) * (5 + C);
+                yt[0] = (float)cx; yt[1] = (float)cy; yt[2] = (float)bw; yt[3] = (float)bh; yt[4] = 1.0f;
+                if ((unsigned)cls < (unsigned)C) yt[5 + cls] = 1.0f;
+                float* tb = true_boxes + ((long long)b * T + tbi) * 4;
+                tb[0] = (float)cx; tb[1] = (float)cy; tb[2] = (float)bw; tb[3] = (float)bh;
+                tbi = (tbi + 1) % T;
+            }
+        }
+        ++m;
+    }
+}
+
+// pass 3: pixels.  A workgroup owns AUG_THREADS consecutive output pixels: each thread samples its pixel into LDS, then the workgroup writes its
+// 3 * AUG_THREADS floats and T * AUG_THREADS mask bytes as contiguous runs (consecutive lanes, consecutive words).
+template <int V>
+__global__ __launch_bounds__(AUG_THREADS) void augment_render_kernel(const uint8_t* __restrict__ src_images, const uint8_t* __restrict__ src_masks,
+                                                                     const double* __restrict__ params, const int* __restrict__ slotmap,
+                                                                     double cval, float* __restrict__ images, uint8_t* __restrict__ masks,
+                                                                     int H, int W, int T, int words_ok)
+{
+    __shared__ float s_img[AUG_THREADS * 3];
+    __shared__ __attribute__((aligned(4))) uint8_t s_msk[AUG_THREADS * AUG_MAXT];
+    __shared__ int s_slot[AUG_MAXT];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const long long HW = (long long)H * W;
+    const long long pix0 = (long long)blockIdx.x * AUG_THREADS, pix = pix0 + tid;
+    const int nv = (int)((HW - pix0) < AUG_THREADS ? (HW - pix0) : AUG_THREADS);      // pixels of this workgroup inside the image
+    if (tid < T) s_slot[tid] = slotmap[b * T + tid];
+    __syncthreads();
+    if (tid < nv) {
+        const int py = (int)(pix / W), px = (int)(pix - (long long)py * W);
+        const double* p = params + (long long)b * 8;
+        double sx, sy;
+        aug_source(p, px, py, sx, sy);
+        // masks: nearest
+        uint8_t* sm = s_msk + tid * T;
+        for (int t = 0; t < T; ++t) sm[t] = 0;
+        int ix, iy;
+        if (aug_nearest(sx, sy, H, W, ix, iy)) {
+            const uint8_t* mp = src_masks + ((long long)b * HW + (long long)iy * W + ix) * T;
+            for (int w = 0; w < T; w += V) {
+                const uint32_t word = aug_load<V>(mp + w);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const int slot = s_slot[w + k];
+                    if (slot >= 0 && ((word >> (8 * k)) & 0xffu) != 0) sm[slot] = 1;
+                }
+            }
+        }
+        // image: bilinear, a tap outside the frame reads cval
+        const double flx = floor(sx), fly = floor(sy);
+        const double fx = sx - flx, fy = sy - fly;
+        const bool near_x = flx >= -1.0 && flx < (double)W, near_y = fly >= -1.0 && fly < (double)H;       // some tap may be inside
+        const int x0 = near_x ? (int)flx : -2, y0 = near_y ? (int)fly : -2;
+        const bool in_x0 = x0 >= 0 && x0 < W, in_x1 = x0 + 1 >= 0 && x0 + 1 < W;
+        const bool in_y0 = y0 >= 0 && y0 < H, in_y1 = y0 + 1 >= 0 && y0 + 1 < H;
+        const uint8_t* ib = src_images + (long long)b * HW * 3;
+        const uint8_t* r0 = ib + ((long long)y0 * W + x0) * 3;
+        const uint8_t* r1 = r0 + (long long)W * 3;
+        for (int c = 0; c < 3; ++c) {
+            const double p00 = (in_y0 && in_x0) ? (double)r0[c] : cval, p01 = (in_y0 && in_x1) ? (double)r0[3 + c] : cval;
+            const double p10 = (in_y1 && in_x0) ? (double)r1[c] : cval, p11 = (in_y1 && in_x1) ? (double)r1[3 + c] : cval;
+            const double top = (1.0 - fx) * p00 + fx * p01;
+            const double bot = (1.0 - fx) * p10 + fx * p11;
+            double v = (1.0 - fy) * top + fy * bot;
+            v = fmin(fmax(p[6] * v + p[7], 0.0), 255.0);
+            s_img[tid * 3 + c] = (float)(v / 255.0);
+        }
+    }
+    __syncthreads();
+    float* ip = images + ((long long)b * HW + pix0) * 3;
+    for (int i = tid; i < nv * 3; i += AUG_THREADS) ip[i] = s_img[i];
+    uint8_t* mo = masks + ((long long)b * HW + pix0) * T;
+    const int nbytes = nv * T;
+    int done = 0;
+    if (words_ok) {                                            // mo is 4-aligned: pix0 * T is a multiple of 256 and the caller checked the rest
+        const int nwords = nbytes >> 2;
+        const uint32_t* sw = (const uint32_t*)s_msk;
+        uint32_t* mw = (uint32_t*)mo;
+        for (int i = tid; i < nwords; i += AUG_THREADS) mw[i] = sw[i];
+        done = nwords << 2;
+    }
+    for (int i = done + tid; i < nbytes; i += AUG_THREADS) mo[i] = s_msk[i];
+}
+
+extern "C" {
+
+size_t myolo_augment_batch_ws_bytes(int B, int T)
+{
+    if (B <= 0 || T <= 0) return 0;
+    return (size_t)B * T * (AUG_STAT_INTS + 1) * sizeof(int);
+}
+
+int myolo_augment_batch(const uint8_t* src_images, const uint8_t* src_masks, const int32_t* src_class_ids, const double* params, double cval,
+                        const double* anchors, float* images, uint8_t* gt_masks, int32_t* gt_boxes, int32_t* gt_class_ids, float* y_true,
+                        float* true_boxes, int B, int H, int W, int T, int G, int A, int C, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(src_images && src_masks && src_class_ids && params && images && gt_masks && gt_boxes && gt_class_ids,
+                  "augment_batch: null pointer");
+    MYOLO_REQUIRE((y_true != nullptr) == (true_boxes != nullptr), "augment_batch: y_true and true_boxes are given together or not at all");
+    MYOLO_REQUIRE(!y_true || anchors, "augment_batch: targets need the anchors");
+    MYOLO_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31) - AUG_THREADS * AUG_SPT, "augment_batch: bad sizes (B=%d, H=%d, W=%d)", B, H, W);
+    MYOLO_REQUIRE(T > 0 && T <= AUG_MAXT, "augment_batch: need 1 <= T <= %d (got %d)", AUG_MAXT, T);
+    MYOLO_REQUIRE(!y_true || (G > 0 && A > 0 && C > 0), "augment_batch: bad target sizes (G=%d, A=%d, C=%d)", G, A, C);
+    MYOLO_NEED_WS(myolo_augment_batch_ws_bytes(B, T));
+    int* stats = (int*)ws;
+    int* slotmap = stats + (size_t)B * T * AUG_STAT_INTS;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipMemsetAsync(stats, 0, (size_t)B * T * AUG_STAT_INTS * sizeof(int), s);
+    (void)hipMemsetAsync(gt_boxes, 0, (size_t)B * T * 4 * sizeof(int32_t), s);
+    (void)hipMemsetAsync(gt_class_ids, 0, (size_t)B * T * sizeof(int32_t), s);
+    if (y_true) {
+        (void)hipMemsetAsync(y_true, 0, (size_t)B * G * G * A * (5 + C) * sizeof(float), s);
+        (void)hipMemsetAsync(true_boxes, 0, (size_t)B * T * 4 * sizeof(float), s);
+    }
+    const long long HW = (long long)H * W;
+    const dim3 grid((unsigned)((HW + AUG_THREADS - 1) / AUG_THREADS), B), grid1((unsigned)((HW + AUG_THREADS * AUG_SPT - 1) / (AUG_THREADS * AUG_SPT)), B);
+    // bytes per load of a pixel's T mask slots: every pixel's run starts on a multiple of T from the base pointer
+    const int V = (T % 4 == 0 && ((uintptr_t)src_masks & 3) == 0) ? 4 : (T % 2 == 0 && ((uintptr_t)src_masks & 1) == 0) ? 2 : 1;
+    // word stores of the mask bytes need every workgroup's run to start on a word: the base pointer and each image's H*W*T bytes
+    const int words_ok = (((uintptr_t)gt_masks & 3) == 0 && ((HW * T) & 3) == 0) ? 1 : 0;
+#define AUG_LAUNCH(V_)                                                                                                                       \
+    do {                                                                                                                                     \
+        hipLaunchKernelGGL(augment_stats_kernel<V_>, grid1, dim3(AUG_THREADS), 0, s, src_masks, src_class_ids, params, stats, H, W, T);      \
+        hipLaunchKernelGGL(augment_encode_kernel, dim3(B), dim3(64), 0, s, src_class_ids, (const int*)stats, slotmap, gt_class_ids, gt_boxes, \
+                           y_true, true_boxes, anchors, H, W, T, G, A, C);                                                                  \
+        hipLaunchKernelGGL(augment_render_kernel<V_>, grid, dim3(AUG_THREADS), 0, s, src_images, src_masks, params, (const int*)slotmap, cval, \
+                           images, gt_masks, H, W, T, words_ok);                                                                             \
+    } while (0)
+    if (V == 4) AUG_LAUNCH(4);
+    else if (V == 2) AUG_LAUNCH(2);
+    else AUG_LAUNCH(1);
+#undef AUG_LAUNCH
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+}  // extern "C"

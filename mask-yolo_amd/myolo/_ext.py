@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MYOLO_LIB: an alternative build of the same C-ABI (the sanitizer build of __graft_entry__.build_sanitized(), used by the host-side tests)
 LIB_PATH = os.environ.get("MYOLO_LIB") or os.path.join(_HERE, "_lib", "libmyolo_hip.so")
 
-P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+P, I, L, F, Z, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 
 # name -> argtypes (all return int).  Order/meaning: include/myolo_hip.h
 SIGS = {
@@ -132,6 +132,7 @@ SIGS = {
     "myolo_residual_bwd": [P, P, P, L, P],
     "myolo_fill": [P, F, L, P],
     "myolo_u8_to_unit_f32": [P, P, L, P],
+    "myolo_augment_batch": [P, P, P, P, D, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],
@@ -211,6 +212,8 @@ def load():
     lib.myolo_dwconv3x3_bwd_data_bnsums_rows.restype = I
     lib.myolo_conv7x7s2_c3_ws_bytes.argtypes = [I, I, I, I]
     lib.myolo_conv7x7s2_c3_ws_bytes.restype = Z
+    lib.myolo_augment_batch_ws_bytes.argtypes = [I, I]
+    lib.myolo_augment_batch_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
     lib.myolo_wprep_refresh.restype = I
     _LIB = lib
@@ -222,7 +225,7 @@ def exported_symbols():
                               "myolo_pwconv1x1_bnstats_ws_bytes", "myolo_pwconv1x1_bnstats_ok",
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
-                              "myolo_conv7x7s2_c3_ws_bytes"]
+                              "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes"]
 
 
 def ptr(t):
@@ -425,6 +428,10 @@ def measure_mfma_tflops(iters=20000, reps=3, device="cuda:0"):
 
 def conv7x7s2_ws_bytes(n, h, w, cout):
     return int(load().myolo_conv7x7s2_c3_ws_bytes(int(n), int(h), int(w), int(cout)))
+
+
+def augment_ws_bytes(b, t):
+    return int(load().myolo_augment_batch_ws_bytes(int(b), int(t)))
 
 
 def workspace_bytes(rows, cin, cout):

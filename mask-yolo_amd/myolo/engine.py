@@ -1941,6 +1941,35 @@ class Net(object):
                 ("y_true", (n, cfg.GRID_H, G, A, 5 + C), torch.float32)]
         if not yolo:
             spec += [("gt_ids", (n, T), torch.int32), ("gt_boxes", (n, T, 4), torch.int32), ("gt_masks", (n, H, W, cfg.MAX_GT_INSTANCES), torch.uint8)]
+
+        def finish(out):
+            if u8_images:
+                raw = out["images"]
+                out["images"] = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev)
+                X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(out["images"]), raw.numel(), X.stream())
+                out["_raw_images"] = raw              # (kept until the conversion has run)
+            return out
+        return self._stage_upload(spec, fill, finish)
+
+    def stage_augmented(self, fill, n, augmenter, yolo=False):
+        """The augmented form of stage_batch: fill(arrays) writes [raw images uint8 [n,H,W,3], un-augmented masks uint8 [n,H,W,T], class ids
+        int32 [n,T] (0 = empty slot), parameter rows float64 [n,8]] (BatchGenerator.fill_raw) into the same ring of pinned staging sets; behind
+        the copies, on the copy stream, `augmenter` (myolo.augment.DeviceAugmenter) produces the step's inputs from them.  No target is encoded
+        on the host.  -> device batch dict (the three arrays of 'yolo' mode with yolo=True)."""
+        cfg = self.cfg
+        H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
+        spec = [("raw_images", (n, H, W, 3), torch.uint8), ("src_masks", (n, H, W, T), torch.uint8), ("src_ids", (n, T), torch.int32),
+                ("aug_params", (n, 8), torch.float64)]
+
+        def finish(out):
+            return augmenter.apply(out["raw_images"], out["src_masks"], out["src_ids"], out["aug_params"], yolo=yolo)
+        return self._stage_upload(spec, fill, finish)
+
+    def _stage_upload(self, spec, fill, finish):
+        """one staging set of the ring: fill(arrays) into its pinned buffers (one per (name, shape, dtype) of `spec`), the asynchronous copies
+        into fresh device tensors on the copy stream, then finish(dict) -> dict there (device work that belongs behind the copies); the
+        result carries the event `_ready`."""
+        dev = self.dev
         with self._stage_lock:
             if self._stage is None:
                 self._stage = [dict(bufs={}, ev=None, busy=threading.Lock()) for _ in range(self._STAGE_SETS)]
@@ -1979,11 +2008,7 @@ class Net(object):
                     t = torch.empty(shape, dtype=dt, device=dev)
                     t.copy_(st["bufs"][(key, shape, dt)], non_blocking=True)
                     out[key] = t
-                if u8_images:
-                    raw = out["images"]
-                    out["images"] = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev)
-                    X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(out["images"]), raw.numel(), X.stream())
-                    out["_raw_images"] = raw              # (kept until the conversion has run)
+                out = finish(out)
                 ev = torch.cuda.Event()
                 ev.record(self._copy_stream)
                 st["ev"] = ev

@@ -390,14 +390,23 @@ class MaskYOLO(object):
         if layers in layer_regex:
             layers = layer_regex[layers]
         cfg = self.config
+        if augmentation is not None:
+            from .augment import Augmentation
+            if not isinstance(augmentation, Augmentation):
+                raise TypeError("augmentation must be a myolo.augment.Augmentation (the warp runs on the device; imgaug objects are not taken), "
+                                "got %r" % type(augmentation).__name__)
 
-        def collect(ds):
+        def collect(ds, tag=False):
             ids = list(ds.image_ids)
             if max_samples is not None:
                 ids = ids[:max_samples]
-            return [list(mutils.load_image_gt(ds, cfg, i, use_mini_mask=cfg.USE_MINI_MASK)) for i in ids]
+            info = [list(mutils.load_image_gt(ds, cfg, i, use_mini_mask=cfg.USE_MINI_MASK)) for i in ids]
+            if tag:        # the augmented path keys a sample's parameters by its dataset image id: the generator shuffles these rows
+                for inst, i in zip(info, ids):
+                    inst.append(int(i))
+            return info
 
-        train_info = collect(train_dataset)
+        train_info = collect(train_dataset, tag=augmentation is not None)
         val_info = collect(val_dataset) if val_dataset is not None else []
         mode = self.mode if self.mode in ('yolo', 'training') else 'training'
         rank, world = self._data_parallel()
@@ -428,9 +437,13 @@ class MaskYOLO(object):
                 print("epoch %d step %d/%d loss %.4f (yolo %.4f mask %.4f recall %.3f)" %
                       (ep + 1, i + 1, n_steps, out["loss"], out["yolo_sum_loss"], out["mask_loss"], out["recall"]))
 
+        make_item = lambda it: make(it[1])             # noqa: E731
+        if augmentation is not None:
+            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
+
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
         # are encoded and uploaded while epoch e finishes
-        prefetch = _Prefetcher([(e, i) for e in range(epochs) for i in schedule], lambda it: make(it[1]), self.net.dev)
+        prefetch = _Prefetcher([(e, i) for e in range(epochs) for i in schedule], make_item, self.net.dev)
         stream = iter(prefetch)
         try:
             with _gc_parked():                          # for the whole run: a full collection at every epoch end cost ~50 ms per epoch
@@ -475,6 +488,35 @@ class MaskYOLO(object):
 
         self.epoch = max(self.epoch, epochs)
         return history
+
+    def augmentation_rows(self, augmentation, no_augmentation_sources, dataset, epoch, image_ids):
+        """-> float64 [n,8]: the parameter rows train() hands the device augmenter for these dataset image ids in this epoch -- keyed by image id
+        and epoch (never by position after the shuffle), the identity for a sample whose source is in no_augmentation_sources."""
+        from .augment import IDENTITY_ROW
+        H, W = self.config.IMAGE_SHAPE[0], self.config.IMAGE_SHAPE[1]
+        skip = set(no_augmentation_sources or [])
+        rows = np.empty((len(image_ids), 8), np.float64)
+        for k, i in enumerate(image_ids):
+            plain = bool(skip) and dataset.image_info[i]['source'] in skip
+            rows[k] = IDENTITY_ROW if plain else augmentation.params(epoch, i, H, W)
+        return rows
+
+    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+        """-> make((epoch, batch index)) for train()'s prefetch thread: raw bytes, un-augmented masks, class ids and parameter rows go up through the
+        engine's staging ring, and the device augmenter runs behind the copies on the copy stream, under the previous step."""
+        from .augment import DeviceAugmenter
+        if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
+            raise ValueError("train(augmentation=...) needs uint8 images")
+        aug = DeviceAugmenter(self.config, self.net.dev, cval=augmentation.cval)
+
+        def make(it):
+            epoch, i = it
+            lo, hi = gen.batch_bounds(i)
+
+            def row_of(inst):
+                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
+            return self.net.stage_augmented(lambda arrays: gen.fill_raw(i, arrays, row_of), hi - lo, aug, yolo=(mode == 'yolo'))
+        return make
 
     def train_shapes_stream(self, steps, learning_rate=None, seed=1234, start_index=0, verbose=0):
         """Train on the endless synthetic Shapes stream with the inputs produced ON THE DEVICE

@@ -5,7 +5,7 @@ post-processing helpers.  Same names / argument meaning as the reference's
 
   BatchGenerator.__getitem__  myolo_utils.py:727-860   (a19)
   extract_bboxes              myolo_utils.py:247-271   (a20)
-  load_image_gt               myolo_utils.py:274-366   (no resize/augment: out of scope)
+  load_image_gt               myolo_utils.py:274-366   (imgaug augmentation is not taken: myolo.augment does it on the device)
   BoundBox/bbox_iou           myolo_utils.py:161-244
   decode_one_yolo_output/NMB/unmold_mask  :36-113,883-912  ("next" rows, section 8(f))
 
@@ -145,7 +145,8 @@ def resize_mask(mask, scale):
 def load_image_gt(dataset, config, image_id, augment=False, augmentation=None, use_mini_mask=False):
     """-> image, class_ids, bbox [n,(x1,y1,x2,y2)], mask [H,W,n] (myolo_utils.py:274-366): load, resize image and masks to
     config.IMAGE_SHAPE, drop the instances whose mask came out empty, tight boxes.  `augment=True` is the reference's deprecated random horizontal flip; imgaug
-    augmentation and mini-masks are image-file I/O options outside the hot path and are refused.  Pinned by tests/golden/ref_load_image_gt.npz (the reference's function executed)."""
+    augmentation and mini-masks are image-file I/O options outside the hot path and are refused here (training augmentation runs on the device:
+    myolo.augment.Augmentation through MaskYOLO.train).  Pinned by tests/golden/ref_load_image_gt.npz (the reference's function executed)."""
     if augmentation is not None or use_mini_mask:
         raise NotImplementedError("imgaug augmentation / mini-masks are outside the hot path")
     image = dataset.load_image(image_id)
@@ -243,6 +244,30 @@ class BatchGenerator(object):
             self._encode(l_bound, r_bound, out[0], tb, out[2], None, None, None)
         else:
             self._encode(l_bound, r_bound, out[0], tb, out[2], out[3], out[4], out[5])
+        return out
+
+    def fill_raw(self, idx, out, row_of):
+        """The augmented path's form of fill: batch idx as the device augmenter takes it (myolo.augment.DeviceAugmenter), written INTO `out` =
+        [raw images uint8 [n,H,W,3], instance masks uint8 / bool [n,H,W,T], class ids int32 [n,T] (0 = empty slot), parameter rows float64 [n,8]];
+        row_of(sample) -> the sample's eight parameters.  Nothing is encoded here: boxes and targets are re-derived on the device from the warped
+        masks.  More than T instances are sub-sampled as in _encode (myolo_utils.py:758-761)."""
+        l_bound, r_bound = self.batch_bounds(idx)
+        images, masks_b, ids_b, rows = out
+        T = self.config.TRUE_BOX_BUFFER
+        masks_b.fill(0)
+        ids_b.fill(0)
+        for k, inst in enumerate(self.all_info[l_bound:r_bound]):
+            image, class_ids, masks = inst[0], inst[1], inst[3]
+            if image.dtype != np.uint8:
+                raise ValueError("the augmented path needs uint8 images, got %s" % image.dtype)
+            if class_ids.shape[0] > T:
+                ids = np.random.choice(np.arange(class_ids.shape[0]), T, replace=False)
+                class_ids, masks = class_ids[ids], masks[:, :, ids]
+            images[k] = image
+            ids_b[k, :class_ids.shape[0]] = class_ids
+            for j in range(masks.shape[-1]):
+                masks_b[k, :, :, j] = masks[:, :, j]
+            rows[k] = row_of(inst)
         return out
 
     def _encode(self, l_bound, r_bound, images, true_boxes, y_true, gt_ids, gt_boxes_b, gt_masks_b):
