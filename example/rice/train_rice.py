@@ -1,0 +1,48 @@
+#!/usr/bin/env python
+"""Train Mask-YOLO on a dataset annotated with the VGG Image Annotator on one MI355X -- the working counterpart of the reference's
+example/rice/train_rice.py and rice_dataset.py (RiceConfig, a dataset of <dir>/train and <dir>/val, each with its images and one
+via_*_annotation.json, MaskYOLO(mode="training"), model.train(...)).  The outlines are rasterised on the device: no mask
+is built on the host.
+
+  python example/rice/train_rice.py DATASET_DIR [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks]
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
+from myolo.augment import Augmentation               # noqa: E402
+from myolo.config import RiceConfig, make_config     # noqa: E402
+from myolo.model import MaskYOLO                     # noqa: E402
+from myolo.via import load_via                       # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("dataset", help="directory with train/ and val/, each holding the images and one via_*_annotation.json")
+    ap.add_argument("--epochs", type=int, default=30)
+    ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--logs", default="./logs")
+    ap.add_argument("--no-augment", action="store_true")
+    ap.add_argument("--host-masks", action="store_true", help="fill the outlines on the host (load_mask) instead of on the device")
+    a = ap.parse_args()
+
+    config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
+    dataset_train = load_via(a.dataset, "train")
+    dataset_val = load_via(a.dataset, "val") if os.path.isdir(os.path.join(a.dataset, "val")) else None
+    print("train: %d images, classes %s" % (len(dataset_train.image_ids), dataset_train.class_names))
+    augmentation = None if a.no_augment else Augmentation(fliplr=.5, scale=(.8, 1.2), translate=(-.1, .1), rotate=(-15, 15),
+                                                          brightness=(.8, 1.2))
+    model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)
+    hist = model.train(dataset_train, dataset_val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all',
+                       augmentation=augmentation, device_polygons=not a.host_masks)
+    print("epoch losses:", ["%.4f" % h for h in hist])
+    print("batches rasterised on the device: %d of %d" % (model.host_times["polygon_batches"], model.host_times["steps"]))
+    os.makedirs(a.logs, exist_ok=True)
+    model.save_weights(os.path.join(a.logs, "mask_yolo_rice_final.npz"))
+
+
+if __name__ == "__main__":
+    main()

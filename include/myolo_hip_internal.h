@@ -324,6 +324,18 @@ int myolo_augment_batch(const uint8_t* src_images,   /* [B,H,W,3] */
                         int B, int H, int W, int T, int G, int A, int C,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---- polygon rasteriser (myolo/via.py datasets, csrc/polygon_kernels.hip; arithmetic contract: DESIGN.md "Polygon annotations").  Fills the
+ * outlines of a batch into the instance masks myolo_augment_batch reads: masks[b,i,j,t] = 1 when skimage.draw.polygon (0.18.3) lists source pixel
+ * (src_row[b,i], src_col[b,j]) for the polygon of slot b*T+t.  The two tables are made on the host by the rule of resize_mask (the identity for an
+ * image already at network size); they only name pixels inside the source frame, which is all the frame clipping there is.  No limit on the
+ * vertices of a polygon, nor on T. */
+int myolo_polygon_masks(const double* verts,      /* [n_total,2] (row, col), source-image pixels */
+                        const int32_t* poly_off,  /* [B*T+1] offsets into verts; slot k empty when off[k+1]==off[k] */
+                        const int32_t* src_row,   /* [B,H] source row that output row i samples */
+                        const int32_t* src_col,   /* [B,W] */
+                        uint8_t* masks,           /* [B,H,W,T] 0/1, EVERY element written */
+                        int B, int H, int W, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,7 @@ SIGS = {
     "myolo_fill": [P, F, L, P],
     "myolo_u8_to_unit_f32": [P, P, L, P],
     "myolo_augment_batch": [P, P, P, P, D, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
+    "myolo_polygon_masks": [P, P, P, P, P, I, I, I, I, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],

@@ -1965,6 +1965,32 @@ class Net(object):
             return augmenter.apply(out["raw_images"], out["src_masks"], out["src_ids"], out["aug_params"], yolo=yolo)
         return self._stage_upload(spec, fill, finish)
 
+    def stage_polygons(self, fill, n, augmenter, yolo=False, n_verts=0):
+        """stage_augmented for outlines instead of masks (myolo.via datasets): fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64
+        [cap,2] (row, col) in source-image pixels packed slot after slot, offsets int32 [n*T+1] into them (slot k empty when off[k+1] == off[k]),
+        class ids int32 [n,T] (0 = empty slot), source-row table int32 [n,H], source-column table int32 [n,W] (myolo_utils.mask_index_tables),
+        parameter rows float64 [n,8]] (BatchGenerator.polygon_batch).  Behind the copies, on the copy stream, myolo_polygon_masks fills the
+        outlines into a device [n,H,W,T] buffer and `augmenter` takes it from there: no mask exists on the host or crosses PCIe.
+        n_verts: the vertices fill will write; the pinned vertex buffer holds cap = the next power of two (at least 1024), so that batches of
+        different outlines share a few staging shapes."""
+        cfg, dev = self.cfg, self.dev
+        H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
+        cap = 1024
+        while cap < n_verts:
+            cap *= 2
+        spec = [("raw_images", (n, H, W, 3), torch.uint8), ("poly_verts", (cap, 2), torch.float64), ("poly_off", (n * T + 1,), torch.int32),
+                ("src_ids", (n, T), torch.int32), ("src_row", (n, H), torch.int32), ("src_col", (n, W), torch.int32),
+                ("aug_params", (n, 8), torch.float64)]
+
+        def finish(out):
+            masks = torch.empty((n, H, W, T), dtype=torch.uint8, device=dev)
+            X.call("myolo_polygon_masks", X.ptr(out["poly_verts"]), X.ptr(out["poly_off"]), X.ptr(out["src_row"]), X.ptr(out["src_col"]),
+                   X.ptr(masks), n, H, W, T, X.stream())
+            d = augmenter.apply(out["raw_images"], masks, out["src_ids"], out["aug_params"], yolo=yolo)
+            d["_poly_src"] = (out["poly_verts"], out["poly_off"], out["src_row"], out["src_col"])      # read asynchronously, like _src
+            return d
+        return self._stage_upload(spec, fill, finish)
+
     def _stage_upload(self, spec, fill, finish):
         """one staging set of the ring: fill(arrays) into its pinned buffers (one per (name, shape, dtype) of `spec`), the asynchronous copies
         into fresh device tensors on the copy stream, then finish(dict) -> dict there (device work that belongs behind the copies); the

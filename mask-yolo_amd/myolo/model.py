@@ -244,7 +244,8 @@ class MaskYOLO(object):
         self.net = self.build(mode=mode, config=self.config)
         self.keras_model = _KerasModelShim(self)
         self.epoch = 0
-        self.host_times = {"wait_for_batch_s": 0.0, "launch_step_s": 0.0, "steps": 0}    # train(): where the launch thread's wall time goes
+        # train(): where the launch thread's wall time goes; polygon_batches = the batches that came through Net.stage_polygons
+        self.host_times = {"wait_for_batch_s": 0.0, "launch_step_s": 0.0, "steps": 0, "polygon_batches": 0}
 
     # ------------------------------------------------------------------ build
     def build(self, mode, config):
@@ -380,12 +381,17 @@ class MaskYOLO(object):
                     loss_xy=float(yt[1]), loss_wh=float(yt[2]), loss_conf=float(yt[3]), loss_class=float(yt[4]), recall=float(yt[5]))
 
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers,
-              augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0):
+              augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0,
+              device_polygons=True):
         """model.py:943-1060.  Returns the list of per-epoch mean training losses; ``self.history`` holds
         {"loss": [...], "val_loss": [...]} like the Keras History the reference's fit_generator produces.
         shuffle_seed: the generators' one-off shuffle (myolo_utils.py:711-712) draws from RandomState(shuffle_seed) -- the
         same permutation on every data-parallel rank, so that dp_batch_indices really hands out disjoint samples; None =
-        the global numpy generator, as the reference (single process only)."""
+        the global numpy generator, as the reference (single process only).
+        device_polygons: a train_dataset that has load_polygons (myolo.via.VIADataset) is never asked for a mask: its outlines go to the device
+        and are filled there, in front of the device augmenter (identity rows with augmentation=None) -- DESIGN.md section 13.  An outline that
+        fills no pixel is dropped on the device, AFTER the sub-sampling to TRUE_BOX_BUFFER instances (the host route drops it before).
+        False, or a dataset without load_polygons: load_mask and the host route.  Validation batches always use load_mask."""
         layer_regex = {"all": ".*"}
         if layers in layer_regex:
             layers = layer_regex[layers]
@@ -406,7 +412,11 @@ class MaskYOLO(object):
                     inst.append(int(i))
             return info
 
-        train_info = collect(train_dataset, tag=augmentation is not None)
+        polygon_route = bool(device_polygons) and hasattr(train_dataset, "load_polygons")
+        if polygon_route:
+            train_info = self._collect_polygons(train_dataset, max_samples)
+        else:
+            train_info = collect(train_dataset, tag=augmentation is not None)
         val_info = collect(val_dataset) if val_dataset is not None else []
         mode = self.mode if self.mode in ('yolo', 'training') else 'training'
         rank, world = self._data_parallel()
@@ -438,7 +448,9 @@ class MaskYOLO(object):
                       (ep + 1, i + 1, n_steps, out["loss"], out["yolo_sum_loss"], out["mask_loss"], out["recall"]))
 
         make_item = lambda it: make(it[1])             # noqa: E731
-        if augmentation is not None:
+        if polygon_route:
+            make_item = self._polygon_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
+        elif augmentation is not None:
             make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
 
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
@@ -516,6 +528,57 @@ class MaskYOLO(object):
             def row_of(inst):
                 return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
             return self.net.stage_augmented(lambda arrays: gen.fill_raw(i, arrays, row_of), hi - lo, aug, yolo=(mode == 'yolo'))
+        return make
+
+    def _collect_polygons(self, dataset, max_samples=None):
+        """train()'s sample list on the polygon route: per image [image resized to the network frame uint8, class ids int32 [n], outlines (list of
+        float64 [k,2] (row, col) in source-image pixels), (source-row table int32 [H], source-column table int32 [W]), dataset image id].
+        load_image_gt without load_mask: the tables name the source pixel resize_mask would read for every pixel of the network frame."""
+        cfg = self.config
+        if cfg.USE_MINI_MASK:
+            raise NotImplementedError("mini-masks are outside the hot path")
+        H, W = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1]
+        ids = list(dataset.image_ids)
+        if max_samples is not None:
+            ids = ids[:max_samples]
+        info = []
+        for i in ids:
+            image = dataset.load_image(i)
+            polys, class_ids = dataset.load_polygons(i)
+            polys = [np.ascontiguousarray(p, dtype=np.float64) for p in polys]
+            class_ids = np.asarray(class_ids, dtype=np.int32)
+            if len(polys) != class_ids.shape[0] or any(p.ndim != 2 or p.shape[1] != 2 or p.shape[0] == 0 or not np.isfinite(p).all() for p in polys):
+                raise ValueError("load_polygons(%r): need one finite [k,2] (row, col) array with k >= 1 per class id" % (i,))
+            h, w = image.shape[:2]
+            scale = [1, 1]
+            if [h, w] != [H, W]:
+                image, scale = mutils.resize_image(image, cfg.IMAGE_SHAPE)
+            rows, cols = mutils.mask_index_tables(h, w, scale)
+            if rows.shape[0] != H or cols.shape[0] != W:
+                raise ValueError("image %r: %d x %d does not resize to the %d x %d network frame" % (i, h, w, H, W))
+            info.append([image, class_ids, polys, (rows.astype(np.int32), cols.astype(np.int32)), int(i)])
+        return info
+
+    def _polygon_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+        """-> make((epoch, batch index)) for train()'s prefetch thread on the polygon route: image bytes, outlines, class ids, index tables and
+        parameter rows go up through the engine's staging ring; the rasteriser and the device augmenter run behind the copies on the copy stream."""
+        from .augment import DeviceAugmenter, IDENTITY_ROW
+        if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
+            raise ValueError("train() on a dataset with load_polygons needs uint8 images (or device_polygons=False)")
+        aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
+
+        def make(it):
+            epoch, i = it
+            lo, hi = gen.batch_bounds(i)
+
+            def row_of(inst):
+                if augmentation is None:
+                    return IDENTITY_ROW
+                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
+            fill, n_verts = gen.polygon_batch(i, row_of)
+            db = self.net.stage_polygons(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts)
+            self.host_times["polygon_batches"] += 1
+            return db
         return make
 
     def train_shapes_stream(self, steps, learning_rate=None, seed=1234, start_index=0, verbose=0):

@@ -129,17 +129,25 @@ def resize_image(image, net_image_shape):
     return image.astype(image_dtype), scale
 
 
+def zoom_index(n, o):
+    """-> int [o]: the input index each of o outputs reads along an axis of extent n under scipy.ndimage.zoom order 0:
+    floor(i * (n - 1) / (o - 1) + .5) (corner-aligned nearest neighbour)."""
+    if o <= 1:
+        return np.zeros(max(o, 0), int)
+    return np.floor(np.arange(o) * ((n - 1) / float(o - 1)) + 0.5).astype(int)
+
+
+def mask_index_tables(h, w, scale):
+    """-> (src_row [round(h * scale_y)], src_col [round(w * scale_x)]): the source pixel every pixel of resize_mask's output reads.  Shared by
+    resize_mask and by the polygon rasterisers (myolo.polygon.polygon_mask_sampled, myolo_polygon_masks), which evaluate the fill only there."""
+    return zoom_index(h, int(round(h * scale[0]))), zoom_index(w, int(round(w * scale[1])))
+
+
 def resize_mask(mask, scale):
     """scipy.ndimage.zoom(mask, [scale_y, scale_x, 1], order=0) restated (myolo_utils.py:395-411): output extent round(n * scale), output
     index o reads input index floor(o * (n - 1) / (out - 1) + .5) (corner-aligned nearest neighbour)."""
-    h, w = mask.shape[:2]
-    oh, ow = int(round(h * scale[0])), int(round(w * scale[1]))
-
-    def idx(n, o):
-        if o <= 1:
-            return np.zeros(max(o, 0), int)
-        return np.floor(np.arange(o) * ((n - 1) / float(o - 1)) + 0.5).astype(int)
-    return mask[idx(h, oh)][:, idx(w, ow)]
+    rows, cols = mask_index_tables(mask.shape[0], mask.shape[1], scale)
+    return mask[rows][:, cols]
 
 
 def load_image_gt(dataset, config, image_id, augment=False, augmentation=None, use_mini_mask=False):
@@ -269,6 +277,46 @@ class BatchGenerator(object):
                 masks_b[k, :, :, j] = masks[:, :, j]
             rows[k] = row_of(inst)
         return out
+
+    def polygon_batch(self, idx, row_of):
+        """The polygon route's form of fill_raw (Net.stage_polygons): the samples are [resized image uint8, class ids int32 [n], outlines (list of
+        float64 [k,2] (row, col) in source-image pixels), (source-row table [H], source-column table [W]), ...] and no mask exists on the host.
+        -> (fill, n_verts): fill(out) writes batch idx INTO out = [raw images uint8 [n,H,W,3], vertices float64 [cap >= n_verts,2], offsets int32
+        [n*T+1], class ids int32 [n,T], source rows int32 [n,H], source columns int32 [n,W], parameter rows float64 [n,8]].  More than T outlines
+        are sub-sampled with the one np.random.choice draw fill_raw makes -- BEFORE anything is rasterised, so an outline that fills no pixel of
+        the network frame can take a slot here that the host route would have given to another instance."""
+        l_bound, r_bound = self.batch_bounds(idx)
+        T = self.config.TRUE_BOX_BUFFER
+        picked = []
+        for inst in self.all_info[l_bound:r_bound]:
+            class_ids, polys = inst[1], inst[2]
+            if inst[0].dtype != np.uint8:
+                raise ValueError("the polygon route needs uint8 images, got %s" % inst[0].dtype)
+            if class_ids.shape[0] > T:
+                ids = np.random.choice(np.arange(class_ids.shape[0]), T, replace=False)
+                class_ids, polys = class_ids[ids], [polys[j] for j in ids]
+            picked.append((inst, class_ids, polys))
+        n_verts = sum(p.shape[0] for _, _, polys in picked for p in polys)
+
+        def fill(out):
+            images, verts, off, ids_b, rows_t, cols_t, rows = out
+            if n_verts > verts.shape[0]:
+                raise ValueError("polygon_batch: %d vertices do not fit the %d staged" % (n_verts, verts.shape[0]))
+            ids_b.fill(0)
+            o = 0
+            for k, (inst, class_ids, polys) in enumerate(picked):
+                images[k] = inst[0]
+                ids_b[k, :class_ids.shape[0]] = class_ids
+                rows_t[k], cols_t[k] = inst[3]
+                for j in range(T):
+                    off[k * T + j] = o
+                    if j < len(polys):
+                        verts[o:o + polys[j].shape[0]] = polys[j]
+                        o += polys[j].shape[0]
+                rows[k] = row_of(inst)
+            off[len(picked) * T] = o
+            return out
+        return fill, n_verts
 
     def _encode(self, l_bound, r_bound, images, true_boxes, y_true, gt_ids, gt_boxes_b, gt_masks_b):
         """the body of myolo_utils.py:748-844 on zero-initialised outputs."""
