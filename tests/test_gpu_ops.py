@@ -61,6 +61,33 @@ def rnd(rng, *shape, scale=1.0):
     return (rng.standard_normal(shape) * scale).astype(np.float32)
 
 
+def _np(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+STAT_NAMES = ("mean", "var", "scale", "shift", "moving_mean", "moving_var")
+
+
+def check_stats_agree(got, want, what=""):
+    """BatchNorm statistics out of a fused output transform (mean, var, scale, shift, moving_mean, moving_var) against myolo_bn_stats of the same y:
+    within 2e-6 of the tensor's magnitude"""
+    for a, b, name in zip(got, want, STAT_NAMES):
+        a, b = _np(a), _np(b)
+        assert np.abs(a - b).max() <= 2e-6 * max(1.0, np.abs(b).max()), (what, name)
+
+
+def check_mean_var_float64(mean, var, y2d, what=""):
+    """mean / var against the float64 statistics of y [M, C]"""
+    ym = _np(y2d).astype(np.float64)
+    assert np.abs(_np(mean) - ym.mean(0)).max() < 1e-5 and np.abs(_np(var) - ym.var(0)).max() < 1e-4 * max(1.0, ym.var(0).max()), what
+
+
+def check_f63_equals_f43(got, want, what):
+    """an F(6,3) gradient against the F(4,3) kernel's on the same operands: 1e-4 of the tensor's magnitude"""
+    err = float((got - want).abs().max()) / float(want.abs().max())
+    assert err < 1e-4, (what, err)
+
+
 # ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,Cin,Cout,bias", [(300, 32, 64, False), (1568, 1024, 27, True), (130, 16, 16, True), (1568, 1024, 24, True),
                                              (6272, 512, 512, False),                                        # split-K forward
@@ -190,10 +217,8 @@ def test_winograd_transforms_with_folded_batchnorm(N, H, W, C):
                    X.ptr(mm), X.ptr(mv), N * H * W, C, *ws(), st)
         outs.append([t.cpu().numpy() for t in (mean, var, sc, sh, mm, mv)])
     assert torch.equal(y, y_ref)
-    for a, b, name in zip(outs[0], outs[1], ("mean", "var", "scale", "shift", "moving_mean", "moving_var")):
-        assert np.abs(a - b).max() <= 2e-6 * max(1.0, np.abs(a).max()), name
-    ym = y_ref.cpu().numpy().astype(np.float64)
-    assert np.abs(outs[1][0] - ym.mean(0)).max() < 1e-5 and np.abs(outs[1][1] - ym.var(0)).max() < 1e-4 * max(1.0, ym.var(0).max())
+    check_stats_agree(outs[1], outs[0])
+    check_mean_var_float64(outs[1][0], outs[1][1], y_ref)
     # (b)
     sc, sh = dt(outs[1][2]), dt(outs[1][3])
     a = new(N * H * W, C)
@@ -1091,8 +1116,7 @@ def test_winograd_f63_conv1_pieces():
         torch.cuda.synchronize()
         outs.append([t.clone() for t in (y, mean, var, sc, sh, mm, mv)])
     assert torch.equal(outs[0][0], outs[1][0])
-    for t0, t1 in zip(outs[0][1:], outs[1][1:]):
-        assert float((t0 - t1).abs().max()) <= 2e-6 * max(1.0, float(t1.abs().max()))
+    check_stats_agree(outs[0][1:], outs[1][1:])
     y_pre, sc, sh = outs[0][0], outs[0][3], outs[0][4]
     # (c), (d): gradients behind that BN with a row-sparse upstream gradient, against the F(4,3) kernels on the same operands
     npos = 5
@@ -1115,8 +1139,7 @@ def test_winograd_f63_conv1_pieces():
     X.call("myolo_wino63_bwd_data_lazybn", *lazy, X.ptr(w_t), X.ptr(dx63), nb, C, Co, *wsa, st)
     torch.cuda.synchronize()
     for got, want, what in ((dw63, dw43, "dw"), (dx63, dx43, "dx")):
-        err = float((got - want).abs().max()) / float(want.abs().max())
-        assert err < 1e-4, (what, err)
+        check_f63_equals_f43(got, want, what)
     # (e) the merged form the engine uses: ONE kernel sends the lazily formed gradient out as V and as Q, the two gradients finish separately
     pe = X.wino63_plane_elems(nb, Co)
     Vd, Qd = new(pe), new(pe)
