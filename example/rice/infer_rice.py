@@ -1,0 +1,56 @@
+#!/usr/bin/env python
+"""Run a trained Mask-YOLO over a folder of photographs on one MI355X -- the inference counterpart of train_rice.py.  The photographs go to
+MaskYOLO.detect_many as they are, whatever their sizes: they are resized to the network frame on the device and the boxes and masks come back
+in each photograph's own frame.
+
+  python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame]
+"""
+import argparse
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
+import numpy as np                                   # noqa: E402
+from myolo.config import RiceConfig, make_config     # noqa: E402
+from myolo.model import MaskYOLO                     # noqa: E402
+
+
+def load_rgb(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("weights", help="weights saved by train_rice.py (mask_yolo_rice_final.npz)")
+    ap.add_argument("images", help="directory of .jpg / .jpeg / .png photographs, of any sizes")
+    ap.add_argument("--size", type=int, default=224, help="the network frame the weights were trained at")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--threshold", type=float, default=0.35)
+    ap.add_argument("--network-frame", action="store_true", help="report boxes and masks in the network frame (cheap for large photographs)")
+    a = ap.parse_args()
+
+    paths = sorted(p for ext in ("jpg", "jpeg", "png", "JPG", "JPEG", "PNG") for p in glob.glob(os.path.join(a.images, "*." + ext)))
+    if not paths:
+        raise SystemExit("no .jpg / .jpeg / .png file in %s" % a.images)
+    config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
+    model = MaskYOLO(mode="inference", config=config)
+    model.load_weights(a.weights)
+    total = 0
+    for lo in range(0, len(paths), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
+        chunk = paths[lo:lo + 8 * a.batch]
+        results = model.detect_many([load_rgb(p) for p in chunk], cs_threshold=a.threshold,
+                                    mask_frame="network" if a.network_frame else "image")
+        for p, r in zip(chunk, results):
+            n = len(r["class_ids"])
+            total += n
+            print("%s: %d (mask frame %d x %d%s)" % (os.path.basename(p), n, r["full_masks"].shape[0], r["full_masks"].shape[1],
+                                                      "".join(", %.2f" % s for s in r["confidence_scores"])))
+    print("%d detections in %d images" % (total, len(paths)))
+
+
+if __name__ == "__main__":
+    main()

@@ -336,6 +336,21 @@ int myolo_polygon_masks(const double* verts,      /* [n_total,2] (row, col), sou
                         uint8_t* masks,           /* [B,H,W,T] 0/1, EVERY element written */
                         int B, int H, int W, int T, void* stream);
 
+/* ---- inference input of any size (MaskYOLO.detect / detect_many, csrc/resize_kernels.hip; arithmetic contract: DESIGN.md section 14).  Declared here
+ * rather than in the operator API (myolo_hip.h, held to 70 entries).  B uint8 [h,w,3] images of mixed sizes, packed back to back in src at ANY byte
+ * offset, resized to the network frame: per image and channel myolo_utils.resize(image, (H, W), preserve_range=True).astype(uint8) in binary64 --
+ * pixel centres aligned, taps floor / ceil, a tap outside the source reads 0, clipped to the minimum / maximum byte of the whole source image --
+ * bit for bit; out_unit = (float)((double)u8 / 255.), as myolo_u8_to_unit_f32 forms it.  Two launches: per-image min / max, then the samples.
+ * MYOLO_EINVAL (message "resize_images: ...") for a null pointer, B, H, W <= 0, h or w < 1, an image that does not lie inside src_bytes (read from
+ * desc_host before anything is launched) and a workspace under myolo_resize_images_ws_bytes(B). */
+size_t myolo_resize_images_ws_bytes(int B);
+int myolo_resize_images_u8(const uint8_t* src, size_t src_bytes,
+                           const int64_t* desc,      /* device [B,3]: byte offset into src, h, w of image b ([h,w,3] uint8, dense) */
+                           const int64_t* desc_host, /* the same values in host memory */
+                           uint8_t* out_u8,          /* [B,H,W,3] or NULL */
+                           float* out_unit,          /* [B,H,W,3] or NULL; at least one of the two */
+                           int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,39 @@ def resnet_check_size(n_images, h, w, n_box):
         raise ValueError("BACKBONE='resnet50': %d images of %dx%d with N_BOX=%d give %d mask-head ROIs per launch; only up to %d are supported "
                          "(larger launches have not been audited against the kernels' 32-bit buffer descriptors)"
                          % (n_images, h, w, n_box, rois, RESNET_MAX_MASK_ROIS))
+
+
+def packed_bytes(images, n_slots=None):
+    """bytes pack_images needs for these images: the [n_slots,3] int64 descriptor, then every image's h * w * 3 bytes back to back"""
+    n = len(images) if n_slots is None else int(n_slots)
+    return n * 24 + sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images)
+
+
+def pack_images(images, out, n_slots=None):
+    """Pack uint8 [h,w,3] images of mixed sizes into the byte array `out` the way myolo_resize_images_u8 reads them: out[:n_slots * 24] holds the
+    descriptor, int64 [n_slots,3] = (byte offset of the image behind the descriptor, h, w), and the images follow back to back with no padding
+    (an image starts wherever the one before ended).  Slots beyond len(images) name the last image again.  -> the descriptor (a host copy)."""
+    n = len(images) if n_slots is None else int(n_slots)
+    if not images or n < len(images):
+        raise ValueError("pack_images: %d images for %d slots" % (len(images), n))
+    desc = np.empty((n, 3), np.int64)
+    o = 0
+    for k, im in enumerate(images):
+        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("pack_images: image %d is %s %s; uint8 [h,w,3] expected" % (k, im.dtype, tuple(im.shape)))
+        desc[k] = (o, im.shape[0], im.shape[1])
+        o += im.shape[0] * im.shape[1] * 3
+    desc[len(images):] = desc[len(images) - 1]
+    head = n * 24
+    if out.dtype != np.uint8 or out.ndim != 1 or out.size < head + o:
+        raise ValueError("pack_images: out must be a flat uint8 array of at least %d bytes" % (head + o))
+    out[:head].view(np.int64)[:] = desc.reshape(-1)
+    for k, im in enumerate(images):
+        lo = head + int(desc[k, 0])
+        np.copyto(out[lo:lo + im.size].reshape(im.shape), im)
+    return desc
+
+
 # classes above this take the mask loss / 1x1 backward that carry only the selected class's logit gradient (myolo_mask_bce_sel,
 # myolo_mask_head_out_bwd_sel: dz_sel [rows] + the class ids in place of a dense dz [rows, C]); up to it, the dense kernels
 MASK_DENSE_MAX_CLASSES = 8
@@ -465,6 +498,8 @@ class Net(object):
                 self.bnbuf[name] = torch.zeros(4, shp, **f32)        # mean, var, scale, shift
         self._graphs = {}                 # predict_graphed: (input shape, modes, lane) -> (hipGraph, static input, static outputs)
         self._lanes = {}                  # predict_stream: lane -> its stream / scratch / coefficient buffers
+        self._resize_stage = None         # resize_to_frame: its own pinned staging buffer (grow-only) and the event of the last upload from it
+        self._resize_stage_ev = None
         self._cap_stream = None           # graph capture never happens with the default stream current (see _capture_predict)
         self._fm_stream = None            # inference: feature_map's conv beside the YOLO head (trunk_fwd)
         self.infer_fork_feature_map = False   # opt-in, and then only forwards that run alone: measured +0.0-0.5 % alone, -9 % with several batches in flight (forked graphs, 1150 -> 1055 img/s at Rice-416); and the extra stream it brings into a process moved the lanes' hardware-queue mapping in the full bench run (three lanes 1152 -> 1086)
@@ -2596,6 +2631,41 @@ class Net(object):
             pending.append((ev, outs))
         while pending:
             yield hand_out()
+
+    def resize_to_frame(self, images, want_u8=False, n_slots=None, stage=None):
+        """A list of uint8 [h,w,3] arrays of MIXED sizes -> the float32 [n,H,W,3] device tensor the forward takes (H, W of cfg.IMAGE_SHAPE):
+        myolo_utils.resize_image of every image, then / 255., bit for bit, computed on the device from the uploaded bytes (myolo_resize_images_u8,
+        DESIGN.md section 14).  The images are packed back to back behind their descriptor in ONE pinned staging buffer (pack_images) that goes
+        up in one asynchronous copy.  want_u8: -> (float32 tensor, the uint8 [n,H,W,3] one).  n_slots > len(images): the tensor has n_slots images,
+        the last one repeated (a descriptor, not a copy).  stage: a pinned uint8 tensor of >= packed_bytes(images, n_slots) bytes that the caller
+        keeps off-limits until the work queued here has run (detect_many's ring); without one, the Net's own grow-only buffer, waited on here."""
+        images = list(images)
+        n = len(images) if n_slots is None else int(n_slots)
+        need = packed_bytes(images, n)
+        if stage is None:
+            if self._resize_stage is None or self._resize_stage.numel() < need:
+                self._resize_stage = torch.empty(max(need, 1 << 20), dtype=torch.uint8).pin_memory()
+            elif self._resize_stage_ev is not None:
+                self._resize_stage_ev.synchronize()          # the previous call's upload has left the buffer
+            stage = self._resize_stage
+            own = True
+        else:
+            own = False
+            if stage.is_cuda or stage.dtype != torch.uint8 or stage.numel() < need:
+                raise ValueError("resize_to_frame: stage must be a host uint8 tensor of at least %d bytes" % need)
+        desc = pack_images(images, stage.numpy(), n)
+        H, W = int(self.cfg.IMAGE_SHAPE[0]), int(self.cfg.IMAGE_SHAPE[1])
+        packed = stage[:need].to(self.dev, non_blocking=True)
+        if own:
+            self._resize_stage_ev = torch.cuda.Event()
+            self._resize_stage_ev.record()
+        head = desc.size * 8                                  # the descriptor leads the buffer: the image bytes start behind it
+        x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
+        u8 = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.dev) if want_u8 else None
+        ws = torch.empty(2 * n, dtype=torch.int32, device=self.dev)
+        X.call("myolo_resize_images_u8", packed.data_ptr() + head, need - head, packed.data_ptr(), desc.ctypes.data, X.ptr(u8), X.ptr(x),
+               n, H, W, ws.data_ptr(), ws.numel() * 4, X.stream())
+        return (x, u8) if want_u8 else x
 
     def overlap_counts(self, det_d, mask_d, sel, gt_masks):
         """Pixel overlaps of the pasted masks of selected detections with ground-truth planes, counted on the device

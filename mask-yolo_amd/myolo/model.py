@@ -626,20 +626,34 @@ class MaskYOLO(object):
         return mutils.decode_one_yolo_output(netout[0], anchors=cfg.ANCHORS, nms_threshold=0.3, obj_threshold=0.35,
                                              nb_class=cfg.NUM_CLASSES)
 
-    def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False):
-        """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ]."""
+    @staticmethod
+    def _check_frame(images, mask_frame):
+        if mask_frame not in ("image", "network"):
+            raise ValueError("mask_frame must be 'image' or 'network' (got %r)" % (mask_frame,))
+        for im in images:
+            assert im.dtype == 'uint8' and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] >= 1 and im.shape[1] >= 1, \
+                "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
+
+    def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image"):
+        """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ].  An image of another size than config.IMAGE_SHAPE
+        is resized to it on the device (Net.resize_to_frame: myolo_utils.resize_image's result, bit for bit) and reported in
+        the frame mask_frame names: "image" -- bboxes in pixels of the image given, full_masks [h,w,n] pasted at that size -- or "network" --
+        both in the IMAGE_SHAPE frame, as detect(resize_image(image, IMAGE_SHAPE)[0]) gives them."""
         cfg = self.config
-        assert list(image.shape) == list(cfg.IMAGE_SHAPE)
-        assert image.dtype == 'uint8'
+        self._check_frame([image], mask_frame)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
-        # (image / 255.).astype(float32) formed on the device from the uploaded bytes (myolo_u8_to_unit_f32: the float32 of the float64 quotient, as numpy
-        # forms it on the host) -- bit-identical, a quarter of the bytes over PCIe and no 4 MB float64 temporary on the host (see detect_many)
         from . import _ext as X
-        raw = torch.from_numpy(np.ascontiguousarray(image)).to(self.net.dev)
-        x = torch.empty((1,) + tuple(raw.shape), dtype=torch.float32, device=self.net.dev)
-        X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
+        if list(image.shape) == list(cfg.IMAGE_SHAPE):
+            # (image / 255.).astype(float32) formed on the device from the uploaded bytes (myolo_u8_to_unit_f32: the float32 of the float64 quotient, as numpy
+            # forms it on the host) -- bit-identical, a quarter of the bytes over PCIe and no 4 MB float64 temporary on the host (see detect_many)
+            raw = torch.from_numpy(np.ascontiguousarray(image)).to(self.net.dev)
+            x = torch.empty((1,) + tuple(raw.shape), dtype=torch.float32, device=self.net.dev)
+            X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
+        else:
+            x = self.net.resize_to_frame([image])
+        frame = image.shape if mask_frame == "image" else cfg.IMAGE_SHAPE
         selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
         if selected_only:
             yolo_output, det_d, feature = self.net.predict_detections(x)   # the mask head runs below, on the survivors only
@@ -647,37 +661,55 @@ class MaskYOLO(object):
         else:
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
             yolo_output, det_d, mask_d = predict(x)                        # device tensors
-        return [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], image.shape, cs_threshold,
+        return [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], frame, cs_threshold,
                                         feature=feature if selected_only else None)]
 
-    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3):
+    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image"):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
         config.BATCH_SIZE with `in_flight` batches running at once (one stream / hipGraph / scratch per lane: the launch-bound trunk of one
         batch under the matrix-pipe-bound mask head of another), and every image gets detect()'s own selection and unmolding
-        (model.py:1238-1328).  Returns one result dict per image, equal to detect(image)[0]."""
+        (model.py:1238-1328).  The images may have any sizes, mixed in one call: a batch whose images are all at config.IMAGE_SHAPE goes up as its
+        bytes, any other batch is resized on the device (Net.resize_to_frame).  Returns one result dict per image, equal to
+        detect(image, mask_frame=mask_frame)[0]."""
         cfg = self.config
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
         images = list(images)
-        for im in images:
-            assert list(im.shape) == list(cfg.IMAGE_SHAPE) and im.dtype == 'uint8'
+        self._check_frame(images, mask_frame)
         B = int(cfg.BATCH_SIZE)
         dev = self.net.dev
+        groups = [images[lo:lo + B] for lo in range(0, len(images), B)]
+        at_frame = [all(list(im.shape) == list(cfg.IMAGE_SHAPE) for im in grp) for grp in groups]
 
         from . import _ext as X
+        from .engine import packed_bytes
         # the bytes go up as they are (a quarter of the float32 image) from a ring of pinned buffers, and (image / 255.).astype(float32) is formed on the
         # device (myolo_u8_to_unit_f32: the float32 of the float64 quotient, which is what numpy does on the host) -- bit-identical to detect()'s input (the host
         # normalisation + pageable upload of 8 MB per batch of four 416 x 416 images cost 2.3 ms per batch, more than half the forward)
-        key = (B, tuple(cfg.IMAGE_SHAPE), 2 * in_flight + 2)
-        if getattr(self, "_stage_ring_key", None) != key:            # (pinning costs ~5 ms per buffer: once per model, not once per call)
-            self._stage_ring = [torch.empty((B,) + tuple(cfg.IMAGE_SHAPE), dtype=torch.uint8).pin_memory() for _ in range(key[2])]
-            self._stage_ring_key = key
-        ring = self._stage_ring
+        nring = 2 * in_flight + 2
+        ring = rring = None
+        if any(at_frame):
+            key = (B, tuple(cfg.IMAGE_SHAPE), nring)
+            if getattr(self, "_stage_ring_key", None) != key:            # (pinning costs ~5 ms per buffer: once per model, not once per call)
+                self._stage_ring = [torch.empty((B,) + tuple(cfg.IMAGE_SHAPE), dtype=torch.uint8).pin_memory() for _ in range(key[2])]
+                self._stage_ring_key = key
+            ring = self._stage_ring
+        if not all(at_frame):
+            # the ring of the resized batches: flat buffers sized once per call to the largest packed batch, kept while they are large enough
+            need = max(packed_bytes(grp, B) for grp, ok in zip(groups, at_frame) if not ok)
+            rkey = getattr(self, "_resize_ring_key", None)
+            if rkey is None or rkey[0] < need or rkey[1] != nring:
+                self._resize_ring = [torch.empty(need, dtype=torch.uint8).pin_memory() for _ in range(nring)]
+                self._resize_ring_key = (need, nring)
+            rring = self._resize_ring
 
         def batches():
-            for bi, lo in enumerate(range(0, len(images), B)):
-                grp = images[lo:lo + B]
+            for bi, grp in enumerate(groups):
+                if not at_frame[bi]:
+                    # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out; a short last batch repeats its last image)
+                    yield self.net.resize_to_frame(grp, n_slots=B, stage=rring[bi % nring])
+                    continue
                 grp = grp + [grp[-1]] * (B - len(grp))                       # a short last batch is padded (the captured graph has one shape)
                 stage = ring[bi % len(ring)]             # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out)
                 np.stack(grp, out=stage.numpy())
@@ -689,7 +721,8 @@ class MaskYOLO(object):
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
             det_all = det_d.cpu().numpy()
             for k in range(min(B, len(images) - bi * B)):
-                out.append(self._select_and_unmold(det_d[k], mask_d[k], images[bi * B + k].shape, cs_threshold, det_host=det_all[k]))
+                frame = images[bi * B + k].shape if mask_frame == "image" else cfg.IMAGE_SHAPE
+                out.append(self._select_and_unmold(det_d[k], mask_d[k], frame, cs_threshold, det_host=det_all[k]))
         return out
         # (one unmold launch and one download per BATCH instead of per image was measured: 514 img/s against 865 -- a pageable 6.9 MB download runs at
         # 2 GB/s where four of 1.7 MB do not, and cutting the H x W x 40 block into per-image H x W x n arrays costs the host another 0.5 ms per image)
