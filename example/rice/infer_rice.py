@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """Run a trained Mask-YOLO over a folder of photographs on one MI355X -- the inference counterpart of train_rice.py.  The photographs go to
 MaskYOLO.detect_many as they are, whatever their sizes: they are resized to the network frame on the device and the boxes and masks come back
-in each photograph's own frame.
+in each photograph's own frame.  With --coco-json the masks are asked for as COCO run-length codes (encoded on the device,
+DESIGN section 15: no dense mask is written or downloaded) and every detection goes into one COCO results file.
 
-  python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame]
+  python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame] [--coco-json PATH]
 """
 import argparse
 import glob
+import json
 import os
 import sys
 
@@ -15,6 +17,7 @@ sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 import numpy as np                                   # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
+from myolo import rle                                # noqa: E402
 
 
 def load_rgb(path):
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--threshold", type=float, default=0.35)
     ap.add_argument("--network-frame", action="store_true", help="report boxes and masks in the network frame (cheap for large photographs)")
+    ap.add_argument("--coco-json", metavar="PATH", help="write the detections as a COCO results file (image_id = the file's name without extension)")
     a = ap.parse_args()
 
     paths = sorted(p for ext in ("jpg", "jpeg", "png", "JPG", "JPEG", "PNG") for p in glob.glob(os.path.join(a.images, "*." + ext)))
@@ -39,17 +43,26 @@ def main():
     config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
     model = MaskYOLO(mode="inference", config=config)
     model.load_weights(a.weights)
-    total = 0
+    total, coco = 0, []
     for lo in range(0, len(paths), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
         chunk = paths[lo:lo + 8 * a.batch]
         results = model.detect_many([load_rgb(p) for p in chunk], cs_threshold=a.threshold,
-                                    mask_frame="network" if a.network_frame else "image")
+                                    mask_frame="network" if a.network_frame else "image", mask_format="rle" if a.coco_json else "dense")
+        if a.coco_json:
+            coco += rle.coco_results(results, [os.path.splitext(os.path.basename(p))[0] for p in chunk])
         for p, r in zip(chunk, results):
             n = len(r["class_ids"])
             total += n
-            print("%s: %d (mask frame %d x %d%s)" % (os.path.basename(p), n, r["full_masks"].shape[0], r["full_masks"].shape[1],
-                                                      "".join(", %.2f" % s for s in r["confidence_scores"])))
+            if "full_masks" in r:
+                fh, fw = r["full_masks"].shape[:2]
+            else:
+                fh, fw = r["rle_masks"][0]["size"] if n else (0, 0)
+            print("%s: %d (mask frame %d x %d%s)" % (os.path.basename(p), n, fh, fw, "".join(", %.2f" % s for s in r["confidence_scores"])))
     print("%d detections in %d images" % (total, len(paths)))
+    if a.coco_json:
+        with open(a.coco_json, "w") as f:
+            json.dump(coco, f)
+        print("wrote %s" % a.coco_json)
 
 
 if __name__ == "__main__":

@@ -306,6 +306,25 @@ int myolo_mask_overlap_counts(const float* masks, const float* det, const int32_
                               int32_t* inter, int32_t* area_pred, int32_t* area_gt, int32_t* win, int B, int R, int K, int T, int mh, int mw,
                               int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection masks as run-length codes (myolo/rle.py, MaskYOLO.detect(mask_format="rle"); format and kernels: DESIGN.md section 15): the PASTED
+ * masks of selected detections -- the paste of myolo_unmold_masks, the same device function, pixel for pixel -- as the boundaries of COCO's
+ * run-length form, without writing or downloading a full-size mask.  Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).
+ * masks, det, sel, sel_host as myolo_mask_overlap_counts takes them (K <= 16, sel < 0 = empty slot, a value >= R refused); frames [B,2] int32 =
+ * (h, w) of image b's output frame, on the device and (frames_host) in host memory: every image has its own.  sel_host and frames_host are read
+ * before anything is launched.
+ * With the pixels of a mask in column-major order, p = x * h + y, a boundary is every p in [0, h * w) whose pixel differs from pixel p - 1 (pixel -1
+ * counts as 0): bounds[run_off[s] .. run_off[s + 1]) are the boundaries of slot s = b * K + k, ascending (positions, not lengths: COCO's counts are
+ * diff([0, boundaries..., h * w])); an empty slot has none.  run_off [B*K+1] is always written in full; nothing is written at or beyond
+ * bounds + cap, so a caller that finds run_off[B*K] > cap grows its buffer and calls again.  Integer work only: bit-identical from run to run.
+ * MYOLO_EINVAL (message "rle_masks: ...", nothing written) for a null pointer, K > 16, h or w < 1, h * w >= 2^31, sel >= R, and a workspace under
+ * myolo_rle_masks_ws_bytes(B, K, max_w), max_w = the widest frame of the call (a workspace planned for narrower frames is refused). */
+size_t myolo_rle_masks_ws_bytes(int B, int K, int max_w);
+int myolo_rle_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,R,6]*/,
+                    const int32_t* sel /*[B,K] device, <0 = empty*/, const int32_t* sel_host,
+                    const int32_t* frames /*[B,2] device: h, w of image b's output frame*/, const int32_t* frames_host,
+                    int32_t* run_off /*[B*K+1]*/, uint32_t* bounds /*[cap]*/, int64_t cap,
+                    int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- on-device training augmentation (myolo/augment.py, csrc/augment_kernels.hip; arithmetic contract: DESIGN.md "On-device augmentation").
  * Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).  Per image b one row of params: the INVERSE affine map
  * (output pixel -> source position, pixel-centre convention baked into m02 / m12), then gain and bias of the byte values.  The image is sampled

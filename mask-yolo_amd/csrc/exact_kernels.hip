@@ -555,6 +555,113 @@ __global__ __launch_bounds__(256) void mask_overlap_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------
+// Run-length form of the pasted masks (myolo/rle.py): for every image b (its own output frame h x w, frames [B][2]) and
+// selected detection k, the BOUNDARIES of the pasted mask in COCO's column-major pixel order p = x * h + y: every p in [0, h * w) whose pixel
+// differs from pixel p - 1 (pixel -1 = 0).  A pixel is unmold_pixel -- the byte unmold_kernel would write -- so the runs are the dense paste's
+// by construction; no full-size mask is written.
+// Outside the paste window every pixel is 0, so a boundary has p or p - 1 inside it.  One wave owns one window column x and walks the rows
+// ya .. yb (rle_column_rows) 64 at a time: a ballot of the 64 pixels, XOR with itself shifted by one (the carried last pixel of the previous
+// group coming in at bit 0) gives the boundaries, a popcount their number, the popcount below a lane its boundary's rank.  The pixel before a
+// column's first row is pixel p - 1: the last row of the column to the left when the window starts at row 0 (a run goes on across the column
+// joint without a boundary), 0 otherwise.  rle_columns_kernel<false> leaves the number of boundaries of column x of slot s in
+// cols [s][max_w]; rle_scan_columns_kernel scans every slot's row in place and leaves the slot's total in run_off [s], rle_scan_slots_kernel
+// scans those; rle_columns_kernel<true> walks again and stores each boundary at run_off[s] + cols[s][x] + rank -- when that lies below cap.
+// Integer work only: bit-identical from run to run.
+// ---------------------------------------------------------------------------------------
+// the rows ya .. yb (both included) of window column x that the column's wave owns; row H stands for row 0 of column x + 1, the pixel behind the
+// column's last one.  That pixel belongs to column x + 1's wave when the window has that column and starts at row 0, and to nobody when it is
+// pixel H * W.  false: x is no column of the window (or the window holds no pixel).
+__device__ __forceinline__ bool rle_column_rows(const float* __restrict__ d, int H, int W, int x, int& ya, int& yb)
+{
+    int x1, y1, x2, y2;
+    unmold_window(d, H, W, x1, y1, x2, y2);
+    if (x < x1 || x >= x2 || y1 >= y2) return false;
+    ya = y1, yb = y2;
+    if (y2 == H && ((y1 == 0 && x + 1 < x2) || x + 1 == W)) yb = H - 1;
+    return true;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void rle_columns_kernel(const float* __restrict__ masks, const float* __restrict__ det,
+                                                          const int32_t* __restrict__ sel, const int32_t* __restrict__ allhigh,
+                                                          const int32_t* __restrict__ frames, int32_t* __restrict__ cols,
+                                                          const int32_t* __restrict__ run_off, uint32_t* __restrict__ bounds, long long cap,
+                                                          int R, int K, int mh, int mw, int C, int max_w)
+{
+    const int lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 4 + (threadIdx.x >> 6);            // one column per wave: everything below is uniform over the wave
+    const int slot = blockIdx.y, b = slot / K;
+    if (x >= max_w) return;
+    const int s = sel[slot];
+    const int H = frames[2 * b], W = frames[2 * b + 1];
+    const long long row = (long long)b * R + max(s, 0);
+    const float* d = det + row * 6;
+    int ya = 0, yb = -1;
+    if (!(s >= 0 && s < R && x < W && rle_column_rows(d, H, W, x, ya, yb))) {
+        if (!WRITE && lane == 0) cols[(long long)slot * max_w + x] = 0;
+        return;
+    }
+    const float* m0 = masks + row * mh * mw * C;
+    const int ah = allhigh[slot];
+    unsigned long long carry = (ya == 0 && x > 0) ? unmold_pixel(d, m0, ah, x - 1, H - 1, mh, mw, C, H, W) : 0;
+    const long long base = WRITE ? (long long)run_off[slot] + cols[(long long)slot * max_w + x] : 0;
+    int n = 0;
+    for (int y0 = ya; y0 <= yb; y0 += 64) {
+        const int y = y0 + lane;
+        const bool in = y <= yb;
+        int v = 0;
+        if (in) v = (y < H) ? unmold_pixel(d, m0, ah, x, y, mh, mw, C, H, W) : unmold_pixel(d, m0, ah, x + 1, 0, mh, mw, C, H, W);
+        const unsigned long long bits = __ballot(v), valid = __ballot(in);
+        const unsigned long long bnd = (bits ^ ((bits << 1) | carry)) & valid;
+        carry = bits >> 63;
+        if (WRITE && ((bnd >> lane) & 1ull)) {
+            const long long at = base + n + __popcll(bnd & ((1ull << lane) - 1ull));
+            if (at < cap) bounds[at] = (uint32_t)(x * H + y);
+        }
+        n += __popcll(bnd);
+    }
+    if (!WRITE && lane == 0) cols[(long long)slot * max_w + x] = n;
+}
+
+// a [0, n) -> its exclusive prefix sums, in place, by one workgroup of 256; -> the total (in every thread)
+__device__ __forceinline__ int rle_scan_in_place(int32_t* __restrict__ a, int n)
+{
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int carry = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const int v = i < n ? a[i] : 0;
+        int inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int off = carry;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        if (i < n) a[i] = off + inc - v;
+        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    return carry;
+}
+
+__global__ __launch_bounds__(256) void rle_scan_columns_kernel(int32_t* __restrict__ cols, int32_t* __restrict__ run_off, int max_w)
+{
+    const int total = rle_scan_in_place(cols + (long long)blockIdx.x * max_w, max_w);
+    if (threadIdx.x == 0) run_off[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void rle_scan_slots_kernel(int32_t* __restrict__ run_off, int nslots)
+{
+    const int total = rle_scan_in_place(run_off, nslots);
+    if (threadIdx.x == 0) run_off[nslots] = total;
+}
+
+// ---------------------------------------------------------------------------------------
 // GPU producer of the Shapes input pipeline: rasterise the images and instance masks
 // of a batch from their shape specifications (example/shapes/dataset_shapes.py:80-135: load_image / load_mask /
 // draw_shape incl. the occlusion rule :112-116), drop empty instances and take tight boxes (load_image_gt + extract_bboxes,
@@ -770,6 +877,51 @@ int myolo_mask_overlap_counts(const float* masks, const float* det, const int32_
     hipLaunchKernelGGL(mask_overlap_kernel, dim3((ngroups + OV_GROUPS - 1) / OV_GROUPS, B), dim3(256), 0, s, masks, det, sel,
                        (const int32_t*)allhigh, gt_masks, inter, area_pred, area_gt, win, R, K, T, mh, mw, C, H, W,
                        ((uintptr_t)gt_masks & 15) == 0 ? 1 : 0);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+// the B * K all-high flags, then the B * K rows of max_w column counts
+size_t myolo_rle_masks_ws_bytes(int B, int K, int max_w)
+{
+    if (B <= 0 || K <= 0 || max_w <= 0) return 0;
+    const size_t words = (size_t)B * K * ((size_t)max_w + 1);
+    return (words * sizeof(int32_t) + 255) / 256 * 256;
+}
+
+int myolo_rle_masks(const float* masks, const float* det, const int32_t* sel, const int32_t* sel_host, const int32_t* frames,
+                    const int32_t* frames_host, int32_t* run_off, uint32_t* bounds, int64_t cap, int B, int R, int K, int mh, int mw, int C,
+                    void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(masks && det && sel && sel_host && frames && frames_host && run_off && bounds && ws, "rle_masks: null pointer");
+    MYOLO_REQUIRE(B > 0 && R > 0 && mh > 0 && mw > 0 && C > 0 && cap >= 0, "rle_masks: bad sizes");
+    MYOLO_REQUIRE(K > 0 && K <= OV_MAXK, "rle_masks: need 1 <= K <= %d (got K=%d)", OV_MAXK, K);
+    MYOLO_REQUIRE((long long)B * K <= 65535, "rle_masks: B * K = %lld slots, more than the 65535 of one launch", (long long)B * K);
+    int max_w = 0;
+    long long pixels = 0;                                          // an upper bound of the boundaries of all slots: run_off is 32-bit
+    for (int b = 0; b < B; ++b) {
+        const int h = frames_host[2 * b], w = frames_host[2 * b + 1];
+        MYOLO_REQUIRE(h >= 1 && w >= 1, "rle_masks: frame %d is %d x %d (h, w >= 1 needed)", b, h, w);
+        MYOLO_REQUIRE((long long)h * w < (1ll << 31), "rle_masks: frame %d (%d x %d) has 2^31 pixels or more", b, h, w);
+        pixels += (long long)h * w * K;
+        max_w = w > max_w ? w : max_w;
+    }
+    MYOLO_REQUIRE(pixels < (1ll << 31), "rle_masks: the frames of the batch hold %lld pixels x slots, 2^31 or more", pixels);
+    for (long long i = 0; i < (long long)B * K; ++i)
+        MYOLO_REQUIRE(sel_host[i] < R, "rle_masks: sel[%lld] = %d is not a row of the %d detections", i, sel_host[i], R);
+    const size_t need = myolo_rle_masks_ws_bytes(B, K, max_w);
+    MYOLO_REQUIRE(ws_bytes >= need, "rle_masks: workspace too small (%zu needed for frames up to %d wide, %zu given)", need, max_w, ws_bytes);
+    int32_t* allhigh = (int32_t*)ws;
+    int32_t* cols = allhigh + (size_t)B * K;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((max_w + 3) / 4, B * K);
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(B * K), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
+    hipLaunchKernelGGL(rle_columns_kernel<false>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, cols,
+                       (const int32_t*)run_off, bounds, (long long)cap, R, K, mh, mw, C, max_w);
+    hipLaunchKernelGGL(rle_scan_columns_kernel, dim3(B * K), dim3(256), 0, s, cols, run_off, max_w);
+    hipLaunchKernelGGL(rle_scan_slots_kernel, dim3(1), dim3(256), 0, s, run_off, B * K);
+    hipLaunchKernelGGL(rle_columns_kernel<true>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, cols,
+                       (const int32_t*)run_off, bounds, (long long)cap, R, K, mh, mw, C, max_w);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

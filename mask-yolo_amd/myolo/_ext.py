@@ -135,6 +135,7 @@ SIGS = {
     "myolo_augment_batch": [P, P, P, P, D, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
     "myolo_polygon_masks": [P, P, P, P, P, I, I, I, I, P],
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
+    "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],
@@ -218,6 +219,8 @@ def load():
     lib.myolo_augment_batch_ws_bytes.restype = Z
     lib.myolo_resize_images_ws_bytes.argtypes = [I]
     lib.myolo_resize_images_ws_bytes.restype = Z
+    lib.myolo_rle_masks_ws_bytes.argtypes = [I, I, I]
+    lib.myolo_rle_masks_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
     lib.myolo_wprep_refresh.restype = I
     _LIB = lib
@@ -229,7 +232,8 @@ def exported_symbols():
                               "myolo_pwconv1x1_bnstats_ws_bytes", "myolo_pwconv1x1_bnstats_ok",
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
-                              "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_resize_images_ws_bytes"]
+                              "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_resize_images_ws_bytes",
+                              "myolo_rle_masks_ws_bytes"]
 
 
 def ptr(t):
@@ -440,6 +444,10 @@ def augment_ws_bytes(b, t):
 
 def resize_ws_bytes(b):
     return int(load().myolo_resize_images_ws_bytes(int(b)))
+
+
+def rle_masks_ws_bytes(b, k, max_w):
+    return int(load().myolo_rle_masks_ws_bytes(int(b), int(k), int(max_w)))
 
 
 def workspace_bytes(rows, cin, cout):

@@ -500,6 +500,8 @@ class Net(object):
         self._lanes = {}                  # predict_stream: lane -> its stream / scratch / coefficient buffers
         self._resize_stage = None         # resize_to_frame: its own pinned staging buffer (grow-only) and the event of the last upload from it
         self._resize_stage_ev = None
+        self._rle_bounds = None           # rle_masks: the device buffer of the boundaries (int32 words, grow-only) and its pinned host staging
+        self._rle_pin = None
         self._cap_stream = None           # graph capture never happens with the default stream current (see _capture_predict)
         self._fm_stream = None            # inference: feature_map's conv beside the YOLO head (trunk_fwd)
         self.infer_fork_feature_map = False   # opt-in, and then only forwards that run alone: measured +0.0-0.5 % alone, -9 % with several batches in flight (forked graphs, 1150 -> 1055 img/s at Rice-416); and the extra stream it brings into a process moved the lanes' hardware-queue mapping in the full bench run (three lanes 1152 -> 1086)
@@ -2694,6 +2696,55 @@ class Net(object):
                area_pred.data_ptr(), area_gt.data_ptr(), win.data_ptr(), B, R, K, T, mh, mw, C, H, W, scratch.data_ptr(), scratch.numel() * 4,
                X.stream())
         return inter.view(B, K, T), area_pred.view(B, K), area_gt.view(B, T), win.view(B, K, 4)
+
+    RLE_BOUNDS_START = 1 << 16            # rle_masks: first size of the boundary buffer, in boundaries (ten 416 x 416 masks hold a few thousand)
+
+    def rle_masks(self, det_d, mask_d, sel, frames):
+        """The pasted masks of selected detections as run boundaries of COCO's run-length form, encoded on the device (myolo_rle_masks,
+        include/myolo_hip_internal.h; the format: myolo/rle.py): det_d [B,R,6], mask_d [B,R,mh,mw,C] as predict returns them, sel [B,K] int32 in
+        HOST memory = rows of det_d per image, -1 = empty slot, K <= 16; frames [B,2] int32 in host memory = (h, w) of the frame image b's masks
+        are pasted into.  -> (run_off [B*K+1] int32, bounds [run_off[-1]] uint32) numpy arrays: bounds[run_off[s]:run_off[s+1]] are the boundaries
+        of slot s = b*K + k, and rle.counts_from_boundaries(those, h*w) its counts.
+        One upload (sel and frames together) and two small downloads: the offsets, then bounds[:total].  The boundaries land in ONE device buffer
+        per Net that only grows; when a batch holds more than it has room for, the entry has still written every offset, so the buffer is
+        enlarged to the total and the call repeated."""
+        sel_h = np.ascontiguousarray(sel.numpy() if torch.is_tensor(sel) else sel)
+        frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)
+        if sel_h.dtype != np.int32 or sel_h.ndim != 2 or frames_h.dtype != np.int32 or frames_h.ndim != 2:
+            raise ValueError("rle_masks: sel [B,K] and frames [B,2] must be int32 arrays in host memory")
+        det_d, mask_d = det_d.contiguous(), mask_d.contiguous()
+        B, R = int(det_d.shape[0]), int(det_d.shape[1])
+        K = int(sel_h.shape[1])
+        if (det_d.dtype != torch.float32 or mask_d.dtype != torch.float32 or mask_d.dim() != 5 or tuple(mask_d.shape[:2]) != (B, R)
+                or int(det_d.shape[2]) != 6 or int(sel_h.shape[0]) != B or tuple(frames_h.shape) != (B, 2)):
+            raise ValueError("rle_masks: det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32 expected")
+        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
+        nsel, nslot = B * K, B * K + 1
+        # host side: [sel | frames | run_off] in one pinned buffer (free again when this call returns: it ends with a synchronising download)
+        if self._rle_pin is None or self._rle_pin.numel() < nsel + 2 * B + nslot:
+            self._rle_pin = torch.empty(nsel + 2 * B + nslot, dtype=torch.int32).pin_memory()
+        pin = self._rle_pin
+        args_h, off_h = pin[:nsel + 2 * B], pin[nsel + 2 * B:nsel + 2 * B + nslot]
+        args_np = args_h.numpy()
+        args_np[:nsel], args_np[nsel:] = sel_h.reshape(-1), frames_h.reshape(-1)
+        args_d = args_h.to(self.dev, non_blocking=True)
+        ws_bytes = X.rle_masks_ws_bytes(B, K, max(int(frames_h[:, 1].max()), 1))
+        buf = torch.empty(nslot + ws_bytes // 4, dtype=torch.int32, device=self.dev)           # [run_off | workspace]
+        if self._rle_bounds is None:
+            self._rle_bounds = torch.empty(self.RLE_BOUNDS_START, dtype=torch.int32, device=self.dev)
+        while True:
+            bounds = self._rle_bounds
+            X.call("myolo_rle_masks", X.ptr(mask_d), X.ptr(det_d), args_d.data_ptr(), args_np.ctypes.data, args_d.data_ptr() + nsel * 4,
+                   args_np.ctypes.data + nsel * 4, buf.data_ptr(), bounds.data_ptr(), bounds.numel(), B, R, K, mh, mw, C,
+                   buf.data_ptr() + nslot * 4, ws_bytes, X.stream())
+            off_h.copy_(buf[:nslot], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            run_off = off_h.numpy().copy()
+            total = int(run_off[-1])
+            if total <= bounds.numel():
+                break
+            self._rle_bounds = torch.empty(max(total, 2 * bounds.numel()), dtype=torch.int32, device=self.dev)
+        return run_off, bounds[:total].cpu().numpy().view(np.uint32)
 
     def predict_yolo(self, images):
         """'yolo' mode forward (model.py:906-920)."""

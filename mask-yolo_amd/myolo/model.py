@@ -634,13 +634,19 @@ class MaskYOLO(object):
             assert im.dtype == 'uint8' and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] >= 1 and im.shape[1] >= 1, \
                 "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
 
-    def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image"):
+    def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image",
+               mask_format="dense"):
         """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ].  An image of another size than config.IMAGE_SHAPE
         is resized to it on the device (Net.resize_to_frame: myolo_utils.resize_image's result, bit for bit) and reported in
         the frame mask_frame names: "image" -- bboxes in pixels of the image given, full_masks [h,w,n] pasted at that size -- or "network" --
-        both in the IMAGE_SHAPE frame, as detect(resize_image(image, IMAGE_SHAPE)[0]) gives them."""
+        both in the IMAGE_SHAPE frame, as detect(resize_image(image, IMAGE_SHAPE)[0]) gives them.
+        mask_format="rle": instead of full_masks the dict has rle_masks, a list of COCO run-length dicts {"size": [h, w], "counts": int64 array}
+        (myolo/rle.py) in the order of class_ids, size = the frame mask_frame names; rle.decode of each is the full_masks plane bit for bit.  The
+        masks are encoded on the device (Net.rle_masks) and no dense mask is written or downloaded.  Not supported together
+        with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).  Any other mask_format raises ValueError."""
         cfg = self.config
         self._check_frame([image], mask_frame)
+        self._check_format(mask_format)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -655,6 +661,10 @@ class MaskYOLO(object):
             x = self.net.resize_to_frame([image])
         frame = image.shape if mask_frame == "image" else cfg.IMAGE_SHAPE
         selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
+        if mask_format == "rle":
+            predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
+            _, det_d, mask_d = predict(x)
+            return self._select_and_encode(det_d, mask_d, det_d.cpu().numpy(), [frame], cs_threshold)
         if selected_only:
             yolo_output, det_d, feature = self.net.predict_detections(x)   # the mask head runs below, on the survivors only
             mask_d = None
@@ -664,14 +674,18 @@ class MaskYOLO(object):
         return [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], frame, cs_threshold,
                                         feature=feature if selected_only else None)]
 
-    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image"):
+    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense"):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
         config.BATCH_SIZE with `in_flight` batches running at once (one stream / hipGraph / scratch per lane: the launch-bound trunk of one
         batch under the matrix-pipe-bound mask head of another), and every image gets detect()'s own selection and unmolding
         (model.py:1238-1328).  The images may have any sizes, mixed in one call: a batch whose images are all at config.IMAGE_SHAPE goes up as its
         bytes, any other batch is resized on the device (Net.resize_to_frame).  Returns one result dict per image, equal to
-        detect(image, mask_frame=mask_frame)[0]."""
+        detect(image, mask_frame=mask_frame)[0].
+        mask_format="rle" (see detect; ValueError with config.DETECT_MASKS_FOR_SELECTED_ONLY): rle_masks in place of full_masks, and the
+        post-processing runs once per BATCH -- the selection of all its images on the host from the one detection download, one [B, K] upload,
+        one Net.rle_masks call whose two downloads are a few KB -- where the dense form pastes and downloads per image."""
         cfg = self.config
+        self._check_format(mask_format)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -720,6 +734,11 @@ class MaskYOLO(object):
         out = []
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
             det_all = det_d.cpu().numpy()
+            if mask_format == "rle":
+                live = images[bi * B:(bi + 1) * B]
+                out += self._select_and_encode(det_d, mask_d, det_all, [im.shape if mask_frame == "image" else cfg.IMAGE_SHAPE for im in live],
+                                               cs_threshold)
+                continue
             for k in range(min(B, len(images) - bi * B)):
                 frame = images[bi * B + k].shape if mask_frame == "image" else cfg.IMAGE_SHAPE
                 out.append(self._select_and_unmold(det_d[k], mask_d[k], frame, cs_threshold, det_host=det_all[k]))
@@ -759,6 +778,38 @@ class MaskYOLO(object):
             "confidence_scores": scores[nmb],
             "full_masks": full_masks,
         }
+
+    def _check_format(self, mask_format):
+        if mask_format not in ("dense", "rle"):
+            raise ValueError("mask_format must be 'dense' or 'rle' (got %r)" % (mask_format,))
+        if mask_format == "rle" and bool(getattr(self.config, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
+            raise ValueError("mask_format='rle' is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
+
+    def _select_and_encode(self, det_d, mask_d, det_all, frames, cs_threshold):
+        """detect()'s post-processing of a BATCH in run-length form: det_d [B,R,6], mask_d [B,R,mh,mw,C] device tensors, det_all = det_d's host
+        copy, frames = the (h, w, ...) of the first len(frames) <= B images (the rest of the batch is padding).  -> their result dicts."""
+        from .rle import counts_from_boundaries
+        B, K, n = int(det_d.shape[0]), self.EVAL_SLOTS, len(frames)
+        sel = np.full((B, K), -1, np.int32)
+        fr = np.ones((B, 2), np.int32)                                   # (padding: no slot, a 1 x 1 frame)
+        picked = []
+        for k in range(n):
+            keep, nmb, boxes, scores, class_ids = self._select(det_all[k], cs_threshold)
+            sel[k, :len(nmb)] = keep[nmb]
+            fr[k] = (int(frames[k][0]), int(frames[k][1]))
+            picked.append((boxes[nmb], class_ids[nmb], scores[nmb]))
+        run_off, bounds = self.net.rle_masks(det_d, mask_d, sel, fr)
+        out = []
+        for k, (boxes, class_ids, scores) in enumerate(picked):
+            h, w = int(fr[k, 0]), int(fr[k, 1])
+            out.append({
+                "bboxes": boxes * np.array([float(w), float(h), float(w), float(h)], dtype=boxes.dtype),     # pixels (model.py:1307)
+                "class_ids": class_ids,
+                "confidence_scores": scores,
+                "rle_masks": [{"size": [h, w], "counts": counts_from_boundaries(bounds[run_off[s]:run_off[s + 1]], h * w)}
+                              for s in range(k * K, k * K + len(class_ids))],
+            })
+        return out
 
     def _select(self, det_h, cs_threshold):
         """detect()'s selection on the host copy det_h [R,6] of one image's detections (model.py:1290-1304, 1373-1380): drop the zero-area boxes,
