@@ -2,9 +2,11 @@
 """Run a trained Mask-YOLO over a folder of photographs on one MI355X -- the inference counterpart of train_rice.py.  The photographs go to
 MaskYOLO.detect_many as they are, whatever their sizes: they are resized to the network frame on the device and the boxes and masks come back
 in each photograph's own frame.  With --coco-json the masks are asked for as COCO run-length codes (encoded on the device,
-DESIGN section 15: no dense mask is written or downloaded) and every detection goes into one COCO results file.
+DESIGN section 15: no dense mask is written or downloaded) and every detection goes into one COCO results file.  With --render-dir every
+photograph's overlay -- masks, outlines and boxes drawn over it on the device -- is written there as <name>.png.
 
   python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame] [--coco-json PATH]
+                                    [--render-dir DIR]
 """
 import argparse
 import glob
@@ -17,7 +19,7 @@ sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 import numpy as np                                   # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
-from myolo import rle                                # noqa: E402
+from myolo import render, rle                        # noqa: E402
 
 
 def load_rgb(path):
@@ -35,7 +37,10 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.35)
     ap.add_argument("--network-frame", action="store_true", help="report boxes and masks in the network frame (cheap for large photographs)")
     ap.add_argument("--coco-json", metavar="PATH", help="write the detections as a COCO results file (image_id = the file's name without extension)")
+    ap.add_argument("--render-dir", metavar="DIR", help="write every photograph's overlay (masks, outlines, boxes) as DIR/<name>.png")
     a = ap.parse_args()
+    if a.render_dir and a.network_frame:
+        ap.error("--render-dir draws on the photograph given: it does not go with --network-frame")
 
     paths = sorted(p for ext in ("jpg", "jpeg", "png", "JPG", "JPEG", "PNG") for p in glob.glob(os.path.join(a.images, "*." + ext)))
     if not paths:
@@ -47,12 +52,15 @@ def main():
     for lo in range(0, len(paths), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
         chunk = paths[lo:lo + 8 * a.batch]
         results = model.detect_many([load_rgb(p) for p in chunk], cs_threshold=a.threshold,
-                                    mask_frame="network" if a.network_frame else "image", mask_format="rle" if a.coco_json else "dense")
+                                    mask_frame="network" if a.network_frame else "image", mask_format="rle" if a.coco_json or a.render_dir else "dense", render=bool(a.render_dir))
         if a.coco_json:
             coco += rle.coco_results(results, [os.path.splitext(os.path.basename(p))[0] for p in chunk])
         for p, r in zip(chunk, results):
             n = len(r["class_ids"])
             total += n
+            if a.render_dir:
+                os.makedirs(a.render_dir, exist_ok=True)
+                render.write_png(os.path.join(a.render_dir, os.path.splitext(os.path.basename(p))[0] + ".png"), r["rendered"])
             if "full_masks" in r:
                 fh, fw = r["full_masks"].shape[:2]
             else:

@@ -325,6 +325,28 @@ int myolo_rle_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,
                     int32_t* run_off /*[B*K+1]*/, uint32_t* bounds /*[cap]*/, int64_t cap,
                     int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- overlay of the selected detections (myolo/render.py, MaskYOLO.detect(render=True); the picture and the kernel: DESIGN.md section 16): the
+ * three layers of render.render_instances -- every PASTED mask blended into the image, every mask's one-pixel outline, the dashed ring of every
+ * paste window, each over the slots in order -- drawn from the uploaded image bytes in one launch.  A mask pixel is the paste of
+ * myolo_unmold_masks (the same device function), so out is render_instances of the dense paste byte for byte; no dense mask is written or
+ * downloaded.  Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).
+ * images: the pack_images layout -- desc [B,3] int64 = (byte offset from images, h, w) of image b, on the device and (desc_host) in host memory;
+ * nbytes = the bytes of the batch behind images (< 2^31), which every image must lie within.  A batch at one size is the descriptor of B equal
+ * images over a [B,H,W,3] tensor.  out: uint8 in the same layout at the same offsets (nbytes too; the bytes between images are not touched); two
+ * descriptors must not name overlapping bytes.  masks, det, sel, sel_host as myolo_mask_overlap_counts takes them (image b pastes into its own
+ * h x w frame; K <= 16, sel < 0 = empty slot, a value >= R refused); colors [B,K,3] double in [0, 1] (device).
+ * flags: bit 0 the blend, bit 1 the outline, bit 2 the box.  The blend is canvas * (1 - alpha) + (alpha * colour) * 255 in double, each product and
+ * the sum rounded on its own, truncated to the canvas; box_alpha takes alpha's place in the ring.
+ * MYOLO_EINVAL (message "render_instances: ...", nothing launched) for a null pointer, K outside 1 .. 16, sel >= R, h or w < 1, an image beyond
+ * nbytes, nbytes >= 2^31, alpha or box_alpha outside [0, 1], and a workspace under B * K int32.  desc_host and sel_host are read before anything
+ * is launched. */
+int myolo_render_instances(const uint8_t* images, uint8_t* out, size_t nbytes,
+                           const int64_t* desc /*[B,3] device: offset, h, w*/, const int64_t* desc_host,
+                           const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,R,6]*/,
+                           const int32_t* sel /*[B,K] device, <0 = empty*/, const int32_t* sel_host,
+                           const double* colors /*[B,K,3] device*/, double alpha, double box_alpha, int flags,
+                           int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- on-device training augmentation (myolo/augment.py, csrc/augment_kernels.hip; arithmetic contract: DESIGN.md "On-device augmentation").
  * Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).  Per image b one row of params: the INVERSE affine map
  * (output pixel -> source position, pixel-centre convention baked into m02 / m12), then gain and bias of the byte values.  The image is sampled

@@ -662,6 +662,153 @@ __global__ __launch_bounds__(256) void rle_scan_slots_kernel(int32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------
+// Overlay of the selected detections on the uploaded image bytes (myolo/render.py render_instances is the statement of the picture, DESIGN.md
+// section 16): for every image b of a packed batch (desc [B][3] = byte offset, h, w, the pack_images layout) the three layers of the host
+// renderer -- blend every pasted mask into the canvas, draw the one-pixel outline of every mask, blend the dashed ring of every paste window --
+// each over the slots k = 0 .. K-1 in order, written as uint8 at the image's own offset.  A mask pixel is unmold_pixel, so the picture is the
+// host render of the dense paste byte for byte; no dense mask is written.
+// One workgroup = one RN_TW x RN_TH tile of one image.  It first leaves in LDS, for every pixel of the tile and of a one-pixel halo around it,
+// the word whose bit k says that slot k's pasted mask holds the pixel (0 outside the frame: the zero padding the outline is defined on); only
+// the slots whose window meets the haloed tile are evaluated, a test that is the same for the whole workgroup.  Then every thread takes four
+// pixels in a row: its membership word and those of the four neighbours come from LDS, the blend runs in double with the product and the sum
+// as two roundings (no fused multiply-add: this file is compiled with -ffp-contract=off, and the intrinsics say so again) and truncates into
+// the canvas as numpy's store into a uint32 array does.  Four pixels are 12 bytes: loaded and stored as three dwords when the row's first
+// byte is 4-byte aligned (every row of an image whose width is a multiple of 4 in a batch of such images), as bytes otherwise.
+// ---------------------------------------------------------------------------------------
+#define RN_TW 128
+#define RN_TH 8
+#define RN_PITCH (RN_TW + 4)
+#define RN_HALO_PIXELS ((RN_TW + 2) * (RN_TH + 2))
+#define RN_FILL ((RN_HALO_PIXELS + 255) / 256)
+#define RN_BLEND 1
+#define RN_OUTLINE 2
+#define RN_BOX 4
+
+__global__ __launch_bounds__(256) void render_instances_kernel(const uint8_t* __restrict__ images, uint8_t* __restrict__ out,
+                                                               const int64_t* __restrict__ desc, const float* __restrict__ masks,
+                                                               const float* __restrict__ det, const int32_t* __restrict__ sel,
+                                                               const int32_t* __restrict__ allhigh, const double* __restrict__ colors,
+                                                               double alpha, double box_alpha, int flags, int R, int K, int mh, int mw, int C)
+{
+    __shared__ unsigned short memb[RN_TH + 2][RN_PITCH];
+    __shared__ int winL[OV_MAXK][4];                               // [x1, y1, x2, y2) of the slot's paste; x2 = 0 for a slot that draws nothing
+    __shared__ double blendL[OV_MAXK][3], boxL[OV_MAXK][3];        // (alpha * colour) * 255 of layer 1 and of layer 3
+    __shared__ unsigned lineL[OV_MAXK][3];                         // uint32(colour * 255) of layer 2
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const long long off = desc[3 * b];
+    const int H = (int)desc[3 * b + 1], W = (int)desc[3 * b + 2];
+    const int tiles_x = (W + RN_TW - 1) / RN_TW, tiles_y = (H + RN_TH - 1) / RN_TH;
+    if ((long long)blockIdx.x >= (long long)tiles_x * tiles_y) return;                  // the grid is the largest image's: uniform over the workgroup
+    const int tx0 = (int)(blockIdx.x % tiles_x) * RN_TW, ty0 = (int)(blockIdx.x / tiles_x) * RN_TH;
+
+    if (tid < K) {
+        const int s = sel[b * K + tid];
+        int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+        if (s >= 0 && s < R) unmold_window(det + ((long long)b * R + s) * 6, H, W, x1, y1, x2, y2);
+        if (x2 <= x1 || y2 <= y1) x1 = y1 = x2 = y2 = 0;
+        winL[tid][0] = x1, winL[tid][1] = y1, winL[tid][2] = x2, winL[tid][3] = y2;
+    }
+    if (tid < 3 * K) {
+        const int k = tid / 3, c = tid - 3 * k;
+        const double col = colors[((long long)b * K + k) * 3 + c];
+        blendL[k][c] = __dmul_rn(__dmul_rn(alpha, col), 255.0);
+        boxL[k][c] = __dmul_rn(__dmul_rn(box_alpha, col), 255.0);
+        lineL[k][c] = (unsigned)__dmul_rn(col, 255.0);
+    }
+    __syncthreads();
+
+    // the membership words of the haloed tile
+    unsigned word[RN_FILL];
+#pragma unroll
+    for (int j = 0; j < RN_FILL; ++j) word[j] = 0;
+    for (int k = 0; k < K; ++k) {
+        const int x1 = winL[k][0], y1 = winL[k][1], x2 = winL[k][2], y2 = winL[k][3];
+        // an empty slot or window (sel may be -1: nothing below may be read), or a window clear of the haloed tile
+        if (x2 <= x1 || x2 <= tx0 - 1 || x1 >= tx0 + RN_TW + 1 || y2 <= ty0 - 1 || y1 >= ty0 + RN_TH + 1) continue;
+        const long long row = (long long)b * R + sel[b * K + k];
+        const float* d = det + row * 6;
+        const float* m0 = masks + row * mh * mw * C;
+        const int ah = allhigh[b * K + k];
+#pragma unroll
+        for (int j = 0; j < RN_FILL; ++j) {
+            const int p = tid + 256 * j;
+            const int py = p / (RN_TW + 2), px = p - py * (RN_TW + 2);
+            const int x = tx0 - 1 + px, y = ty0 - 1 + py;
+            if (p < RN_HALO_PIXELS && x >= 0 && x < W && y >= 0 && y < H)
+                word[j] |= (unsigned)unmold_pixel(d, m0, ah, x, y, mh, mw, C, H, W) << k;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < RN_FILL; ++j) {
+        const int p = tid + 256 * j;
+        const int py = p / (RN_TW + 2), px = p - py * (RN_TW + 2);
+        if (p < RN_HALO_PIXELS) memb[py][px] = (unsigned short)word[j];
+    }
+    __syncthreads();
+
+    // four pixels of one row per thread
+    const int ly = tid / (RN_TW / 4), lx = (tid - ly * (RN_TW / 4)) * 4;
+    const int y = ty0 + ly, xa = tx0 + lx;
+    if (y >= H || xa >= W) return;
+    const int npix = min(4, W - xa);
+    const long long at = off + ((long long)y * W + xa) * 3;
+    const uint8_t* src = images + at;
+    uint8_t* dst = out + at;
+    const bool wide = npix == 4 && ((((uintptr_t)src) | ((uintptr_t)dst)) & 3) == 0;
+    unsigned px3[3];                                               // the 12 bytes, little-endian
+    if (wide) {
+        px3[0] = ((const unsigned*)src)[0], px3[1] = ((const unsigned*)src)[1], px3[2] = ((const unsigned*)src)[2];
+    } else {
+        px3[0] = px3[1] = px3[2] = 0;
+        for (int i = 0; i < 3 * npix; ++i) px3[i >> 2] |= (unsigned)src[i] << (8 * (i & 3));
+    }
+    const double keep1 = 1.0 - alpha, keep3 = 1.0 - box_alpha;
+    unsigned res[3] = {0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned cv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cv[c] = (px3[(3 * i + c) >> 2] >> (8 * ((3 * i + c) & 3))) & 255u;
+        if (i < npix) {
+            const int x = xa + i;
+            const unsigned m = memb[ly + 1][lx + i + 1];
+            if (flags & RN_BLEND)
+                for (unsigned rest = m; rest; rest &= rest - 1) {
+                    const int k = __ffs(rest) - 1;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) cv[c] = (unsigned)__dadd_rn(__dmul_rn((double)cv[c], keep1), blendL[k][c]);
+                }
+            if (flags & RN_OUTLINE) {
+                // on the outline of slot k: set, and one of the four neighbours (0 beyond the frame) is not.  The slots are drawn in order, so the
+                // last one shows.
+                const unsigned edge = m & ~(memb[ly][lx + i + 1] & memb[ly + 2][lx + i + 1] & memb[ly + 1][lx + i] & memb[ly + 1][lx + i + 2]);
+                if (edge) {
+                    const int k = 31 - __clz(edge);
+                    cv[0] = lineL[k][0], cv[1] = lineL[k][1], cv[2] = lineL[k][2];
+                }
+            }
+            if (flags & RN_BOX)
+                for (int k = 0; k < K; ++k) {
+                    const int x1 = winL[k][0], y1 = winL[k][1], x2 = winL[k][2], y2 = winL[k][3];
+                    if (x < x1 || x >= x2 || y < y1 || y >= y2) continue;
+                    const bool band = y - y1 < 2 || y2 - 1 - y < 2;                    // the top or the bottom band of the ring
+                    if (!band && !(x - x1 < 2 || x2 - 1 - x < 2)) continue;
+                    if ((((band ? x - x1 : y - y1) / 6) & 1) != 0) continue;           // the gaps of the dashes
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) cv[c] = (unsigned)__dadd_rn(__dmul_rn((double)cv[c], keep3), boxL[k][c]);
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) res[(3 * i + c) >> 2] |= (cv[c] & 255u) << (8 * ((3 * i + c) & 3));
+    }
+    if (wide) {
+        ((unsigned*)dst)[0] = res[0], ((unsigned*)dst)[1] = res[1], ((unsigned*)dst)[2] = res[2];
+    } else {
+        for (int i = 0; i < 3 * npix; ++i) dst[i] = (uint8_t)(res[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // GPU producer of the Shapes input pipeline: rasterise the images and instance masks
 // of a batch from their shape specifications (example/shapes/dataset_shapes.py:80-135: load_image / load_mask /
 // draw_shape incl. the occlusion rule :112-116), drop empty instances and take tight boxes (load_image_gt + extract_bboxes,
@@ -922,6 +1069,40 @@ int myolo_rle_masks(const float* masks, const float* det, const int32_t* sel, co
     hipLaunchKernelGGL(rle_scan_slots_kernel, dim3(1), dim3(256), 0, s, run_off, B * K);
     hipLaunchKernelGGL(rle_columns_kernel<true>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, cols,
                        (const int32_t*)run_off, bounds, (long long)cap, R, K, mh, mw, C, max_w);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+int myolo_render_instances(const uint8_t* images, uint8_t* out, size_t nbytes, const int64_t* desc, const int64_t* desc_host, const float* masks,
+                           const float* det, const int32_t* sel, const int32_t* sel_host, const double* colors, double alpha, double box_alpha,
+                           int flags, int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(images && out && desc && desc_host && masks && det && sel && sel_host && colors && ws, "render_instances: null pointer");
+    MYOLO_REQUIRE(B > 0 && B <= 65535 && R > 0 && mh > 0 && mw > 0 && C > 0, "render_instances: bad sizes");
+    MYOLO_REQUIRE(K > 0 && K <= OV_MAXK, "render_instances: need 1 <= K <= %d (got K=%d)", OV_MAXK, K);
+    MYOLO_REQUIRE(alpha >= 0.0 && alpha <= 1.0 && box_alpha >= 0.0 && box_alpha <= 1.0 && (flags & ~(RN_BLEND | RN_OUTLINE | RN_BOX)) == 0,
+                  "render_instances: alpha and box_alpha must lie in [0, 1] and flags in [0, 7] (got %g, %g, %d)", alpha, box_alpha, flags);
+    MYOLO_REQUIRE(nbytes < ((size_t)1 << 31), "render_instances: a batch of %zu bytes, 2^31 or more", nbytes);
+    long long tiles = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t off = desc_host[b * 3], h = desc_host[b * 3 + 1], w = desc_host[b * 3 + 2];
+        MYOLO_REQUIRE(h >= 1 && w >= 1, "render_instances: frame %d is %lld x %lld (h, w >= 1 needed)", b, (long long)h, (long long)w);
+        // 3 * h * w <= nbytes < 2^31 without forming a product that could overflow, then the offset
+        MYOLO_REQUIRE(off >= 0 && w <= (int64_t)nbytes / 3 && h <= (int64_t)nbytes / 3 / w && off <= (int64_t)nbytes - 3 * h * w,
+                      "render_instances: image %d (offset %lld, %lld x %lld x 3) does not fit the %zu bytes of the batch", b, (long long)off,
+                      (long long)h, (long long)w, nbytes);
+        const long long t = ((w + RN_TW - 1) / RN_TW) * ((h + RN_TH - 1) / RN_TH);
+        tiles = t > tiles ? t : tiles;
+    }
+    for (long long i = 0; i < (long long)B * K; ++i)
+        MYOLO_REQUIRE(sel_host[i] < R, "render_instances: sel[%lld] = %d is not a row of the %d detections", i, sel_host[i], R);
+    const size_t need = (size_t)B * K * sizeof(int32_t);
+    MYOLO_REQUIRE(ws_bytes >= need, "render_instances: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    int32_t* allhigh = (int32_t*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(B * K), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
+    hipLaunchKernelGGL(render_instances_kernel, dim3((unsigned)tiles, B), dim3(256), 0, s, images, out, desc, masks, det, sel,
+                       (const int32_t*)allhigh, colors, alpha, box_alpha, flags, R, K, mh, mw, C);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -136,6 +136,7 @@ SIGS = {
     "myolo_polygon_masks": [P, P, P, P, P, I, I, I, I, P],
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
+    "myolo_render_instances": [P, P, Z, P, P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, P, Z, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],

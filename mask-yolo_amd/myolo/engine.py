@@ -502,6 +502,8 @@ class Net(object):
         self._resize_stage_ev = None
         self._rle_bounds = None           # rle_masks: the device buffer of the boundaries (int32 words, grow-only) and its pinned host staging
         self._rle_pin = None
+        self._render_args = None          # render_instances: the pinned buffer of its arguments and the pinned, grow-only one the overlays come down into
+        self._render_pin = None
         self._cap_stream = None           # graph capture never happens with the default stream current (see _capture_predict)
         self._fm_stream = None            # inference: feature_map's conv beside the YOLO head (trunk_fwd)
         self.infer_fork_feature_map = False   # opt-in, and then only forwards that run alone: measured +0.0-0.5 % alone, -9 % with several batches in flight (forked graphs, 1150 -> 1055 img/s at Rice-416); and the extra stream it brings into a process moved the lanes' hardware-queue mapping in the full bench run (three lanes 1152 -> 1086)
@@ -2634,13 +2636,15 @@ class Net(object):
         while pending:
             yield hand_out()
 
-    def resize_to_frame(self, images, want_u8=False, n_slots=None, stage=None):
+    def resize_to_frame(self, images, want_u8=False, n_slots=None, stage=None, want_packed=False):
         """A list of uint8 [h,w,3] arrays of MIXED sizes -> the float32 [n,H,W,3] device tensor the forward takes (H, W of cfg.IMAGE_SHAPE):
         myolo_utils.resize_image of every image, then / 255., bit for bit, computed on the device from the uploaded bytes (myolo_resize_images_u8,
         DESIGN.md section 14).  The images are packed back to back behind their descriptor in ONE pinned staging buffer (pack_images) that goes
         up in one asynchronous copy.  want_u8: -> (float32 tensor, the uint8 [n,H,W,3] one).  n_slots > len(images): the tensor has n_slots images,
         the last one repeated (a descriptor, not a copy).  stage: a pinned uint8 tensor of >= packed_bytes(images, n_slots) bytes that the caller
-        keeps off-limits until the work queued here has run (detect_many's ring); without one, the Net's own grow-only buffer, waited on here."""
+        keeps off-limits until the work queued here has run (detect_many's ring); without one, the Net's own grow-only buffer, waited on here.
+        want_packed: the result gains a last element (bytes_d, desc): the uploaded image bytes as a flat uint8 device tensor and the host
+        descriptor [n,3] int64 (offset into bytes_d, h, w) -- what render_instances draws on."""
         images = list(images)
         n = len(images) if n_slots is None else int(n_slots)
         need = packed_bytes(images, n)
@@ -2667,7 +2671,77 @@ class Net(object):
         ws = torch.empty(2 * n, dtype=torch.int32, device=self.dev)
         X.call("myolo_resize_images_u8", packed.data_ptr() + head, need - head, packed.data_ptr(), desc.ctypes.data, X.ptr(u8), X.ptr(x),
                n, H, W, ws.data_ptr(), ws.numel() * 4, X.stream())
+        if want_packed:
+            return ((x, u8) if want_u8 else (x,)) + ((packed[head:], desc),)
         return (x, u8) if want_u8 else x
+
+    RENDER_BLEND, RENDER_OUTLINE, RENDER_BOX = 1, 2, 4         # the layers of myolo_render_instances' flags word
+
+    def render_instances(self, images_d, desc, det_d, mask_d, sel, colors=None, alpha=0.5, box_alpha=0.7, show_mask=True, show_outline=True,
+                         show_bbox=True):
+        """The overlays of a batch, drawn on the device from the uploaded image bytes (myolo_render_instances, include/myolo_hip_internal.h; the
+        picture: myolo/render.py render_instances, whose bytes these are): images_d a uint8 device tensor holding the images, desc [B,3] int64 in
+        HOST memory = (byte offset into images_d, h, w) of image b -- the pack_images layout, as resize_to_frame(want_packed=True) hands both
+        back; desc=None: images_d is [B,H,W,3].  det_d [B,R,6], mask_d [B,R,mh,mw,C] as predict returns them, sel [B,K] int32 in host memory =
+        rows of det_d per image in drawing order, -1 = empty slot, K <= 16; image b's masks are pasted into its own h x w frame.  colors [B,K,3]
+        float64 in [0,1], None: render.instance_colors(n) over the n live slots of each image.
+        -> a list of B uint8 [h,w,3] arrays (copies).  sel, colors and the descriptor go up in one pinned buffer; the overlays have the layout
+        of the input and come down in one copy into a pinned buffer that only grows."""
+        from .render import instance_colors
+        sel_h = np.ascontiguousarray(sel.numpy() if torch.is_tensor(sel) else sel)
+        if sel_h.dtype != np.int32 or sel_h.ndim != 2:
+            raise ValueError("render_instances: sel must be a [B,K] int32 array in host memory")
+        B, K = int(sel_h.shape[0]), int(sel_h.shape[1])
+        if images_d.dtype != torch.uint8 or not images_d.is_cuda:
+            raise ValueError("render_instances: images must be a uint8 device tensor")
+        images_d, det_d, mask_d = images_d.contiguous(), det_d.contiguous(), mask_d.contiguous()
+        if desc is None:
+            if images_d.dim() != 4 or int(images_d.shape[0]) != B or int(images_d.shape[3]) != 3:
+                raise ValueError("render_instances: without a descriptor the images must be [B,H,W,3]")
+            h, w = int(images_d.shape[1]), int(images_d.shape[2])
+            desc = np.array([[b * h * w * 3, h, w] for b in range(B)], dtype=np.int64)
+        desc_h = np.ascontiguousarray(desc.numpy() if torch.is_tensor(desc) else desc)
+        R = int(det_d.shape[1]) if det_d.dim() == 3 else -1
+        if (desc_h.dtype != np.int64 or tuple(desc_h.shape) != (B, 3) or det_d.dtype != torch.float32 or mask_d.dtype != torch.float32
+                or mask_d.dim() != 5 or tuple(det_d.shape) != (B, R, 6) or tuple(mask_d.shape[:2]) != (B, R)):
+            raise ValueError("render_instances: desc [B,3] i64, det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32 expected")
+        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
+        if colors is None:
+            col_h = np.zeros((B, K, 3), np.float64)
+            for b in range(B):
+                live = np.flatnonzero(sel_h[b] >= 0)
+                if live.size:
+                    col_h[b, live] = np.asarray(instance_colors(live.size), dtype=np.float64)
+        else:
+            col_h = np.ascontiguousarray(colors, dtype=np.float64)
+            if tuple(col_h.shape) != (B, K, 3) or not (np.isfinite(col_h).all() and col_h.min() >= 0.0 and col_h.max() <= 1.0):
+                raise ValueError("render_instances: colors must be [B,K,3] values in [0, 1]")
+        flags = (self.RENDER_BLEND if show_mask else 0) | (self.RENDER_OUTLINE if show_outline else 0) | (self.RENDER_BOX if show_bbox else 0)
+        # host side: [descriptor | colours | sel] in one pinned buffer of 8-byte words (free again when this call returns: it ends with a
+        # synchronising download)
+        n_desc, n_col, n_sel = 3 * B, 3 * B * K, (B * K + 1) // 2
+        if self._render_args is None or self._render_args.numel() < n_desc + n_col + n_sel:
+            self._render_args = torch.empty(n_desc + n_col + n_sel, dtype=torch.int64).pin_memory()
+        args_h = self._render_args[:n_desc + n_col + n_sel]
+        args_np = args_h.numpy()
+        args_np[:n_desc] = desc_h.reshape(-1)
+        args_np[n_desc:n_desc + n_col].view(np.float64)[:] = col_h.reshape(-1)
+        args_np[n_desc + n_col:].view(np.int32)[:B * K] = sel_h.reshape(-1)
+        args_d = args_h.to(self.dev, non_blocking=True)
+        p_h, p_d = args_np.ctypes.data, args_d.data_ptr()
+        nbytes = int(images_d.numel())
+        out_d = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        ws = torch.empty(B * K, dtype=torch.int32, device=self.dev)
+        X.call("myolo_render_instances", X.ptr(images_d), X.ptr(out_d), nbytes, p_d, p_h, X.ptr(mask_d), X.ptr(det_d),
+               p_d + 8 * (n_desc + n_col), p_h + 8 * (n_desc + n_col), p_d + 8 * n_desc, float(alpha), float(box_alpha), flags,
+               B, R, K, mh, mw, C, ws.data_ptr(), ws.numel() * 4, X.stream())
+        used = int((desc_h[:, 0] + 3 * desc_h[:, 1] * desc_h[:, 2]).max())          # (the entry has checked every image against nbytes)
+        if self._render_pin is None or self._render_pin.numel() < used:
+            self._render_pin = torch.empty(max(used, 1 << 20), dtype=torch.uint8).pin_memory()
+        self._render_pin[:used].copy_(out_d[:used], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        flat = self._render_pin.numpy()
+        return [flat[int(o):int(o) + 3 * int(h) * int(w)].reshape(int(h), int(w), 3).copy() for o, h, w in desc_h]
 
     def overlap_counts(self, det_d, mask_d, sel, gt_masks):
         """Pixel overlaps of the pasted masks of selected detections with ground-truth planes, counted on the device

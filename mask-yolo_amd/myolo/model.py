@@ -635,7 +635,7 @@ class MaskYOLO(object):
                 "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
 
     def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image",
-               mask_format="dense"):
+               mask_format="dense", render=False):
         """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ].  An image of another size than config.IMAGE_SHAPE
         is resized to it on the device (Net.resize_to_frame: myolo_utils.resize_image's result, bit for bit) and reported in
         the frame mask_frame names: "image" -- bboxes in pixels of the image given, full_masks [h,w,n] pasted at that size -- or "network" --
@@ -643,20 +643,31 @@ class MaskYOLO(object):
         mask_format="rle": instead of full_masks the dict has rle_masks, a list of COCO run-length dicts {"size": [h, w], "counts": int64 array}
         (myolo/rle.py) in the order of class_ids, size = the frame mask_frame names; rle.decode of each is the full_masks plane bit for bit.  The
         masks are encoded on the device (Net.rle_masks) and no dense mask is written or downloaded.  Not supported together
-        with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).  Any other mask_format raises ValueError."""
+        with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).  Any other mask_format raises ValueError.
+        render=True: the dict gains "rendered", uint8 [h,w,3]: the overlay the reference's detect() draws (visualize.display_instances without the
+        captions) over the image given -- the masks blended in, their outlines, the dashed boxes, instance i of class_ids in colour i of
+        render.instance_colors(len(class_ids)) -- drawn on the device from the uploaded bytes (Net.render_instances); with a
+        save_path that is not None it is also written to save_path/InferMaskYOLO-0.png (the directory is created).
+        ValueError with mask_frame="network" for an image of another size than IMAGE_SHAPE (the canvas is the image given) and with
+        config.DETECT_MASKS_FOR_SELECTED_ONLY.  Without render, save_path and display are ignored."""
         cfg = self.config
         self._check_frame([image], mask_frame)
         self._check_format(mask_format)
+        self._check_render([image], mask_frame, render)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
         from . import _ext as X
+        canvas = None                                                    # render: (the image bytes on the device, their descriptor)
         if list(image.shape) == list(cfg.IMAGE_SHAPE):
             # (image / 255.).astype(float32) formed on the device from the uploaded bytes (myolo_u8_to_unit_f32: the float32 of the float64 quotient, as numpy
             # forms it on the host) -- bit-identical, a quarter of the bytes over PCIe and no 4 MB float64 temporary on the host (see detect_many)
             raw = torch.from_numpy(np.ascontiguousarray(image)).to(self.net.dev)
             x = torch.empty((1,) + tuple(raw.shape), dtype=torch.float32, device=self.net.dev)
             X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
+            canvas = (raw.unsqueeze(0), None)
+        elif render:
+            x, canvas = self.net.resize_to_frame([image], want_packed=True)
         else:
             x = self.net.resize_to_frame([image])
         frame = image.shape if mask_frame == "image" else cfg.IMAGE_SHAPE
@@ -664,17 +675,23 @@ class MaskYOLO(object):
         if mask_format == "rle":
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
             _, det_d, mask_d = predict(x)
-            return self._select_and_encode(det_d, mask_d, det_d.cpu().numpy(), [frame], cs_threshold)
+            out = self._select_and_encode(det_d, mask_d, det_d.cpu().numpy(), [frame], cs_threshold, canvas=canvas if render else None)
+            return self._save_rendered(out, save_path) if render else out
         if selected_only:
             yolo_output, det_d, feature = self.net.predict_detections(x)   # the mask head runs below, on the survivors only
             mask_d = None
         else:
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
             yolo_output, det_d, mask_d = predict(x)                        # device tensors
-        return [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], frame, cs_threshold,
-                                        feature=feature if selected_only else None)]
+        rows = [] if render else None
+        out = [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], frame, cs_threshold,
+                                       feature=feature if selected_only else None, rows=rows)]
+        if render:
+            self._render_into(out, canvas, det_d, mask_d, rows)
+            self._save_rendered(out, save_path)
+        return out
 
-    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense"):
+    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense", render=False):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
         config.BATCH_SIZE with `in_flight` batches running at once (one stream / hipGraph / scratch per lane: the launch-bound trunk of one
         batch under the matrix-pipe-bound mask head of another), and every image gets detect()'s own selection and unmolding
@@ -683,7 +700,9 @@ class MaskYOLO(object):
         detect(image, mask_frame=mask_frame)[0].
         mask_format="rle" (see detect; ValueError with config.DETECT_MASKS_FOR_SELECTED_ONLY): rle_masks in place of full_masks, and the
         post-processing runs once per BATCH -- the selection of all its images on the host from the one detection download, one [B, K] upload,
-        one Net.rle_masks call whose two downloads are a few KB -- where the dense form pastes and downloads per image."""
+        one Net.rle_masks call whose two downloads are a few KB -- where the dense form pastes and downloads per image.
+        render=True (see detect; nothing is written to disk here): every dict gains "rendered", drawn once per BATCH on the bytes the batch went
+        up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere."""
         cfg = self.config
         self._check_format(mask_format)
         assert self.mode == 'inference'
@@ -691,6 +710,7 @@ class MaskYOLO(object):
             self.load_weights(weights_dir)
         images = list(images)
         self._check_frame(images, mask_frame)
+        self._check_render(images, mask_frame, render)
         B = int(cfg.BATCH_SIZE)
         dev = self.net.dev
         groups = [images[lo:lo + B] for lo in range(0, len(images), B)]
@@ -718,11 +738,16 @@ class MaskYOLO(object):
                 self._resize_ring_key = (need, nring)
             rring = self._resize_ring
 
+        canvases = {}                                    # render: batch -> (the image bytes on the device, their descriptor), until it is drawn
+
         def batches():
             for bi, grp in enumerate(groups):
                 if not at_frame[bi]:
                     # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out; a short last batch repeats its last image)
-                    yield self.net.resize_to_frame(grp, n_slots=B, stage=rring[bi % nring])
+                    x = self.net.resize_to_frame(grp, n_slots=B, stage=rring[bi % nring], want_packed=render)
+                    if render:
+                        x, canvases[bi] = x
+                    yield x
                     continue
                 grp = grp + [grp[-1]] * (B - len(grp))                       # a short last batch is padded (the captured graph has one shape)
                 stage = ring[bi % len(ring)]             # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out)
@@ -730,24 +755,65 @@ class MaskYOLO(object):
                 raw = stage.to(dev, non_blocking=True)
                 x = torch.empty(raw.shape, dtype=torch.float32, device=dev)
                 X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())       # one launch (three float64 torch kernels took 0.37 ms per batch)
+                if render:
+                    canvases[bi] = (raw, None)
                 yield x
         out = []
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
             det_all = det_d.cpu().numpy()
+            canvas = canvases.pop(bi) if render else None
             if mask_format == "rle":
                 live = images[bi * B:(bi + 1) * B]
                 out += self._select_and_encode(det_d, mask_d, det_all, [im.shape if mask_frame == "image" else cfg.IMAGE_SHAPE for im in live],
-                                               cs_threshold)
+                                               cs_threshold, canvas=canvas)
                 continue
+            rows = [] if render else None
+            first = len(out)
             for k in range(min(B, len(images) - bi * B)):
                 frame = images[bi * B + k].shape if mask_frame == "image" else cfg.IMAGE_SHAPE
-                out.append(self._select_and_unmold(det_d[k], mask_d[k], frame, cs_threshold, det_host=det_all[k]))
+                out.append(self._select_and_unmold(det_d[k], mask_d[k], frame, cs_threshold, det_host=det_all[k], rows=rows))
+            if render:
+                self._render_into(out[first:], canvas, det_d, mask_d, rows)
         return out
         # (one unmold launch and one download per BATCH instead of per image was measured: 514 img/s against 865 -- a pageable 6.9 MB download runs at
         # 2 GB/s where four of 1.7 MB do not, and cutting the H x W x 40 block into per-image H x W x n arrays costs the host another 0.5 ms per image)
 
-    def _select_and_unmold(self, det_img, mask_img, image_shape, cs_threshold, feature=None, det_host=None):
-        """detect()'s post-processing of ONE image: det_img [R,6], mask_img [R,mh,mw,C] (None: the mask head runs here, on the survivors) device tensors."""
+    def _check_render(self, images, mask_frame, render):
+        if not render:
+            return
+        if bool(getattr(self.config, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
+            raise ValueError("render=True is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
+        if mask_frame == "network" and any(list(im.shape) != list(self.config.IMAGE_SHAPE) for im in images):
+            raise ValueError("render=True draws on the image given: mask_frame='network' needs every image at config.IMAGE_SHAPE")
+
+    def _render_into(self, results, canvas, det_d, mask_d, rows):
+        """results[k]["rendered"] = the overlay of image k of a batch: canvas = (the image bytes on the device, their host descriptor or None for a
+        [B,H,W,3] tensor), rows[k] = the rows of det_d[k] that image k reports, in the order of its class_ids.  One Net.render_instances call."""
+        n = len(results)
+        sel = np.full((n, self.EVAL_SLOTS), -1, np.int32)
+        for k, r in enumerate(rows):
+            sel[k, :len(r)] = r
+        images_d, desc = canvas
+        if desc is None:
+            images_d = images_d[:n]                              # (a short last batch is padded with copies of its last image)
+        else:
+            desc = desc[:n]
+        for r, pic in zip(results, self.net.render_instances(images_d, desc, det_d[:n], mask_d[:n], sel)):
+            r["rendered"] = pic
+
+    def _save_rendered(self, results, save_path):
+        """detect(render=True)'s file: save_path/InferMaskYOLO-<k>.png for result k of the call (the reference saves its figure under save_path
+        too, model.py:1322-1328)"""
+        if save_path is not None:
+            from .render import write_png
+            os.makedirs(save_path, exist_ok=True)
+            for k, r in enumerate(results):
+                write_png(os.path.join(save_path, "InferMaskYOLO-%d.png" % k), r["rendered"])
+        return results
+
+    def _select_and_unmold(self, det_img, mask_img, image_shape, cs_threshold, feature=None, det_host=None, rows=None):
+        """detect()'s post-processing of ONE image: det_img [R,6], mask_img [R,mh,mw,C] (None: the mask head runs here, on the survivors) device tensors.
+        rows: a list that gains the rows of det_img the result reports, in its order."""
         det_d, mask_d = det_img.unsqueeze(0), None if mask_img is None else mask_img.unsqueeze(0)
         selected_only = mask_img is None
         # decode_masks (model.py:1330-1391) unmolds every box and the caller then keeps <= 10 of them (model.py:1290-1304);
@@ -755,6 +821,8 @@ class MaskYOLO(object):
         # (same output: full_masks[:, :, nmb] of the all-box result).
         det_h = det_d[0].cpu().numpy() if det_host is None else det_host          # (detect_many: one download per batch)
         keep, nmb, boxes, scores, class_ids = self._select(det_h, cs_threshold)
+        if rows is not None:
+            rows.append(keep[nmb])
         if len(nmb):
             # (the few indices go up from a pinned buffer without blocking; the download of the pasted masks below ends every image with a
             # synchronisation, so the buffer is free again by the next one)
@@ -785,9 +853,10 @@ class MaskYOLO(object):
         if mask_format == "rle" and bool(getattr(self.config, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
             raise ValueError("mask_format='rle' is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
 
-    def _select_and_encode(self, det_d, mask_d, det_all, frames, cs_threshold):
+    def _select_and_encode(self, det_d, mask_d, det_all, frames, cs_threshold, canvas=None):
         """detect()'s post-processing of a BATCH in run-length form: det_d [B,R,6], mask_d [B,R,mh,mw,C] device tensors, det_all = det_d's host
-        copy, frames = the (h, w, ...) of the first len(frames) <= B images (the rest of the batch is padding).  -> their result dicts."""
+        copy, frames = the (h, w, ...) of the first len(frames) <= B images (the rest of the batch is padding).  -> their result dicts.
+        canvas (see _render_into): the dicts gain "rendered", drawn from the same selection."""
         from .rle import counts_from_boundaries
         B, K, n = int(det_d.shape[0]), self.EVAL_SLOTS, len(frames)
         sel = np.full((B, K), -1, np.int32)
@@ -809,6 +878,8 @@ class MaskYOLO(object):
                 "rle_masks": [{"size": [h, w], "counts": counts_from_boundaries(bounds[run_off[s]:run_off[s + 1]], h * w)}
                               for s in range(k * K, k * K + len(class_ids))],
             })
+        if canvas is not None:
+            self._render_into(out, canvas, det_d, mask_d, [sel[k][sel[k] >= 0] for k in range(n)])
         return out
 
     def _select(self, det_h, cs_threshold):
