@@ -2675,6 +2675,21 @@ class Net(object):
             return ((x, u8) if want_u8 else (x,)) + ((packed[head:], desc),)
         return (x, u8) if want_u8 else x
 
+    @staticmethod
+    def _selected_sizes(who, expected, det_d, mask_d, sel):
+        """The argument check overlap_counts / rle_masks / render_instances share: sel [B,K] int32 in HOST memory (a numpy array is wrapped, a CPU
+        tensor stays the tensor it is -- pinned, it goes up without blocking), det_d [B,R,6] and mask_d [B,R,mh,mw,C] float32.
+        -> (sel as a contiguous host tensor, (B, R, K, mh, mw, C)); ValueError in the name `who`, `expected` = its list of arguments."""
+        sel_t = sel if torch.is_tensor(sel) else torch.from_numpy(np.ascontiguousarray(sel))
+        if sel_t.is_cuda or sel_t.dtype != torch.int32 or sel_t.dim() != 2:
+            raise ValueError("%s: sel must be a [B,K] int32 array in host memory" % who)
+        B, K = int(sel_t.shape[0]), int(sel_t.shape[1])
+        R = int(det_d.shape[1]) if det_d.dim() == 3 else -1
+        if (det_d.dtype != torch.float32 or mask_d.dtype != torch.float32 or mask_d.dim() != 5 or tuple(det_d.shape) != (B, R, 6)
+                or tuple(mask_d.shape[:2]) != (B, R)):
+            raise ValueError("%s: %s expected" % (who, expected))
+        return sel_t.contiguous(), (B, R, K) + tuple(int(v) for v in mask_d.shape[2:])
+
     RENDER_BLEND, RENDER_OUTLINE, RENDER_BOX = 1, 2, 4         # the layers of myolo_render_instances' flags word
 
     def render_instances(self, images_d, desc, det_d, mask_d, sel, colors=None, alpha=0.5, box_alpha=0.7, show_mask=True, show_outline=True,
@@ -2688,10 +2703,9 @@ class Net(object):
         -> a list of B uint8 [h,w,3] arrays (copies).  sel, colors and the descriptor go up in one pinned buffer; the overlays have the layout
         of the input and come down in one copy into a pinned buffer that only grows."""
         from .render import instance_colors
-        sel_h = np.ascontiguousarray(sel.numpy() if torch.is_tensor(sel) else sel)
-        if sel_h.dtype != np.int32 or sel_h.ndim != 2:
-            raise ValueError("render_instances: sel must be a [B,K] int32 array in host memory")
-        B, K = int(sel_h.shape[0]), int(sel_h.shape[1])
+        expected = "desc [B,3] i64, det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32"
+        sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("render_instances", expected, det_d, mask_d, sel)
+        sel_h = sel_t.numpy()
         if images_d.dtype != torch.uint8 or not images_d.is_cuda:
             raise ValueError("render_instances: images must be a uint8 device tensor")
         images_d, det_d, mask_d = images_d.contiguous(), det_d.contiguous(), mask_d.contiguous()
@@ -2701,11 +2715,8 @@ class Net(object):
             h, w = int(images_d.shape[1]), int(images_d.shape[2])
             desc = np.array([[b * h * w * 3, h, w] for b in range(B)], dtype=np.int64)
         desc_h = np.ascontiguousarray(desc.numpy() if torch.is_tensor(desc) else desc)
-        R = int(det_d.shape[1]) if det_d.dim() == 3 else -1
-        if (desc_h.dtype != np.int64 or tuple(desc_h.shape) != (B, 3) or det_d.dtype != torch.float32 or mask_d.dtype != torch.float32
-                or mask_d.dim() != 5 or tuple(det_d.shape) != (B, R, 6) or tuple(mask_d.shape[:2]) != (B, R)):
-            raise ValueError("render_instances: desc [B,3] i64, det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32 expected")
-        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
+        if desc_h.dtype != np.int64 or tuple(desc_h.shape) != (B, 3):
+            raise ValueError("render_instances: %s expected" % expected)
         if colors is None:
             col_h = np.zeros((B, K, 3), np.float64)
             for b in range(B):
@@ -2749,18 +2760,13 @@ class Net(object):
         sel [B,K] int32 in HOST memory (a numpy array or a CPU tensor; a pinned tensor goes up without blocking) = rows of det_d per image,
         -1 = empty slot, K <= 16; gt_masks [B,H,W,T] uint8 0 / 1 device tensor, T <= 32.
         -> device int32 tensors inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4] ([x1,y1,x2,y2) of the paste)."""
-        sel_h = sel if torch.is_tensor(sel) else torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32))
-        if sel_h.is_cuda or sel_h.dtype != torch.int32 or sel_h.dim() != 2:
-            raise ValueError("overlap_counts: sel must be a [B,K] int32 array in host memory")
-        sel_h = sel_h.contiguous()
+        expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, gt_masks [B,H,W,T] u8"
+        sel_h, (B, R, K, mh, mw, C) = self._selected_sizes("overlap_counts", expected, det_d, mask_d,
+                                                            sel if torch.is_tensor(sel) else np.asarray(sel, dtype=np.int32))
+        if gt_masks.dtype != torch.uint8 or gt_masks.dim() != 4 or int(gt_masks.shape[0]) != B:
+            raise ValueError("overlap_counts: %s expected" % expected)
         det_d, mask_d, gt_masks = det_d.contiguous(), mask_d.contiguous(), gt_masks.contiguous()
-        B, R = int(det_d.shape[0]), int(det_d.shape[1])
-        K = int(sel_h.shape[1])
-        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
         H, W, T = int(gt_masks.shape[1]), int(gt_masks.shape[2]), int(gt_masks.shape[3])
-        if (det_d.dtype != torch.float32 or mask_d.dtype != torch.float32 or gt_masks.dtype != torch.uint8 or tuple(mask_d.shape[:2]) != (B, R)
-                or int(det_d.shape[2]) != 6 or int(gt_masks.shape[0]) != B or int(sel_h.shape[0]) != B):
-            raise ValueError("overlap_counts: det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, gt_masks [B,H,W,T] u8 expected")
         sel_d = sel_h.to(self.dev, non_blocking=True)
         # one buffer: [inter | area_pred | area_gt | win | allhigh scratch]
         n = (B * K * T, B * K, B * T, B * K * 4, B * K)
@@ -2782,17 +2788,13 @@ class Net(object):
         One upload (sel and frames together) and two small downloads: the offsets, then bounds[:total].  The boundaries land in ONE device buffer
         per Net that only grows; when a batch holds more than it has room for, the entry has still written every offset, so the buffer is
         enlarged to the total and the call repeated."""
-        sel_h = np.ascontiguousarray(sel.numpy() if torch.is_tensor(sel) else sel)
+        expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32"
+        sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("rle_masks", expected, det_d, mask_d, sel)
+        sel_h = sel_t.numpy()
         frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)
-        if sel_h.dtype != np.int32 or sel_h.ndim != 2 or frames_h.dtype != np.int32 or frames_h.ndim != 2:
-            raise ValueError("rle_masks: sel [B,K] and frames [B,2] must be int32 arrays in host memory")
+        if frames_h.dtype != np.int32 or tuple(frames_h.shape) != (B, 2):
+            raise ValueError("rle_masks: %s expected" % expected)
         det_d, mask_d = det_d.contiguous(), mask_d.contiguous()
-        B, R = int(det_d.shape[0]), int(det_d.shape[1])
-        K = int(sel_h.shape[1])
-        if (det_d.dtype != torch.float32 or mask_d.dtype != torch.float32 or mask_d.dim() != 5 or tuple(mask_d.shape[:2]) != (B, R)
-                or int(det_d.shape[2]) != 6 or int(sel_h.shape[0]) != B or tuple(frames_h.shape) != (B, 2)):
-            raise ValueError("rle_masks: det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32 expected")
-        mh, mw, C = int(mask_d.shape[2]), int(mask_d.shape[3]), int(mask_d.shape[4])
         nsel, nslot = B * K, B * K + 1
         # host side: [sel | frames | run_off] in one pinned buffer (free again when this call returns: it ends with a synchronising download)
         if self._rle_pin is None or self._rle_pin.numel() < nsel + 2 * B + nslot:

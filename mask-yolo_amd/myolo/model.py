@@ -32,6 +32,7 @@ import time
 import numpy as np
 import torch
 
+from . import detect as D
 from . import myolo_utils as mutils
 from .engine import Net, layer_table
 
@@ -239,6 +240,7 @@ class MaskYOLO(object):
         self.yolo_trainable = yolo_trainable
         self._device, self._seed = device, seed
         self._weights_cache = None
+        self._detect_stager = None          # myolo.detect.Stager, made by the first detection call
         self._lr = None
         self._trainable_regex = ".*"
         self.net = self.build(mode=mode, config=self.config)
@@ -626,13 +628,19 @@ class MaskYOLO(object):
         return mutils.decode_one_yolo_output(netout[0], anchors=cfg.ANCHORS, nms_threshold=0.3, obj_threshold=0.35,
                                              nb_class=cfg.NUM_CLASSES)
 
-    @staticmethod
-    def _check_frame(images, mask_frame):
-        if mask_frame not in ("image", "network"):
-            raise ValueError("mask_frame must be 'image' or 'network' (got %r)" % (mask_frame,))
-        for im in images:
-            assert im.dtype == 'uint8' and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] >= 1 and im.shape[1] >= 1, \
-                "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
+    EVAL_SLOTS = D.SLOTS       # detect() keeps at most the top 10 detections of an image (the drivers below run the three pieces of myolo/detect.py)
+
+    def _stager(self):
+        if self._detect_stager is None:
+            self._detect_stager = D.Stager(self.net)
+        return self._detect_stager
+
+    def _select(self, det_h, cs_threshold):
+        """detect()'s selection of one image (detect.select): -> keep, nmb, boxes, scores, class_ids; the selected rows of det_h [R,6] are keep[nmb]"""
+        return D.select(det_h, cs_threshold, self.config.IMAGE_SHAPE)
+
+    def _frames(self, images, mask_frame):
+        return [im.shape if mask_frame == "image" else self.config.IMAGE_SHAPE for im in images]
 
     def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image",
                mask_format="dense", render=False):
@@ -651,45 +659,20 @@ class MaskYOLO(object):
         ValueError with mask_frame="network" for an image of another size than IMAGE_SHAPE (the canvas is the image given) and with
         config.DETECT_MASKS_FOR_SELECTED_ONLY.  Without render, save_path and display are ignored."""
         cfg = self.config
-        self._check_frame([image], mask_frame)
-        self._check_format(mask_format)
-        self._check_render([image], mask_frame, render)
+        D.check_args(cfg, [image], mask_frame, mask_format, render)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
-        from . import _ext as X
-        canvas = None                                                    # render: (the image bytes on the device, their descriptor)
-        if list(image.shape) == list(cfg.IMAGE_SHAPE):
-            # (image / 255.).astype(float32) formed on the device from the uploaded bytes (myolo_u8_to_unit_f32: the float32 of the float64 quotient, as numpy
-            # forms it on the host) -- bit-identical, a quarter of the bytes over PCIe and no 4 MB float64 temporary on the host (see detect_many)
-            raw = torch.from_numpy(np.ascontiguousarray(image)).to(self.net.dev)
-            x = torch.empty((1,) + tuple(raw.shape), dtype=torch.float32, device=self.net.dev)
-            X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
-            canvas = (raw.unsqueeze(0), None)
-        elif render:
-            x, canvas = self.net.resize_to_frame([image], want_packed=True)
-        else:
-            x = self.net.resize_to_frame([image])
-        frame = image.shape if mask_frame == "image" else cfg.IMAGE_SHAPE
-        selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
-        if mask_format == "rle":
-            predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
-            _, det_d, mask_d = predict(x)
-            out = self._select_and_encode(det_d, mask_d, det_d.cpu().numpy(), [frame], cs_threshold, canvas=canvas if render else None)
-            return self._save_rendered(out, save_path) if render else out
-        if selected_only:
-            yolo_output, det_d, feature = self.net.predict_detections(x)   # the mask head runs below, on the survivors only
-            mask_d = None
+        x, canvas = self._stager().stage_one(image, render)
+        mask_d = feature = None
+        if bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
+            _, det_d, feature = self.net.predict_detections(x)             # the mask head runs in dense_masks, on the survivors only
         else:
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
-            yolo_output, det_d, mask_d = predict(x)                        # device tensors
-        rows = [] if render else None
-        out = [self._select_and_unmold(det_d[0], None if mask_d is None else mask_d[0], frame, cs_threshold,
-                                       feature=feature if selected_only else None, rows=rows)]
-        if render:
-            self._render_into(out, canvas, det_d, mask_d, rows)
-            self._save_rendered(out, save_path)
-        return out
+            _, det_d, mask_d = predict(x)                                  # device tensors
+        selection = D.Selection(det_d.cpu().numpy(), 1, cs_threshold, cfg.IMAGE_SHAPE)
+        out = D.batch_results(self._stager(), det_d, mask_d, selection, self._frames([image], mask_frame), mask_format, canvas, feature)
+        return self._save_rendered(out, save_path) if render else out
 
     def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense", render=False):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
@@ -704,102 +687,26 @@ class MaskYOLO(object):
         render=True (see detect; nothing is written to disk here): every dict gains "rendered", drawn once per BATCH on the bytes the batch went
         up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere."""
         cfg = self.config
-        self._check_format(mask_format)
+        images = list(images)
+        D.check_args(cfg, images, mask_frame, mask_format, render)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
-        images = list(images)
-        self._check_frame(images, mask_frame)
-        self._check_render(images, mask_frame, render)
         B = int(cfg.BATCH_SIZE)
-        dev = self.net.dev
         groups = [images[lo:lo + B] for lo in range(0, len(images), B)]
-        at_frame = [all(list(im.shape) == list(cfg.IMAGE_SHAPE) for im in grp) for grp in groups]
-
-        from . import _ext as X
-        from .engine import packed_bytes
-        # the bytes go up as they are (a quarter of the float32 image) from a ring of pinned buffers, and (image / 255.).astype(float32) is formed on the
-        # device (myolo_u8_to_unit_f32: the float32 of the float64 quotient, which is what numpy does on the host) -- bit-identical to detect()'s input (the host
-        # normalisation + pageable upload of 8 MB per batch of four 416 x 416 images cost 2.3 ms per batch, more than half the forward)
-        nring = 2 * in_flight + 2
-        ring = rring = None
-        if any(at_frame):
-            key = (B, tuple(cfg.IMAGE_SHAPE), nring)
-            if getattr(self, "_stage_ring_key", None) != key:            # (pinning costs ~5 ms per buffer: once per model, not once per call)
-                self._stage_ring = [torch.empty((B,) + tuple(cfg.IMAGE_SHAPE), dtype=torch.uint8).pin_memory() for _ in range(key[2])]
-                self._stage_ring_key = key
-            ring = self._stage_ring
-        if not all(at_frame):
-            # the ring of the resized batches: flat buffers sized once per call to the largest packed batch, kept while they are large enough
-            need = max(packed_bytes(grp, B) for grp, ok in zip(groups, at_frame) if not ok)
-            rkey = getattr(self, "_resize_ring_key", None)
-            if rkey is None or rkey[0] < need or rkey[1] != nring:
-                self._resize_ring = [torch.empty(need, dtype=torch.uint8).pin_memory() for _ in range(nring)]
-                self._resize_ring_key = (need, nring)
-            rring = self._resize_ring
-
-        canvases = {}                                    # render: batch -> (the image bytes on the device, their descriptor), until it is drawn
+        stager = self._stager()
+        stager.reserve(in_flight, groups)
+        canvases = {}                                    # batch -> its canvas, until it is drawn
 
         def batches():
             for bi, grp in enumerate(groups):
-                if not at_frame[bi]:
-                    # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out; a short last batch repeats its last image)
-                    x = self.net.resize_to_frame(grp, n_slots=B, stage=rring[bi % nring], want_packed=render)
-                    if render:
-                        x, canvases[bi] = x
-                    yield x
-                    continue
-                grp = grp + [grp[-1]] * (B - len(grp))                       # a short last batch is padded (the captured graph has one shape)
-                stage = ring[bi % len(ring)]             # (predict_stream runs at most 2 * in_flight batches ahead of the results handed out)
-                np.stack(grp, out=stage.numpy())
-                raw = stage.to(dev, non_blocking=True)
-                x = torch.empty(raw.shape, dtype=torch.float32, device=dev)
-                X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())       # one launch (three float64 torch kernels took 0.37 ms per batch)
-                if render:
-                    canvases[bi] = (raw, None)
+                x, canvases[bi] = stager.stage(bi, grp, render)
                 yield x
         out = []
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
-            det_all = det_d.cpu().numpy()
-            canvas = canvases.pop(bi) if render else None
-            if mask_format == "rle":
-                live = images[bi * B:(bi + 1) * B]
-                out += self._select_and_encode(det_d, mask_d, det_all, [im.shape if mask_frame == "image" else cfg.IMAGE_SHAPE for im in live],
-                                               cs_threshold, canvas=canvas)
-                continue
-            rows = [] if render else None
-            first = len(out)
-            for k in range(min(B, len(images) - bi * B)):
-                frame = images[bi * B + k].shape if mask_frame == "image" else cfg.IMAGE_SHAPE
-                out.append(self._select_and_unmold(det_d[k], mask_d[k], frame, cs_threshold, det_host=det_all[k], rows=rows))
-            if render:
-                self._render_into(out[first:], canvas, det_d, mask_d, rows)
+            selection = D.Selection(det_d.cpu().numpy(), len(groups[bi]), cs_threshold, cfg.IMAGE_SHAPE)
+            out += D.batch_results(stager, det_d, mask_d, selection, self._frames(groups[bi], mask_frame), mask_format, canvases.pop(bi))
         return out
-        # (one unmold launch and one download per BATCH instead of per image was measured: 514 img/s against 865 -- a pageable 6.9 MB download runs at
-        # 2 GB/s where four of 1.7 MB do not, and cutting the H x W x 40 block into per-image H x W x n arrays costs the host another 0.5 ms per image)
-
-    def _check_render(self, images, mask_frame, render):
-        if not render:
-            return
-        if bool(getattr(self.config, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
-            raise ValueError("render=True is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
-        if mask_frame == "network" and any(list(im.shape) != list(self.config.IMAGE_SHAPE) for im in images):
-            raise ValueError("render=True draws on the image given: mask_frame='network' needs every image at config.IMAGE_SHAPE")
-
-    def _render_into(self, results, canvas, det_d, mask_d, rows):
-        """results[k]["rendered"] = the overlay of image k of a batch: canvas = (the image bytes on the device, their host descriptor or None for a
-        [B,H,W,3] tensor), rows[k] = the rows of det_d[k] that image k reports, in the order of its class_ids.  One Net.render_instances call."""
-        n = len(results)
-        sel = np.full((n, self.EVAL_SLOTS), -1, np.int32)
-        for k, r in enumerate(rows):
-            sel[k, :len(r)] = r
-        images_d, desc = canvas
-        if desc is None:
-            images_d = images_d[:n]                              # (a short last batch is padded with copies of its last image)
-        else:
-            desc = desc[:n]
-        for r, pic in zip(results, self.net.render_instances(images_d, desc, det_d[:n], mask_d[:n], sel)):
-            r["rendered"] = pic
 
     def _save_rendered(self, results, save_path):
         """detect(render=True)'s file: save_path/InferMaskYOLO-<k>.png for result k of the call (the reference saves its figure under save_path
@@ -811,92 +718,15 @@ class MaskYOLO(object):
                 write_png(os.path.join(save_path, "InferMaskYOLO-%d.png" % k), r["rendered"])
         return results
 
-    def _select_and_unmold(self, det_img, mask_img, image_shape, cs_threshold, feature=None, det_host=None, rows=None):
-        """detect()'s post-processing of ONE image: det_img [R,6], mask_img [R,mh,mw,C] (None: the mask head runs here, on the survivors) device tensors.
-        rows: a list that gains the rows of det_img the result reports, in its order."""
-        det_d, mask_d = det_img.unsqueeze(0), None if mask_img is None else mask_img.unsqueeze(0)
-        selected_only = mask_img is None
-        # decode_masks (model.py:1330-1391) unmolds every box and the caller then keeps <= 10 of them (model.py:1290-1304);
-        # the selection needs only boxes / scores / classes, so it runs first and only the survivors are unmolded
-        # (same output: full_masks[:, :, nmb] of the all-box result).
-        det_h = det_d[0].cpu().numpy() if det_host is None else det_host          # (detect_many: one download per batch)
-        keep, nmb, boxes, scores, class_ids = self._select(det_h, cs_threshold)
-        if rows is not None:
-            rows.append(keep[nmb])
-        if len(nmb):
-            # (the few indices go up from a pinned buffer without blocking; the download of the pasted masks below ends every image with a
-            # synchronisation, so the buffer is free again by the next one)
-            pin = getattr(self, "_sel_pin", None)
-            if pin is None or pin.numel() < len(nmb):
-                pin = self._sel_pin = torch.empty(max(64, len(nmb)), dtype=torch.int64).pin_memory()
-            pin[:len(nmb)].copy_(torch.from_numpy(np.ascontiguousarray(keep[nmb], dtype=np.int64)))
-            sel = pin[:len(nmb)].to(det_d.device, non_blocking=True)
-            det_s = det_d[0].index_select(0, sel).contiguous()
-            if selected_only:
-                mask_s = self.net.predict_masks(feature, det_s[:, :4].unsqueeze(0))[0]
-            else:
-                mask_s = mask_d[0].index_select(0, sel).contiguous()
-            _, _, _, full_masks = self._decode_masks_device(det_s, mask_s, image_shape, det_host=det_h[keep[nmb]])
-        else:
-            full_masks = np.empty((int(image_shape[0]), int(image_shape[1]), 0), dtype=bool)
-        H_img, W_img = float(image_shape[0]), float(image_shape[1])
-        return {
-            "bboxes": boxes[nmb] * np.array([W_img, H_img, W_img, H_img], dtype=boxes.dtype),     # pixels (model.py:1307)
-            "class_ids": class_ids[nmb],
-            "confidence_scores": scores[nmb],
-            "full_masks": full_masks,
-        }
-
-    def _check_format(self, mask_format):
-        if mask_format not in ("dense", "rle"):
-            raise ValueError("mask_format must be 'dense' or 'rle' (got %r)" % (mask_format,))
-        if mask_format == "rle" and bool(getattr(self.config, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
-            raise ValueError("mask_format='rle' is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
-
-    def _select_and_encode(self, det_d, mask_d, det_all, frames, cs_threshold, canvas=None):
-        """detect()'s post-processing of a BATCH in run-length form: det_d [B,R,6], mask_d [B,R,mh,mw,C] device tensors, det_all = det_d's host
-        copy, frames = the (h, w, ...) of the first len(frames) <= B images (the rest of the batch is padding).  -> their result dicts.
-        canvas (see _render_into): the dicts gain "rendered", drawn from the same selection."""
-        from .rle import counts_from_boundaries
-        B, K, n = int(det_d.shape[0]), self.EVAL_SLOTS, len(frames)
-        sel = np.full((B, K), -1, np.int32)
-        fr = np.ones((B, 2), np.int32)                                   # (padding: no slot, a 1 x 1 frame)
-        picked = []
-        for k in range(n):
-            keep, nmb, boxes, scores, class_ids = self._select(det_all[k], cs_threshold)
-            sel[k, :len(nmb)] = keep[nmb]
-            fr[k] = (int(frames[k][0]), int(frames[k][1]))
-            picked.append((boxes[nmb], class_ids[nmb], scores[nmb]))
-        run_off, bounds = self.net.rle_masks(det_d, mask_d, sel, fr)
-        out = []
-        for k, (boxes, class_ids, scores) in enumerate(picked):
-            h, w = int(fr[k, 0]), int(fr[k, 1])
-            out.append({
-                "bboxes": boxes * np.array([float(w), float(h), float(w), float(h)], dtype=boxes.dtype),     # pixels (model.py:1307)
-                "class_ids": class_ids,
-                "confidence_scores": scores,
-                "rle_masks": [{"size": [h, w], "counts": counts_from_boundaries(bounds[run_off[s]:run_off[s + 1]], h * w)}
-                              for s in range(k * K, k * K + len(class_ids))],
-            })
-        if canvas is not None:
-            self._render_into(out, canvas, det_d, mask_d, [sel[k][sel[k] >= 0] for k in range(n)])
-        return out
-
-    def _select(self, det_h, cs_threshold):
-        """detect()'s selection on the host copy det_h [R,6] of one image's detections (model.py:1290-1304, 1373-1380): drop the zero-area boxes,
-        take the top 10 by score, drop those under cs_threshold, NMB at 0.7.  -> keep (rows of det_h with area), nmb (the survivors, indices
-        into keep, in the order detect() reports them), and boxes / scores / class_ids of the keep rows.  The selected rows of det_h are keep[nmb]."""
-        boxes, scores, class_ids = det_h[:, :4], det_h[:, 4], det_h[:, 5].astype(np.int32)
-        keep = np.where((boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) > 0)[0]     # model.py:1373-1380
-        boxes, scores, class_ids = boxes[keep], scores[keep], class_ids[keep]
-        top10 = np.argsort(scores)[::-1][:self.EVAL_SLOTS]
-        kept = np.array([i for i in top10 if scores[i] >= cs_threshold], dtype=np.int64)
-        nmb = mutils.NMB(boxes[kept], class_ids[kept], kept, self.config.IMAGE_SHAPE, nms_threshold=0.7) if len(kept) else kept
-        return keep, np.asarray(nmb, dtype=np.int64), boxes, scores, class_ids
+    def _select_and_unmold(self, det_img, mask_img, image_shape, cs_threshold, feature=None, det_host=None):
+        """detect()'s dense post-processing of ONE image: det_img [R,6], mask_img [R,mh,mw,C] (None: the mask head runs on the survivors, over
+        `feature`) device tensors, det_host = det_img's host copy if the caller has it.  -> its result dict."""
+        det_h = det_img.cpu().numpy() if det_host is None else det_host
+        selection = D.Selection(det_h[None], 1, cs_threshold, self.config.IMAGE_SHAPE)
+        return D.batch_results(self._stager(), det_img.unsqueeze(0), None if mask_img is None else mask_img.unsqueeze(0), selection,
+                               [image_shape], feature=feature)[0]
 
     # ------------------------------------------------------------------ evaluation
-    EVAL_SLOTS = 10            # detect() keeps at most the top 10 detections of an image
-
     def evaluate(self, dataset, cs_threshold=0.35, max_samples=None, in_flight=3):
         """Mask and box average precision of detect()'s output on a dataset (myolo/evaluate.py) -> Evaluator.result().
         dataset: an object load_image_gt reads (as train() takes), or a sequence of (image, class_ids, boxes, masks) rows as load_image_gt
@@ -917,44 +747,26 @@ class MaskYOLO(object):
             assert list(row[0].shape) == list(cfg.IMAGE_SHAPE) and row[0].dtype == 'uint8'
         B, T = int(cfg.BATCH_SIZE), int(cfg.MAX_GT_INSTANCES)
         H, W = int(cfg.IMAGE_SHAPE[0]), int(cfg.IMAGE_SHAPE[1])
-        dev = self.net.dev
-
-        from . import _ext as X
-        nring = 2 * in_flight + 2
-        key = (B, tuple(cfg.IMAGE_SHAPE), nring)
-        if getattr(self, "_stage_ring_key", None) != key:            # detect_many's staging ring (the same key: the two share it)
-            self._stage_ring = [torch.empty((B,) + tuple(cfg.IMAGE_SHAPE), dtype=torch.uint8).pin_memory() for _ in range(nring)]
-            self._stage_ring_key = key
-        ring = self._stage_ring
-        gkey = (B, H, W, T, nring)
-        if getattr(self, "_gt_ring_key", None) != gkey:
-            self._gt_ring = [torch.empty((B, H, W, T), dtype=torch.uint8).pin_memory() for _ in range(nring)]
-            self._gt_ring_key = gkey
-        gt_ring = self._gt_ring
+        stager = self._stager()
+        slots = stager.reserve(in_flight)
+        gt_ring = stager.pinned("gt", slots, (B, H, W, T))               # the ground truth rides beside the images, slot for slot
         truth = collections.deque()
 
         def batches():
             for bi, lo in enumerate(range(0, len(info), B)):
                 grp = info[lo:lo + B]
-                n = len(grp)
-                grp = grp + [grp[-1]] * (B - n)                              # a short last batch is padded; its padding is ignored below
-                stage, gstage = ring[bi % nring], gt_ring[bi % nring]
-                np.stack([r[0] for r in grp], out=stage.numpy())
+                x, _ = stager.stage(bi, [r[0] for r in grp])
+                gstage = gt_ring[bi % slots]
                 gm = gstage.numpy()
-                gm.fill(0)
-                gt_ids = np.zeros((B, T), np.int32)
-                gt_boxes = np.zeros((B, T, 4), np.int32)
+                gm.fill(0)                                                   # (the planes of a short last batch's padding stay 0; ignored below)
+                gt_ids, gt_boxes = np.zeros((B, T), np.int32), np.zeros((B, T, 4), np.int32)
                 for k, (_, class_ids, boxes, masks) in enumerate(grp):
                     m = min(T, int(class_ids.shape[0]))                      # the first MAX_GT_INSTANCES, in order (BatchGenerator._encode's layout)
                     gt_ids[k, :m] = class_ids[:m]
                     gt_boxes[k, :m] = boxes[:m]
                     for j in range(m):
                         gm[k, :, :, j] = masks[:, :, j]
-                raw = stage.to(dev, non_blocking=True)
-                gt_d = gstage.to(dev, non_blocking=True)
-                x = torch.empty(raw.shape, dtype=torch.float32, device=dev)
-                X.call("myolo_u8_to_unit_f32", X.ptr(raw), X.ptr(x), raw.numel(), X.stream())
-                truth.append((n, gt_d, gt_ids, gt_boxes))
+                truth.append((len(grp), gstage.to(self.net.dev, non_blocking=True), gt_ids, gt_boxes))
                 yield x
         return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
 
@@ -980,55 +792,29 @@ class MaskYOLO(object):
         """the common part of evaluate() / evaluate_shapes_stream(): `batches` yields [B,H,W,3] device images and appends each batch's
         (images that count, gt_masks [B,H,W,T] device, gt_ids [B,T], gt_boxes [B,T,4] host or device) to the deque `truth`."""
         from .evaluate import Evaluator
-        cfg = self.config
-        B, K = int(cfg.BATCH_SIZE), self.EVAL_SLOTS
         ev = Evaluator()
-        if getattr(self, "_eval_sel_pin", None) is None or tuple(self._eval_sel_pin.shape) != (B, K):
-            self._eval_sel_pin = torch.empty((B, K), dtype=torch.int32).pin_memory()
-        sel = self._eval_sel_pin          # (free again by the next batch: the download of the counts below ends every batch with a synchronisation)
         for _, det_d, mask_d in self.net.predict_stream(batches, in_flight=in_flight):
             n, gt_d, gt_ids, gt_boxes = truth.popleft()
-            det_all = det_d.cpu().numpy()
-            picked = []
-            sel_h = sel.numpy()
-            sel_h.fill(-1)
-            for k in range(n):
-                keep, nmb, _, scores, class_ids = self._select(det_all[k], cs_threshold)
-                sel_h[k, :len(nmb)] = keep[nmb]
-                picked.append((scores[nmb], class_ids[nmb]))
-            counts = self.net.overlap_counts(det_d, mask_d, sel, gt_d)
-            inter, area_pred, area_gt, win = [t.cpu().numpy() for t in counts]
+            selection = D.Selection(det_d.cpu().numpy(), n, cs_threshold, self.config.IMAGE_SHAPE)
+            inter, area_pred, area_gt, win = D.overlap_counts(self._stager(), det_d, mask_d, selection, gt_d)
             if torch.is_tensor(gt_ids):
                 gt_ids, gt_boxes = gt_ids.cpu().numpy(), gt_boxes.cpu().numpy()
             for k in range(n):
-                scores, class_ids = picked[k]
+                _, class_ids, scores = selection.picked[k]
                 m = len(scores)
                 ev.add_image(scores, class_ids, gt_ids[k], inter[k, :m], area_pred[k, :m], area_gt[k], win[k, :m], gt_boxes[k])
         return ev.result()
 
-    def _decode_masks_device(self, det, masks, image_shape, det_host=None):
-        """decode_masks (model.py:1330-1391) with the unmold/paste of every detection on the GPU
-        (myolo_unmold_masks).  det [N,6], masks [N,mh,mw,C] device tensors of one image (det_host: det's host copy, if the caller has it)."""
-        from . import _ext as X
-        det_h = det.cpu().numpy() if det_host is None else det_host
-        boxes, scores = det_h[:, :4], det_h[:, 4]
-        class_ids = det_h[:, 5].astype(np.int32)
-        keep = np.where((boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) > 0)[0]     # model.py:1373-1380
+    def _decode_masks_device(self, det, masks, image_shape):
+        """decode_masks (model.py:1330-1391) with the unmold/paste of every detection on the GPU (detect.paste): det [N,6], masks [N,mh,mw,C]
+        device tensors of one image.  The zero-area boxes are dropped here; detect()'s selection has dropped them before it pastes."""
+        det_h = det.cpu().numpy()
+        keep = np.where((det_h[:, 2] - det_h[:, 0]) * (det_h[:, 3] - det_h[:, 1]) > 0)[0]     # model.py:1373-1380
         if keep.shape[0] != det_h.shape[0]:
             idx = torch.as_tensor(keep, device=det.device)
-            det, masks = det.index_select(0, idx).contiguous(), masks.index_select(0, idx).contiguous()
-            boxes, scores, class_ids = boxes[keep], scores[keep], class_ids[keep]
-        N = int(det.shape[0])
-        H, W = int(image_shape[0]), int(image_shape[1])
-        if N == 0:
-            return boxes, class_ids, scores, np.empty((H, W, 0))
-        mh, mw, C = int(masks.shape[1]), int(masks.shape[2]), int(masks.shape[3])
-        full = torch.empty(H, W, N, dtype=torch.uint8, device=det.device)
-        ws = torch.empty(N, dtype=torch.int32, device=det.device)
-        X.call("myolo_unmold_masks", X.ptr(masks.contiguous()), X.ptr(det.contiguous()), X.ptr(full), N, mh, mw, C, H, W,
-               ws.data_ptr(), ws.numel() * 4, X.stream())
-        # (a pinned staging buffer for this download was measured slower: the host's astype() then reads uncached memory)
-        return boxes, class_ids, scores, full.view(torch.bool).cpu().numpy()        # (the kernel writes 0 / 1 bytes: the bool view saves the host's astype pass)
+            det, masks, det_h = det.index_select(0, idx), masks.index_select(0, idx), det_h[keep]
+        full = D.paste(det, masks, image_shape) if len(keep) else np.empty((int(image_shape[0]), int(image_shape[1]), 0))
+        return det_h[:, :4], det_h[:, 5].astype(np.int32), det_h[:, 4], full
 
     def decode_masks(self, detections, myolo_mask, image_shape):
         """model.py:1330-1391 (numpy in / numpy out; the unmolding runs on the GPU)."""

@@ -231,3 +231,68 @@ def test_mask_frame_is_checked():
         m.detect(p.astype(np.float32))
     with pytest.raises(AssertionError):
         m.detect_many([p[:, :, 0]])
+
+
+# ------------------------------------------------------------------------------------------------ the staging rings (myolo/detect.py Stager)
+ELEVEN = ((128, 128), (128, 128), (200, 150), (300, 40), (61, 97), (1, 1), (128, 128), (128, 128), (128, 128), (128, 128), (77, 130))
+_PAIRS = []
+
+
+def _pairs():
+    if not _PAIRS:
+        cfg = make_config(ShapesConfig, IMAGE_SHAPE=[128, 128, 3], ALPHA=0.5, BATCH_SIZE=2)
+        _PAIRS.append((cfg, MaskYOLO(mode="inference", config=cfg, seed=4), [_shapes_like(h, w, 40 + k) for k, (h, w) in enumerate(ELEVEN)]))
+    return _PAIRS[0]
+
+
+def _same_results(got, want, what):
+    assert len(got) == len(want)
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert list(a) == list(b), (what, k)
+        for key in a:
+            if key == "rle_masks":
+                assert [x["size"] for x in a[key]] == [x["size"] for x in b[key]], (what, k)
+                assert all(x["counts"].dtype == y["counts"].dtype and np.array_equal(x["counts"], y["counts"]) for x, y in zip(a[key], b[key])), (what, k)
+            else:
+                assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (what, k, key)
+
+
+@pytest.mark.parametrize("fmt", ["dense", "rle"])
+def test_a_wrapping_ring_gives_what_a_ring_that_never_wraps_gives(fmt):
+    """eleven images in batches of two -- six batches, some at frame and some resized, a 1 x 1 image among them, a short last one -- with render:
+    in_flight=1 stages through four slots, so batches 4 and 5 reuse the slots of batches 0 (at frame) and 1 (resized) while earlier batches are
+    in flight; in_flight=3 has eight slots and reuses none.  predict_stream is held bit-identical across in_flight (tests/test_gpu_step.py), so
+    every array of every result must be equal."""
+    cfg, m, imgs = _pairs()
+    stager = m._stager()
+    groups = [imgs[lo:lo + 2] for lo in range(0, len(imgs), 2)]
+    kinds = [stager.at_frame(g) for g in groups]
+    assert len(groups) == 6 and len(groups[-1]) == 1
+    assert kinds[0] and kinds[4] and not kinds[1] and not kinds[5]          # each ring has a slot that is used twice
+    wrapped = m.detect_many(imgs, cs_threshold=0.0, in_flight=1, mask_format=fmt, render=True)
+    assert stager.slots == 4 < len(groups)
+    roomy = m.detect_many(imgs, cs_threshold=0.0, in_flight=3, mask_format=fmt, render=True)
+    assert stager.slots == 8 > len(groups)
+    assert sum(len(r["class_ids"]) for r in wrapped) >= len(imgs)
+    for im, r in zip(imgs, wrapped):
+        assert r["rendered"].shape == im.shape and r["rendered"].dtype == np.uint8
+    _same_results(wrapped, roomy, fmt)
+
+
+@pytest.mark.parametrize("k", [0, 2])
+def test_detect_rle_with_render_equals_the_dense_call(k):
+    """one image at IMAGE_SHAPE and one of another size through detect(render=True, mask_format="rle"): the overlay is detect(render=True)'s,
+    and every run-length mask decodes to the dense plane"""
+    from myolo import rle
+    cfg, m, imgs = _pairs()
+    im = imgs[k]
+    dense = m.detect(im, cs_threshold=0.0, render=True, save_path=None)[0]
+    coded = m.detect(im, cs_threshold=0.0, render=True, save_path=None, mask_format="rle")[0]
+    n = len(dense["class_ids"])
+    assert n >= 1 and list(coded) == ["bboxes", "class_ids", "confidence_scores", "rle_masks", "rendered"] and len(coded["rle_masks"]) == n
+    for key in ("bboxes", "class_ids", "confidence_scores", "rendered"):
+        assert coded[key].dtype == dense[key].dtype and np.array_equal(coded[key], dense[key]), key
+    assert dense["rendered"].shape == im.shape and (dense["rendered"] != im).any()
+    for i, code in enumerate(coded["rle_masks"]):
+        assert code["size"] == list(im.shape[:2]) and np.array_equal(rle.decode(code), dense["full_masks"][:, :, i]), i
+    assert dense["full_masks"].any()
