@@ -1,0 +1,76 @@
+#!/usr/bin/env python
+"""Train and evaluate Mask-YOLO on a dataset in the COCO instance format (an instances_*.json and a folder of images) on one MI355X.  The
+segmentations -- polygon parts and run-length codes -- are decoded on the device, for the training batches and for evaluate()'s ground truth
+(DESIGN section 18): no mask is built on the host.  After training the validation set is scored (MaskYOLO.evaluate) and its detections are
+written as a COCO results file, category ids mapped back through the dataset.
+
+  python example/coco/train_coco.py TRAIN_JSON TRAIN_IMAGES [--val-json PATH --val-images DIR] [--categories 1,3,17] [--keep-crowd]
+                                    [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--results PATH]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
+from myolo import rle                                # noqa: E402
+from myolo.augment import Augmentation               # noqa: E402
+from myolo.coco import load_coco                     # noqa: E402
+from myolo.config import Config, make_config         # noqa: E402
+from myolo.model import MaskYOLO                     # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("train_json", help="COCO instance annotations of the training images")
+    ap.add_argument("train_images", help="the directory their file_name entries are relative to")
+    ap.add_argument("--val-json")
+    ap.add_argument("--val-images")
+    ap.add_argument("--categories", help="comma-separated COCO category ids to keep, in class order (default: all of the file, ascending)")
+    ap.add_argument("--keep-crowd", action="store_true", help="keep iscrowd annotations as ordinary instances (default: skip them)")
+    ap.add_argument("--epochs", type=int, default=30)
+    ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--logs", default="./logs")
+    ap.add_argument("--no-augment", action="store_true")
+    ap.add_argument("--host-masks", action="store_true", help="decode the segmentations on the host (load_mask) for the training batches")
+    ap.add_argument("--results", default=None, help="where the validation detections go as a COCO results file (default: LOGS/coco_results.json)")
+    a = ap.parse_args()
+
+    cats = [int(c) for c in a.categories.split(",")] if a.categories else None
+    crowd = "keep" if a.keep_crowd else "skip"
+    train = load_coco(a.train_json, a.train_images, category_ids=cats, crowd=crowd)
+    val = load_coco(a.val_json, a.val_images or a.train_images, category_ids=train.category_ids[1:], crowd=crowd) if a.val_json else None
+    print("train: %d images, classes %s" % (len(train.image_ids), train.class_names))
+    config = make_config(Config, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch, NUM_CLASSES=train.num_classes, LABELS=train.class_names)
+    augmentation = None if a.no_augment else Augmentation(fliplr=.5, scale=(.8, 1.2), translate=(-.1, .1), rotate=(-15, 15),
+                                                          brightness=(.8, 1.2))
+    model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)
+    hist = model.train(train, val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all', augmentation=augmentation,
+                       device_polygons=not a.host_masks)
+    print("epoch losses:", ["%.4f" % h for h in hist])
+    print("batches decoded on the device: %d of %d" % (model.host_times["segment_batches"], model.host_times["steps"]))
+    os.makedirs(a.logs, exist_ok=True)
+    weights = os.path.join(a.logs, "mask_yolo_coco_final.npz")
+    model.save_weights(weights)
+
+    if val is not None:
+        infer = MaskYOLO(mode="inference", config=config)
+        infer.load_weights(weights)
+        r = infer.evaluate(val)
+        print("validation: mask AP50 %.4f, mask AP %.4f, box AP50 %.4f, box AP %.4f over %d images (%d instances, %d detections)" %
+              (r["mask_ap50"], r["mask_ap"], r["box_ap50"], r["box_ap"], r["n_images"], r["n_gt"], r["n_det"]))
+        out, ids = [], list(val.image_ids)
+        for lo in range(0, len(ids), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
+            chunk = ids[lo:lo + 8 * a.batch]
+            results = infer.detect_many([val.load_image(i) for i in chunk], mask_format="rle")
+            out += rle.coco_results(results, [val.image_info[i]["id"] for i in chunk], category_ids=val.category_ids)
+        path = a.results or os.path.join(a.logs, "coco_results.json")
+        with open(path, "w") as f:
+            json.dump(out, f)
+        print("wrote %d detections to %s" % (len(out), path))
+
+
+if __name__ == "__main__":
+    main()

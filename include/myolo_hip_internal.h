@@ -392,6 +392,26 @@ int myolo_resize_images_u8(const uint8_t* src, size_t src_bytes,
                            float* out_unit,          /* [B,H,W,3] or NULL; at least one of the two */
                            int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- segment rasteriser (myolo/coco.py datasets, csrc/segment_kernels.hip; contract: DESIGN.md section 18).  Declared here rather than in the
+ * operator API (myolo_hip.h, held to 70 entries).  myolo_polygon_masks for COCO segmentations: the slot b*T+t holds any number of polygon parts and /
+ * or one run-length code, and masks[b,i,j,t] = 1 when source pixel (r, c) = (src_row[b,i], src_col[b,j]) is ON in any of the slot's parts under the
+ * polygon rasteriser's rule (every part with its own start vertex, parities and vertex flag: a union, not even-odd across parts), or when the number
+ * of the slot's boundaries <= c * src_h[b] + r is odd.  A slot with neither parts nor boundaries is empty (an all-zero code has no boundary, an
+ * all-one code the single boundary 0).  No limit on parts, vertices, runs or T; the offsets are trusted.  boxes, when given, receives the tight box of
+ * every slot's set pixels in the output frame (integer atomicMin / atomicMax: the same from run to run).
+ * MYOLO_EINVAL (message "segment_masks: ...", nothing launched) for a null pointer other than verts, bounds and boxes, and for B, H, W, T <= 0. */
+int myolo_segment_masks(const double* verts,        /* [n_verts,2] (row, col), source-image pixels; may be NULL when there is no part */
+                        const int32_t* part_off,    /* [n_parts+1] offsets into verts */
+                        const int32_t* slot_part,   /* [B*T+1] offsets into part_off: the parts of slot k */
+                        const int32_t* bounds,      /* [n_bounds] running sums of a code's counts without the final total, ascending, duplicates allowed */
+                        const int32_t* slot_bound,  /* [B*T+1] offsets into bounds */
+                        const int32_t* src_h,       /* [B] source image height (the stride of p = col * h + row) */
+                        const int32_t* src_row,     /* [B,H] source row that output row i samples */
+                        const int32_t* src_col,     /* [B,W] */
+                        uint8_t* masks,             /* [B,H,W,T] 0/1, EVERY element written */
+                        int32_t* boxes,             /* [B,T,4] x1,y1,x2,y2 (far corner exclusive), 0,0,0,0 for a slot without a set pixel; or NULL */
+                        int B, int H, int W, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

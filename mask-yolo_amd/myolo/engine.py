@@ -2030,6 +2030,37 @@ class Net(object):
             return d
         return self._stage_upload(spec, fill, finish)
 
+    def stage_segments(self, fill, n, augmenter, yolo=False, n_verts=0, n_parts=0, n_bounds=0):
+        """stage_polygons for COCO segments (myolo.coco datasets): fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64 [cap,2], part
+        offsets int32 [cap+1], slot -> part offsets int32 [n*T+1], boundaries int32 [cap], slot -> boundary offsets int32 [n*T+1], source heights
+        int32 [n], class ids int32 [n,T], source-row table int32 [n,H], source-column table int32 [n,W], parameter rows float64 [n,8]]
+        (BatchGenerator.segment_batch).  Behind the copies, on the copy stream, myolo_segment_masks decodes the segments into a device [n,H,W,T]
+        buffer (no boxes: the augmenter derives them from the warped masks) and `augmenter` takes it from there.
+        n_verts, n_parts, n_bounds: what fill will write; each pinned buffer holds the next power of two (at least 1024, 64, 1024), so that
+        batches of different segments share a few staging shapes."""
+        cfg, dev = self.cfg, self.dev
+        H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
+
+        def cap(need, least):
+            while least < need:
+                least *= 2
+            return least
+        spec = [("raw_images", (n, H, W, 3), torch.uint8), ("seg_verts", (cap(n_verts, 1024), 2), torch.float64),
+                ("seg_part_off", (cap(n_parts, 64) + 1,), torch.int32), ("seg_slot_part", (n * T + 1,), torch.int32),
+                ("seg_bounds", (cap(n_bounds, 1024),), torch.int32), ("seg_slot_bound", (n * T + 1,), torch.int32), ("seg_src_h", (n,), torch.int32),
+                ("src_ids", (n, T), torch.int32), ("src_row", (n, H), torch.int32), ("src_col", (n, W), torch.int32),
+                ("aug_params", (n, 8), torch.float64)]
+
+        def finish(out):
+            masks = torch.empty((n, H, W, T), dtype=torch.uint8, device=dev)
+            tables = tuple(out[k] for k in ("seg_verts", "seg_part_off", "seg_slot_part", "seg_bounds", "seg_slot_bound", "seg_src_h", "src_row",
+                                            "src_col"))
+            X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(masks), None, n, H, W, T, X.stream())
+            d = augmenter.apply(out["raw_images"], masks, out["src_ids"], out["aug_params"], yolo=yolo)
+            d["_seg_src"] = tables                          # read asynchronously, like _poly_src
+            return d
+        return self._stage_upload(spec, fill, finish)
+
     def _stage_upload(self, spec, fill, finish):
         """one staging set of the ring: fill(arrays) into its pinned buffers (one per (name, shape, dtype) of `spec`), the asynchronous copies
         into fresh device tensors on the copy stream, then finish(dict) -> dict there (device work that belongs behind the copies); the

@@ -246,8 +246,9 @@ class MaskYOLO(object):
         self.net = self.build(mode=mode, config=self.config)
         self.keras_model = _KerasModelShim(self)
         self.epoch = 0
-        # train(): where the launch thread's wall time goes; polygon_batches = the batches that came through Net.stage_polygons
-        self.host_times = {"wait_for_batch_s": 0.0, "launch_step_s": 0.0, "steps": 0, "polygon_batches": 0}
+        # train(): where the launch thread's wall time goes; polygon_batches / segment_batches = the batches that came through
+        # Net.stage_polygons / Net.stage_segments
+        self.host_times = {"wait_for_batch_s": 0.0, "launch_step_s": 0.0, "steps": 0, "polygon_batches": 0, "segment_batches": 0}
 
     # ------------------------------------------------------------------ build
     def build(self, mode, config):
@@ -393,7 +394,9 @@ class MaskYOLO(object):
         device_polygons: a train_dataset that has load_polygons (myolo.via.VIADataset) is never asked for a mask: its outlines go to the device
         and are filled there, in front of the device augmenter (identity rows with augmentation=None) -- DESIGN.md section 13.  An outline that
         fills no pixel is dropped on the device, AFTER the sub-sampling to TRUE_BOX_BUFFER instances (the host route drops it before).
-        False, or a dataset without load_polygons: load_mask and the host route.  Validation batches always use load_mask."""
+        A train_dataset that has load_segments (myolo.coco.COCODataset) goes the same way under the same flag -- "annotations decoded on the
+        device": its polygon parts and run-length codes are decoded by myolo_segment_masks.
+        False, or a dataset with neither: load_mask and the host route.  Validation batches always use load_mask."""
         layer_regex = {"all": ".*"}
         if layers in layer_regex:
             layers = layer_regex[layers]
@@ -415,8 +418,11 @@ class MaskYOLO(object):
             return info
 
         polygon_route = bool(device_polygons) and hasattr(train_dataset, "load_polygons")
+        segment_route = bool(device_polygons) and not polygon_route and hasattr(train_dataset, "load_segments")
         if polygon_route:
             train_info = self._collect_polygons(train_dataset, max_samples)
+        elif segment_route:
+            train_info = self._collect_segments(train_dataset, max_samples)
         else:
             train_info = collect(train_dataset, tag=augmentation is not None)
         val_info = collect(val_dataset) if val_dataset is not None else []
@@ -452,6 +458,8 @@ class MaskYOLO(object):
         make_item = lambda it: make(it[1])             # noqa: E731
         if polygon_route:
             make_item = self._polygon_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
+        elif segment_route:
+            make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
         elif augmentation is not None:
             make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
 
@@ -580,6 +588,67 @@ class MaskYOLO(object):
             fill, n_verts = gen.polygon_batch(i, row_of)
             db = self.net.stage_polygons(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts)
             self.host_times["polygon_batches"] += 1
+            return db
+        return make
+
+    def _collect_segments(self, dataset, max_samples=None, first=None):
+        """_collect_polygons for a dataset with load_segments (myolo.coco): per image [image resized to the network frame uint8, class ids int32 [n],
+        segments (a list of float64 [k,2] (row, col) parts, or a run-length code {"size", "counts"}), (source-row table int32 [H], source-column
+        table int32 [W]), dataset image id, source image height].  first: keep an image's first `first` segments only (evaluate())."""
+        cfg = self.config
+        if cfg.USE_MINI_MASK:
+            raise NotImplementedError("mini-masks are outside the hot path")
+        H, W = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1]
+        ids = list(dataset.image_ids)
+        if max_samples is not None:
+            ids = ids[:max_samples]
+        info = []
+        for i in ids:
+            image = dataset.load_image(i)
+            segs, class_ids = dataset.load_segments(i)
+            class_ids = np.asarray(class_ids, dtype=np.int32)
+            h, w = image.shape[:2]
+            if len(segs) != class_ids.shape[0]:
+                raise ValueError("load_segments(%r): %d segments but %d class ids" % (i, len(segs), class_ids.shape[0]))
+            for s in segs:
+                if isinstance(s, dict):
+                    c = np.asarray(s["counts"])
+                    ok = list(s["size"]) == [h, w] and h * w < 1 << 31 and c.ndim == 1 and c.size > 0 and (c >= 0).all() and int(c.sum()) == h * w
+                else:
+                    ok = all(isinstance(p, np.ndarray) and p.dtype == np.float64 and p.ndim == 2 and p.shape[1] == 2 and p.shape[0] > 0 and
+                             np.isfinite(p).all() for p in s)
+                if not ok:
+                    raise ValueError("load_segments(%r): a segment is a list of finite float64 [k,2] (row, col) parts with k >= 1, or a run-length "
+                                     "code whose counts are >= 0 and sum to the %d x %d image" % (i, h, w))
+            scale = [1, 1]
+            if [h, w] != [H, W]:
+                image, scale = mutils.resize_image(image, cfg.IMAGE_SHAPE)
+            rows, cols = mutils.mask_index_tables(h, w, scale)
+            if rows.shape[0] != H or cols.shape[0] != W:
+                raise ValueError("image %r: %d x %d does not resize to the %d x %d network frame" % (i, h, w, H, W))
+            if first is not None:
+                segs, class_ids = list(segs)[:first], class_ids[:first]
+            info.append([image, class_ids, list(segs), (rows.astype(np.int32), cols.astype(np.int32)), int(i), int(h)])
+        return info
+
+    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+        """_polygon_batches on the segment route: Net.stage_segments decodes the segments behind the copies, then the device augmenter runs."""
+        from .augment import DeviceAugmenter, IDENTITY_ROW
+        if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
+            raise ValueError("train() on a dataset with load_segments needs uint8 images (or device_polygons=False)")
+        aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
+
+        def make(it):
+            epoch, i = it
+            lo, hi = gen.batch_bounds(i)
+
+            def row_of(inst):
+                if augmentation is None:
+                    return IDENTITY_ROW
+                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
+            fill, n_verts, n_parts, n_bounds = gen.segment_batch(i, row_of)
+            db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds)
+            self.host_times["segment_batches"] += 1
             return db
         return make
 
@@ -736,6 +805,8 @@ class MaskYOLO(object):
         An image's ground truth is its first MAX_GT_INSTANCES instances (what a training batch carries)."""
         cfg = self.config
         assert self.mode == 'inference'
+        if hasattr(dataset, "load_segments"):          # (myolo.coco: the ground truth is decoded on the device, load_mask is never called)
+            return self._evaluate_segments(dataset, cs_threshold, max_samples, in_flight)
         if hasattr(dataset, "image_ids"):
             ids = list(dataset.image_ids)
             if max_samples is not None:
@@ -770,6 +841,47 @@ class MaskYOLO(object):
                 yield x
         return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
 
+    def _evaluate_segments(self, dataset, cs_threshold, max_samples, in_flight):
+        """evaluate() on a dataset with load_segments (myolo.coco): per batch the image bytes, the segments of every image's
+        first MAX_GT_INSTANCES annotations and the index tables go up, and myolo_segment_masks writes the ground-truth masks and their boxes on the
+        device -- no mask is filled on the host, no [B,H,W,T] bytes cross PCIe.  A segment that sets no pixel of the network frame is found by its
+        area (myolo_mask_overlap_counts' area_gt) and made padding in _evaluate_stream: it is dropped AFTER the cut to MAX_GT_INSTANCES, where
+        load_image_gt drops it before (with at most MAX_GT_INSTANCES segments per image the two routes give equal results)."""
+        from . import _ext as X
+        cfg = self.config
+        B, T = int(cfg.BATCH_SIZE), int(cfg.MAX_GT_INSTANCES)
+        H, W = int(cfg.IMAGE_SHAPE[0]), int(cfg.IMAGE_SHAPE[1])
+        info = self._collect_segments(dataset, max_samples, first=T)
+        stager = self._stager()
+        stager.reserve(in_flight)
+        dev = self.net.dev
+        truth = collections.deque()
+
+        def batches():
+            for bi, lo in enumerate(range(0, len(info), B)):
+                grp = info[lo:lo + B]
+                x, _ = stager.stage(bi, [r[0] for r in grp])
+                per_image = [r[2] for r in grp]
+                n_verts, n_parts, n_bounds = mutils.segment_sizes(per_image)
+                verts, part_off = np.zeros((max(n_verts, 1), 2), np.float64), np.zeros(n_parts + 1, np.int32)
+                bounds = np.zeros(max(n_bounds, 1), np.int32)
+                slot_part, slot_bound = np.zeros(B * T + 1, np.int32), np.zeros(B * T + 1, np.int32)
+                mutils.pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound)
+                # (the slots of a short last batch's padding are empty; their tables name pixel (0, 0))
+                src_h, rows, cols = np.ones(B, np.int32), np.zeros((B, H), np.int32), np.zeros((B, W), np.int32)
+                gt_ids = np.zeros((B, T), np.int32)
+                for k, r in enumerate(grp):
+                    gt_ids[k, :r[1].shape[0]] = r[1]
+                    rows[k], cols[k] = r[3]
+                    src_h[k] = r[5]
+                tables = [torch.from_numpy(a).to(dev) for a in (verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols)]
+                gt_masks = torch.empty((B, H, W, T), dtype=torch.uint8, device=dev)
+                gt_boxes = torch.empty((B, T, 4), dtype=torch.int32, device=dev)
+                X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(gt_masks), X.ptr(gt_boxes), B, H, W, T, X.stream())
+                truth.append((len(grp), gt_masks, gt_ids, gt_boxes, True))
+                yield x
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+
     def evaluate_shapes_stream(self, n_images, seed=0, start_index=0, cs_threshold=0.35, in_flight=3):
         """evaluate() on images start_index .. start_index + n_images - 1 of the synthetic Shapes stream with the inputs AND the ground truth
         produced on the device (myolo.shapes.ShapesProducer: bit-identical to ShapesDataset / load_image_gt): nothing but the detections' rows and
@@ -790,15 +902,19 @@ class MaskYOLO(object):
 
     def _evaluate_stream(self, batches, truth, cs_threshold, in_flight):
         """the common part of evaluate() / evaluate_shapes_stream(): `batches` yields [B,H,W,3] device images and appends each batch's
-        (images that count, gt_masks [B,H,W,T] device, gt_ids [B,T], gt_boxes [B,T,4] host or device) to the deque `truth`."""
+        (images that count, gt_masks [B,H,W,T] device, gt_ids [B,T], gt_boxes [B,T,4] host or device) to the deque `truth`; a fifth element True
+        (_evaluate_segments): a slot whose ground-truth plane is empty is padding whatever its class id."""
         from .evaluate import Evaluator
         ev = Evaluator()
         for _, det_d, mask_d in self.net.predict_stream(batches, in_flight=in_flight):
-            n, gt_d, gt_ids, gt_boxes = truth.popleft()
+            entry = truth.popleft()
+            n, gt_d, gt_ids, gt_boxes = entry[:4]
+            drop_empty = len(entry) > 4
             selection = D.Selection(det_d.cpu().numpy(), n, cs_threshold, self.config.IMAGE_SHAPE)
             inter, area_pred, area_gt, win = D.overlap_counts(self._stager(), det_d, mask_d, selection, gt_d)
-            if torch.is_tensor(gt_ids):
-                gt_ids, gt_boxes = gt_ids.cpu().numpy(), gt_boxes.cpu().numpy()
+            gt_ids, gt_boxes = [t.cpu().numpy() if torch.is_tensor(t) else t for t in (gt_ids, gt_boxes)]
+            if drop_empty:
+                gt_ids = np.where(area_gt[:gt_ids.shape[0]] > 0, gt_ids, 0)
             for k in range(n):
                 _, class_ids, scores = selection.picked[k]
                 m = len(scores)

@@ -177,6 +177,55 @@ def load_image_gt(dataset, config, image_id, augment=False, augmentation=None, u
     return image, class_ids, bbox, mask
 
 
+def segment_sizes(per_image):
+    """-> (n_verts, n_parts, n_bounds) of the segments of a batch (a list of segments per image, myolo.coco): what pack_segments will write."""
+    n_verts = n_parts = n_bounds = 0
+    for segs in per_image:
+        for s in segs:
+            if isinstance(s, dict):
+                n_bounds += len(s["counts"]) - 1
+            else:
+                n_parts += len(s)
+                n_verts += sum(p.shape[0] for p in s)
+    return n_verts, n_parts, n_bounds
+
+
+def pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound):
+    """The tables myolo_segment_masks reads, written INTO the caller's arrays: image k's segment j (at most T per image; a list of float64 [n,2] parts
+    or a run-length code {"size", "counts"}) is slot k * T + j.  verts float64 [>= n_verts,2] and part_off int32 [>= n_parts+1] hold the parts slot
+    after slot, slot_part int32 [>= B*T+1] the first part of every slot; bounds int32 [>= n_bounds] the running sums of every code's counts without
+    the final total, slot_bound int32 [>= B*T+1] the first of every slot.  Slots beyond an image's segments, and images beyond len(per_image), are
+    empty."""
+    n_verts, n_parts, n_bounds = segment_sizes(per_image)
+    if n_verts > verts.shape[0] or n_parts + 1 > part_off.shape[0] or n_bounds > bounds.shape[0]:
+        raise ValueError("pack_segments: %d vertices, %d parts, %d boundaries do not fit the %d, %d, %d staged" %
+                         (n_verts, n_parts, n_bounds, verts.shape[0], part_off.shape[0] - 1, bounds.shape[0]))
+    if len(per_image) * T + 1 > min(slot_part.shape[0], slot_bound.shape[0]):
+        raise ValueError("pack_segments: %d images of %d slots do not fit the slot tables" % (len(per_image), T))
+    v = p = q = 0
+    part_off[0] = 0
+    for k, segs in enumerate(per_image):
+        if len(segs) > T:
+            raise ValueError("pack_segments: image %d has %d segments for %d slots" % (k, len(segs), T))
+        for j in range(T):
+            slot_part[k * T + j], slot_bound[k * T + j] = p, q
+            if j >= len(segs):
+                continue
+            s = segs[j]
+            if isinstance(s, dict):
+                m = len(s["counts"]) - 1
+                bounds[q:q + m] = np.cumsum(np.asarray(s["counts"], np.int64))[:-1]
+                q += m
+            else:
+                for part in s:
+                    verts[v:v + part.shape[0]] = part
+                    v += part.shape[0]
+                    p += 1
+                    part_off[p] = v
+    slot_part[len(per_image) * T:] = p
+    slot_bound[len(per_image) * T:] = q
+
+
 class BatchGenerator(object):
     """Target encoding + batching (myolo_utils.py:689-860).  __getitem__ returns
     ([images f32, true_boxes f64, y_true f64, gt_class_ids i32, gt_boxes i32, gt_masks bool], [])
@@ -317,6 +366,39 @@ class BatchGenerator(object):
             off[len(picked) * T] = o
             return out
         return fill, n_verts
+
+    def segment_batch(self, idx, row_of):
+        """polygon_batch for segments (myolo.coco datasets, Net.stage_segments): the samples are [resized image uint8, class ids int32 [n], segments,
+        (source-row table [H], source-column table [W]), dataset image id, source image height].  -> (fill, n_verts, n_parts, n_bounds): fill(out)
+        writes batch idx INTO out = [raw images uint8 [n,H,W,3], vertices float64 [>= n_verts,2], part offsets int32 [>= n_parts+1], slot -> part
+        offsets int32 [n*T+1], boundaries int32 [>= n_bounds], slot -> boundary offsets int32 [n*T+1], source heights int32 [n], class ids int32
+        [n,T], source rows int32 [n,H], source columns int32 [n,W], parameter rows float64 [n,8]] (pack_segments).  More than T segments are
+        sub-sampled with the one np.random.choice draw fill_raw makes, before anything is rasterised (polygon_batch's caveat)."""
+        l_bound, r_bound = self.batch_bounds(idx)
+        T = self.config.TRUE_BOX_BUFFER
+        picked = []
+        for inst in self.all_info[l_bound:r_bound]:
+            class_ids, segs = inst[1], inst[2]
+            if inst[0].dtype != np.uint8:
+                raise ValueError("the segment route needs uint8 images, got %s" % inst[0].dtype)
+            if class_ids.shape[0] > T:
+                ids = np.random.choice(np.arange(class_ids.shape[0]), T, replace=False)
+                class_ids, segs = class_ids[ids], [segs[j] for j in ids]
+            picked.append((inst, class_ids, segs))
+        n_verts, n_parts, n_bounds = segment_sizes([segs for _, _, segs in picked])
+
+        def fill(out):
+            images, verts, part_off, slot_part, bounds, slot_bound, src_h, ids_b, rows_t, cols_t, rows = out
+            pack_segments([segs for _, _, segs in picked], T, verts, part_off, slot_part, bounds, slot_bound)
+            ids_b.fill(0)
+            for k, (inst, class_ids, _) in enumerate(picked):
+                images[k] = inst[0]
+                ids_b[k, :class_ids.shape[0]] = class_ids
+                rows_t[k], cols_t[k] = inst[3]
+                src_h[k] = inst[5]
+                rows[k] = row_of(inst)
+            return out
+        return fill, n_verts, n_parts, n_bounds
 
     def _encode(self, l_bound, r_bound, images, true_boxes, y_true, gt_ids, gt_boxes_b, gt_masks_b):
         """the body of myolo_utils.py:748-844 on zero-initialised outputs."""
