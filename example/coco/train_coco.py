@@ -6,6 +6,10 @@ written as a COCO results file, category ids mapped back through the dataset.
 
   python example/coco/train_coco.py TRAIN_JSON TRAIN_IMAGES [--val-json PATH --val-images DIR] [--categories 1,3,17] [--keep-crowd]
                                     [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--results PATH]
+                                    [--fit-anchors K]
+
+--fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
+Config's, which were fitted to UECFOOD100 at 224 x 224.
 """
 import argparse
 import json
@@ -15,6 +19,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 from myolo import rle                                # noqa: E402
+from myolo.anchors import fit_anchors                # noqa: E402
 from myolo.augment import Augmentation               # noqa: E402
 from myolo.coco import load_coco                     # noqa: E402
 from myolo.config import Config, make_config         # noqa: E402
@@ -35,6 +40,7 @@ def main():
     ap.add_argument("--logs", default="./logs")
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--host-masks", action="store_true", help="decode the segmentations on the host (load_mask) for the training batches")
+    ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: Config's anchors)")
     ap.add_argument("--results", default=None, help="where the validation detections go as a COCO results file (default: LOGS/coco_results.json)")
     a = ap.parse_args()
 
@@ -43,7 +49,12 @@ def main():
     train = load_coco(a.train_json, a.train_images, category_ids=cats, crowd=crowd)
     val = load_coco(a.val_json, a.val_images or a.train_images, category_ids=train.category_ids[1:], crowd=crowd) if a.val_json else None
     print("train: %d images, classes %s" % (len(train.image_ids), train.class_names))
-    config = make_config(Config, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch, NUM_CLASSES=train.num_classes, LABELS=train.class_names)
+    overrides = dict(IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch, NUM_CLASSES=train.num_classes, LABELS=train.class_names)
+    if a.fit_anchors:
+        fitted = fit_anchors(train, make_config(Config, **overrides), a.fit_anchors)
+        print("anchors fitted to the training set (mean IoU %.4f): %s" % (fitted.mean_iou[fitted.best], ["%.2f" % v for v in fitted.anchors]))
+        overrides.update(fitted.overrides())
+    config = make_config(Config, **overrides)
     augmentation = None if a.no_augment else Augmentation(fliplr=.5, scale=(.8, 1.2), translate=(-.1, .1), rotate=(-15, 15),
                                                           brightness=(.8, 1.2))
     model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)

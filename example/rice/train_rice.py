@@ -4,7 +4,10 @@ example/rice/train_rice.py and rice_dataset.py (RiceConfig, a dataset of <dir>/t
 via_*_annotation.json, MaskYOLO(mode="training"), model.train(...)).  The outlines are rasterised on the device: no mask
 is built on the host.
 
-  python example/rice/train_rice.py DATASET_DIR [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks]
+  python example/rice/train_rice.py DATASET_DIR [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--fit-anchors K]
+
+--fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
+RiceConfig's.
 """
 import argparse
 import os
@@ -12,6 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
+from myolo.anchors import fit_anchors                # noqa: E402
 from myolo.augment import Augmentation               # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
@@ -27,10 +31,15 @@ def main():
     ap.add_argument("--logs", default="./logs")
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--host-masks", action="store_true", help="fill the outlines on the host (load_mask) instead of on the device")
+    ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: RiceConfig's anchors)")
     a = ap.parse_args()
 
     config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
     dataset_train = load_via(a.dataset, "train")
+    if a.fit_anchors:
+        fitted = fit_anchors(dataset_train, config, a.fit_anchors)
+        print("anchors fitted to the training set (mean IoU %.4f): %s" % (fitted.mean_iou[fitted.best], ["%.2f" % v for v in fitted.anchors]))
+        config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch, **fitted.overrides())
     dataset_val = load_via(a.dataset, "val") if os.path.isdir(os.path.join(a.dataset, "val")) else None
     print("train: %d images, classes %s" % (len(dataset_train.image_ids), dataset_train.class_names))
     augmentation = None if a.no_augment else Augmentation(fliplr=.5, scale=(.8, 1.2), translate=(-.1, .1), rotate=(-15, 15),

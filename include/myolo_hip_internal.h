@@ -412,6 +412,26 @@ int myolo_segment_masks(const double* verts,        /* [n_verts,2] (row, col), s
                         int32_t* boxes,             /* [B,T,4] x1,y1,x2,y2 (far corner exclusive), 0,0,0,0 for a slot without a set pixel; or NULL */
                         int B, int H, int W, int T, void* stream);
 
+/* ---- anchor fitting (myolo/anchors.py, csrc/anchors_kernels.hip; contract: DESIGN.md section 19).  Declared here rather than in the operator API
+ * (myolo_hip.h, held to 70 entries).  k-means over box sizes with 1 - IoU as the distance, `runs` independent runs in ONE call: run r has its own
+ * k = run_k[r] (1 .. 32) and its own initial centroids (w, h) in centroids[r, 0 .. k), which the call replaces by the fitted ones (rows >= k are not
+ * touched).  All in binary64 without contraction: inter = min(w, cw) * min(h, ch), iou = inter / ((w * h + cw * ch) - inter), d = 1.0 - iou, a point
+ * goes to the lowest index of the smallest d.  After an assignment pass that changed nothing the run is converged; otherwise a non-empty cluster's
+ * centroid becomes (double)sum / (double)count (64-bit integer sums: exact, the same bits from run to run) and an EMPTY cluster keeps its centroid.
+ * iterations = assignment passes made (<= max_iter); converged = 0 for a run that max_iter stopped: its centroids are those of the last update.
+ * counts and assign (NULL: not written) are the last pass's; mean_iou = the mean over the points of the largest IoU against the final centroids,
+ * summed from per-workgroup partials in index order (no floating-point atomics).
+ * wh, centroids, counts, iterations, converged, mean_iou, assign, ws are DEVICE pointers, wh holding values >= 1; run_k is read on the host before
+ * anything is launched.  The host drives the passes (one pair of launches each, a finished run's workgroups return at once, its flags are read every
+ * few passes), and the call SYNCHRONISES the stream before it returns: the outputs are final then.
+ * MYOLO_EINVAL (message "anchor_kmeans: ...", nothing launched) for a null pointer other than assign, n < 1, runs < 1, a k outside 1 .. 32,
+ * max_iter < 1, and a workspace under myolo_anchor_kmeans_ws_bytes(n, runs). */
+size_t myolo_anchor_kmeans_ws_bytes(int64_t n, int runs);
+int    myolo_anchor_kmeans(const int32_t* wh /*[n,2] device*/, int64_t n, const int32_t* run_k /*host [runs]*/,
+                           double* centroids /*[runs,32,2] in/out*/, int runs, int max_iter, int64_t* counts /*[runs,32]*/,
+                           int32_t* iterations /*[runs]*/, int32_t* converged /*[runs]*/, double* mean_iou /*[runs]*/,
+                           int32_t* assign /*[runs,n] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

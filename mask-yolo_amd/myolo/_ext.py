@@ -138,6 +138,7 @@ SIGS = {
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
     "myolo_render_instances": [P, P, Z, P, P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, P, Z, P],
+    "myolo_anchor_kmeans": [P, L, P, P, I, I, P, P, P, P, P, P, Z, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],
@@ -223,6 +224,8 @@ def load():
     lib.myolo_resize_images_ws_bytes.restype = Z
     lib.myolo_rle_masks_ws_bytes.argtypes = [I, I, I]
     lib.myolo_rle_masks_ws_bytes.restype = Z
+    lib.myolo_anchor_kmeans_ws_bytes.argtypes = [L, I]
+    lib.myolo_anchor_kmeans_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
     lib.myolo_wprep_refresh.restype = I
     _LIB = lib
@@ -235,7 +238,7 @@ def exported_symbols():
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
                               "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_resize_images_ws_bytes",
-                              "myolo_rle_masks_ws_bytes"]
+                              "myolo_rle_masks_ws_bytes", "myolo_anchor_kmeans_ws_bytes"]
 
 
 def ptr(t):
@@ -450,6 +453,10 @@ def resize_ws_bytes(b):
 
 def rle_masks_ws_bytes(b, k, max_w):
     return int(load().myolo_rle_masks_ws_bytes(int(b), int(k), int(max_w)))
+
+
+def anchor_kmeans_ws_bytes(n, runs):
+    return int(load().myolo_anchor_kmeans_ws_bytes(int(n), int(runs)))
 
 
 def workspace_bytes(rows, cin, cout):
