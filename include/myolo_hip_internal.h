@@ -365,6 +365,29 @@ int myolo_augment_batch(const uint8_t* src_images,   /* [B,H,W,3] */
                         int B, int H, int W, int T, int G, int A, int C,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mosaic (myolo/augment.py: Mosaic; arithmetic contract: DESIGN.md "Mosaic").  myolo_augment_batch with four tiles per output image: pixel
+ * (x, y) of image b lies in tile q = (x >= cx) + 2 * (y >= cy), (cx, cy) = centre[b], and is sampled from image quad_src[b][q] of the same batch
+ * through the row quad_rows[b][q] by the formulas above.  The instance candidates of an image are the 4T pairs (q, t) in q-major order, live iff
+ * src_class_ids[quad_src[b][q]][t] != 0; a candidate covers a pixel of tile q whose source mask tap is set; a candidate with no pixel is dropped,
+ * the first T survivors fill slots 0..T-1 in order, the others are discarded (their pixels are in no output mask) and counted in dropped[b].
+ * Boxes, ids and targets as above.  With quad_src[b] = {b,b,b,b}, quad_rows[b][q] = params[b] and centre (W, H) every output equals
+ * myolo_augment_batch's byte for byte.  The tables are device memory and are NOT read on the host: the caller (DeviceAugmenter) refuses sources
+ * outside [0, B) and centres outside [0, W] x [0, H] before it uploads them; the kernels only keep a bad source index from becoming an address.
+ * T <= 32.  ws: myolo_mosaic_batch_ws_bytes(B, T). */
+size_t myolo_mosaic_batch_ws_bytes(int B, int T);
+int myolo_mosaic_batch(const uint8_t* src_images,   /* [B,H,W,3] */
+                       const uint8_t* src_masks,    /* [B,H,W,T] 0/1 */
+                       const int32_t* src_class_ids,/* [B,T], 0 = empty slot */
+                       const int32_t* quad_src,     /* [B,4] batch positions */
+                       const double*  quad_rows,    /* [B,4,8]: a params row per tile */
+                       const int32_t* centre,       /* [B,2]: cx, cy */
+                       double cval, const double* anchors /* [2A] */,
+                       float* images, uint8_t* gt_masks, int32_t* gt_boxes, int32_t* gt_class_ids,
+                       float* y_true /* [B,G,G,A,5+C], or NULL with true_boxes */, float* true_boxes /* [B,T,4] */,
+                       int32_t* dropped /* [B] */,
+                       int B, int H, int W, int T, int G, int A, int C,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* ---- polygon rasteriser (myolo/via.py datasets, csrc/polygon_kernels.hip; arithmetic contract: DESIGN.md "Polygon annotations").  Fills the
  * outlines of a batch into the instance masks myolo_augment_batch reads: masks[b,i,j,t] = 1 when skimage.draw.polygon (0.18.3) lists source pixel
  * (src_row[b,i], src_col[b,j]) for the polygon of slot b*T+t.  The two tables are made on the host by the rule of resize_mask (the identity for an

@@ -6,12 +6,16 @@ draws one row of eight doubles per image -- Augmentation.params() -- and the war
 inputs (DeviceAugmenter -> myolo_augment_batch, csrc/augment_kernels.hip): bilinear image, nearest-neighbour masks, empty instances
 dropped, boxes re-derived from the warped masks, YOLO targets encoded from those boxes.  The arithmetic is a bit-exact contract, stated
 in DESIGN.md ("On-device augmentation") and restated in numpy by tests/augment_ref.py.
+
+Mosaic (MaskYOLO.train(mosaic=Mosaic(...))) composes every sample from four images of its batch: the host plans three small tables per batch
+(Mosaic.plan, Mosaic.compose) and the same augmenter runs myolo_mosaic_batch on them -- DESIGN.md ("Mosaic"), tests/mosaic_ref.py.
 """
 import math
 
 import numpy as np
 
 IDENTITY_ROW = np.array([1., 0., 0., 0., 1., 0., 1., 0.], dtype=np.float64)
+IDENTITY_TILE = np.array([1., 0., 0., 0., 1., 0.], dtype=np.float64)
 
 
 def _pair(name, v, lo=None, hi=None, lo_open=False):
@@ -99,6 +103,110 @@ class Augmentation(object):
                 (self.fliplr, self.scale, self.translate, self.rotate, self.brightness, self.offset, self.cval, self.seed))
 
 
+class Mosaic(object):
+    """What MaskYOLO.train(mosaic=...) takes: a sample is cut at a random point into four tiles, tile 0 (top left) showing the sample itself and
+    the others three images of the same batch, each zoomed about the frame corner that faces the cut.
+
+    p       probability that a sample is mosaicked
+    centre  (low, high) cut point as a fraction of each side, drawn independently for x and y, within [0, 1]
+    zoom    (low, high) zoom factor of a tile's image, drawn per tile, > 0
+    seed    plan() is a pure function of (seed, epoch, image ids, eligible)
+
+    Tile q = (x >= cx) + 2 * (y >= cy).  With integer pixel positions at pixel centres the frame is [-0.5, W-0.5] x [-0.5, H-0.5] and the cut lies at
+    (cx-0.5, cy-0.5); tile q pins the corner k_q of its image's frame to the cut -- k_0 = (W-0.5, H-0.5), k_1 = (-0.5, H-0.5), k_2 = (W-0.5, -0.5),
+    k_3 = (-0.5, -0.5) -- so its map from an output pixel to a position in its image's own frame is  u = k_q + (out - cut) / z_q."""
+
+    DRAWS = 10           # per sample: mosaicked?, centre x, centre y, three partners, four zooms
+
+    def __init__(self, p=1.0, centre=(0.25, 0.75), zoom=(0.5, 1.0), seed=0):
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p is a probability in [0, 1], got %r" % (p,))
+        self.p = p
+        self.centre = _pair("centre", centre, lo=0.0, hi=1.0)
+        self.zoom = _pair("zoom", zoom, lo=0.0, lo_open=True)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError("seed must be in [0, 2**32), got %r" % (seed,))
+        self.seed = seed
+
+    def plan(self, epoch, image_ids, H, W, eligible=None):
+        """-> (src int32 [B,4], tiles float64 [B,4,6], centre int32 [B,2]) for a batch whose position b holds dataset image image_ids[b].
+        src[b,q]: the batch position tile q shows (src[b,0] = b); tiles[b,q]: m00 m01 m02 m10 m11 m12, output pixel -> position in that image's own
+        frame; centre[b] = (cx, cy).  eligible: the batch positions that may be mosaicked and used as partners, in batch order (default: all; a
+        partner may repeat and may be b itself).  Position b always takes the same DRAWS draws in the same order from
+        RandomState([seed, epoch, image_ids[b]]), whatever the ranges: u0 < p mosaics it, u1 / u2 place the cut (round(fraction x side), clamped to
+        [1, side-1]), u3..u5 pick the partners eligible[floor(u * len(eligible))] of tiles 1..3, u6..u9 are the zooms of tiles 0..3.  A sample that
+        is not mosaicked (u0 >= p, or b not eligible) gets src = [b,b,b,b], identity tiles and the centre (W, H): every pixel in tile 0."""
+        B = len(image_ids)
+        eligible = list(range(B)) if eligible is None else [int(e) for e in eligible]
+        if any(not 0 <= e < B for e in eligible):
+            raise ValueError("eligible holds batch positions in [0, %d), got %r" % (B, eligible))
+        src = np.repeat(np.arange(B, dtype=np.int32)[:, None], 4, axis=1)
+        tiles = np.tile(IDENTITY_TILE, (B, 4, 1))
+        centre = np.tile(np.array([W, H], np.int32), (B, 1))
+        u = np.empty((B, self.DRAWS))
+        rs = np.random.RandomState(0)          # re-seeded per sample: the draws of a fresh RandomState([seed, epoch, id]) at a tenth of its cost
+        for b in range(B):
+            rs.seed([self.seed, int(epoch), int(image_ids[b])])
+            u[b] = rs.random_sample(self.DRAWS)
+        on = u[:, 0] < self.p
+        on &= np.isin(np.arange(B), eligible)
+        if not on.any():
+            return src, tiles, centre
+
+        def between(r, x):
+            return r[0] + (r[1] - r[0]) * x if r[1] > r[0] else np.full_like(x, r[0])
+        cx = np.clip(np.floor(between(self.centre, u[:, 1]) * W + 0.5).astype(np.int64), 1, W - 1)
+        cy = np.clip(np.floor(between(self.centre, u[:, 2]) * H + 0.5).astype(np.int64), 1, H - 1)
+        partner = np.minimum((u[:, 3:6] * len(eligible)).astype(np.int64), len(eligible) - 1)
+        a = 1.0 / between(self.zoom, u[:, 6:10])                                          # [B,4]; zoom 1 gives exactly 1
+        kx, ky = np.array([W - 0.5, -0.5, W - 0.5, -0.5]), np.array([H - 0.5, H - 0.5, -0.5, -0.5])
+        zero = np.zeros_like(a)
+        drawn = np.stack([a, zero, kx - a * (cx[:, None] - 0.5), zero, a, ky - a * (cy[:, None] - 0.5)], axis=-1)
+        src[on, 1:] = np.asarray(eligible, np.int32)[partner[on]]
+        tiles[on] = drawn[on]
+        centre[on] = np.stack([cx, cy], axis=-1)[on]
+        return src, tiles, centre
+
+    @staticmethod
+    def compose(tiles, src, rows):
+        """-> float64 [B,4,8], the rows myolo_mosaic_batch reads: tile (b,q)'s map followed by the Augmentation row r = rows[src[b,q]] of the image it
+        shows -- output pixel -> source position in image src[b,q]; gain and bias are r's.  With the tile a = tiles[b,q], each entry is these binary64
+        operations in this order:
+            m00 = r0*a0 + r1*a3        m01 = r0*a1 + r1*a4        m02 = (r0*a2 + r1*a5) + r2
+            m10 = r3*a0 + r4*a3        m11 = r3*a1 + r4*a4        m12 = (r3*a2 + r4*a5) + r5
+        A tile that is exactly the identity [1,0,0, 0,1,0] copies r instead, so that it leaves the row unchanged to the bit."""
+        tiles, src, rows = np.asarray(tiles, np.float64), np.asarray(src), np.asarray(rows, np.float64)
+        r = rows[src]                                              # [B,4,8]
+        a = tiles
+        out = r.copy()
+        out[..., 0] = r[..., 0] * a[..., 0] + r[..., 1] * a[..., 3]
+        out[..., 1] = r[..., 0] * a[..., 1] + r[..., 1] * a[..., 4]
+        out[..., 2] = (r[..., 0] * a[..., 2] + r[..., 1] * a[..., 5]) + r[..., 2]
+        out[..., 3] = r[..., 3] * a[..., 0] + r[..., 4] * a[..., 3]
+        out[..., 4] = r[..., 3] * a[..., 1] + r[..., 4] * a[..., 4]
+        out[..., 5] = (r[..., 3] * a[..., 2] + r[..., 4] * a[..., 5]) + r[..., 5]
+        same = (a == IDENTITY_TILE).all(axis=-1)
+        out[same] = r[same]
+        return out
+
+    def __repr__(self):
+        return "Mosaic(p=%r, centre=%r, zoom=%r, seed=%r)" % (self.p, self.centre, self.zoom, self.seed)
+
+
+def check_mosaic_tables(quad_src, centre, B, H, W):
+    """myolo_mosaic_batch does not read its tables on the host, so they are checked here, on the host arrays, before they are uploaded: sources in
+    [0, B), centres in [0, W] x [0, H]."""
+    quad_src, centre = np.asarray(quad_src), np.asarray(centre)
+    if quad_src.shape != (B, 4) or centre.shape != (B, 2):
+        raise ValueError("mosaic tables: expected quad_src [%d,4] and centre [%d,2], got %s and %s" % (B, B, quad_src.shape, centre.shape))
+    if ((quad_src < 0) | (quad_src >= B)).any():
+        raise ValueError("mosaic tables: quad_src holds batch positions in [0, %d)" % B)
+    if ((centre < 0) | (centre > np.array([W, H]))).any():
+        raise ValueError("mosaic tables: a centre lies in [0, %d] x [0, %d]" % (W, H))
+
+
 class DeviceAugmenter(object):
     """Runs myolo_augment_batch: raw bytes, un-augmented instance masks and class ids, one parameter row per image -> the device batch dict
     Net.forward_backward consumes.  T = cfg.TRUE_BOX_BUFFER (= cfg.MAX_GT_INSTANCES) slots per image; a class id of 0 marks an empty slot."""
@@ -124,16 +232,20 @@ class DeviceAugmenter(object):
             raise ValueError("DeviceAugmenter: expected shape %s, got %s" % (tuple(shape), tuple(a.shape)))
         return a.to(self.dev).contiguous()
 
-    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None):
+    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None, mosaic=None):
         """raw_images [B,H,W,3] uint8, gt_masks [B,H,W,T] uint8 / bool 0-1, gt_ids [B,T] int32 (0 = empty slot), params [B,8] float64 --
         numpy arrays (uploaded here) or device tensors.  -> dict(images, true_boxes, y_true, gt_ids, gt_boxes, gt_masks), the first three
         with yolo=True.  stream / consumer: as ShapesProducer.batch -- produce on `stream`, the dict carries the event `_ready` and its
-        tensors are registered with the stream that will read them."""
+        tensors are registered with the stream that will read them.
+        mosaic = (quad_src int32 [B,4], quad_rows float64 [B,4,8], centre int32 [B,2]) (Mosaic.plan / Mosaic.compose): myolo_mosaic_batch instead,
+        which reads quad_rows in place of params; the dict gains "mosaic_dropped" int32 [B], the survivors beyond T that were discarded.  Tables
+        given as numpy arrays are checked here (check_mosaic_tables); device tensors must have been checked before their upload, as
+        MaskYOLO.train() does."""
         import torch
         from . import _ext as X
         if stream is not None:
             with torch.cuda.stream(stream):
-                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo)
+                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo, mosaic=mosaic)
                 ev = torch.cuda.Event()
                 ev.record(stream)
             if consumer is not None:
@@ -152,9 +264,14 @@ class DeviceAugmenter(object):
             gt_masks = gt_masks.view(np.uint8)
         if isinstance(raw_images, np.ndarray) and raw_images.dtype != np.uint8:
             raise ValueError("DeviceAugmenter needs uint8 images, got %s" % raw_images.dtype)
+        if mosaic is not None and not (isinstance(mosaic[0], torch.Tensor) and isinstance(mosaic[2], torch.Tensor)):
+            check_mosaic_tables(mosaic[0], mosaic[2], B, H, W)
         src = (self._dev(raw_images, torch.uint8, (B, H, W, 3)), self._dev(gt_masks, torch.uint8, (B, H, W, T)),
                self._dev(gt_ids, torch.int32, (B, T)), self._dev(params, torch.float64, (B, 8)))
-        need = X.augment_ws_bytes(B, T)
+        if mosaic is not None:
+            src += (self._dev(mosaic[0], torch.int32, (B, 4)), self._dev(mosaic[1], torch.float64, (B, 4, 8)),
+                    self._dev(mosaic[2], torch.int32, (B, 2)))
+        need = X.augment_ws_bytes(B, T) if mosaic is None else X.mosaic_ws_bytes(B, T)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.dev)
         d = dict(images=torch.empty(B, H, W, 3, device=self.dev),
@@ -163,11 +280,18 @@ class DeviceAugmenter(object):
                  gt_ids=torch.empty(B, T, dtype=torch.int32, device=self.dev),
                  gt_boxes=torch.empty(B, T, 4, dtype=torch.int32, device=self.dev),
                  gt_masks=torch.empty(B, H, W, T, dtype=torch.uint8, device=self.dev))
-        X.call("myolo_augment_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[3]), self.cval, X.ptr(self.anchors),
-               X.ptr(d["images"]), X.ptr(d["gt_masks"]), X.ptr(d["gt_boxes"]), X.ptr(d["gt_ids"]), X.ptr(d["y_true"]), X.ptr(d["true_boxes"]),
-               B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
+        outs = (X.ptr(d["images"]), X.ptr(d["gt_masks"]), X.ptr(d["gt_boxes"]), X.ptr(d["gt_ids"]), X.ptr(d["y_true"]), X.ptr(d["true_boxes"]))
+        if mosaic is None:
+            X.call("myolo_augment_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[3]), self.cval, X.ptr(self.anchors), *outs,
+                   B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
+        else:
+            dropped = torch.empty(B, dtype=torch.int32, device=self.dev)
+            X.call("myolo_mosaic_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[4]), X.ptr(src[5]), X.ptr(src[6]), self.cval,
+                   X.ptr(self.anchors), *outs, X.ptr(dropped), B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
         if yolo:
             # the step reads three arrays; the other three stay on the dict's side until the kernels that wrote them have run
             d = dict(images=d["images"], true_boxes=d["true_boxes"], y_true=d["y_true"], _gt=(d["gt_ids"], d["gt_boxes"], d["gt_masks"]))
+        if mosaic is not None:
+            d["mosaic_dropped"] = dropped
         d["_src"] = src            # the kernels read them asynchronously
         return d

@@ -385,7 +385,7 @@ class MaskYOLO(object):
 
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers,
               augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0,
-              device_polygons=True):
+              device_polygons=True, mosaic=None):
         """model.py:943-1060.  Returns the list of per-epoch mean training losses; ``self.history`` holds
         {"loss": [...], "val_loss": [...]} like the Keras History the reference's fit_generator produces.
         shuffle_seed: the generators' one-off shuffle (myolo_utils.py:711-712) draws from RandomState(shuffle_seed) -- the
@@ -396,7 +396,11 @@ class MaskYOLO(object):
         fills no pixel is dropped on the device, AFTER the sub-sampling to TRUE_BOX_BUFFER instances (the host route drops it before).
         A train_dataset that has load_segments (myolo.coco.COCODataset) goes the same way under the same flag -- "annotations decoded on the
         device": its polygon parts and run-length codes are decoded by myolo_segment_masks.
-        False, or a dataset with neither: load_mask and the host route.  Validation batches always use load_mask."""
+        False, or a dataset with neither: load_mask and the host route.  Validation batches always use load_mask.
+        mosaic: a myolo.augment.Mosaic -- every training sample it picks is cut into four tiles that show the sample and three others of the same
+        batch, on the device, on every route, with or without `augmentation` (without: identity rows; on the host route the
+        device augmenter then runs all the same).  Samples whose source is in no_augmentation_sources are neither mosaicked nor used as partners;
+        validation batches never are."""
         layer_regex = {"all": ".*"}
         if layers in layer_regex:
             layers = layer_regex[layers]
@@ -406,6 +410,11 @@ class MaskYOLO(object):
             if not isinstance(augmentation, Augmentation):
                 raise TypeError("augmentation must be a myolo.augment.Augmentation (the warp runs on the device; imgaug objects are not taken), "
                                 "got %r" % type(augmentation).__name__)
+        if mosaic is not None:
+            from .augment import Mosaic
+            if not isinstance(mosaic, Mosaic):
+                raise TypeError("mosaic must be a myolo.augment.Mosaic, got %r" % type(mosaic).__name__)
+        device_augmenter = augmentation is not None or mosaic is not None
 
         def collect(ds, tag=False):
             ids = list(ds.image_ids)
@@ -424,7 +433,7 @@ class MaskYOLO(object):
         elif segment_route:
             train_info = self._collect_segments(train_dataset, max_samples)
         else:
-            train_info = collect(train_dataset, tag=augmentation is not None)
+            train_info = collect(train_dataset, tag=device_augmenter)
         val_info = collect(val_dataset) if val_dataset is not None else []
         mode = self.mode if self.mode in ('yolo', 'training') else 'training'
         rank, world = self._data_parallel()
@@ -457,11 +466,11 @@ class MaskYOLO(object):
 
         make_item = lambda it: make(it[1])             # noqa: E731
         if polygon_route:
-            make_item = self._polygon_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
+            make_item = self._polygon_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
         elif segment_route:
-            make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
-        elif augmentation is not None:
-            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode)
+            make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
+        elif device_augmenter:
+            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
 
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
         # are encoded and uploaded while epoch e finishes
@@ -523,21 +532,50 @@ class MaskYOLO(object):
             rows[k] = IDENTITY_ROW if plain else augmentation.params(epoch, i, H, W)
         return rows
 
-    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+    def _row_of(self, augmentation, no_augmentation_sources, dataset, epoch):
+        """-> row_of(sample) for the generators' fill functions: the sample's parameter row in this epoch, the identity with augmentation=None"""
+        from .augment import IDENTITY_ROW
+        if augmentation is None:
+            return lambda inst: IDENTITY_ROW
+        return lambda inst: self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
+
+    def mosaic_tables(self, mosaic, no_augmentation_sources, dataset, epoch, image_ids):
+        """-> (src [n,4], tiles [n,4,6], centre [n,2]): the plan train() draws for a batch that holds these dataset image ids, in this order, in this
+        epoch (Mosaic.plan).  A sample whose source is in no_augmentation_sources is neither mosaicked nor a partner."""
+        skip = set(no_augmentation_sources or [])
+        eligible = [k for k, i in enumerate(image_ids) if not (skip and dataset.image_info[i]['source'] in skip)]
+        return mosaic.plan(epoch, image_ids, self.config.IMAGE_SHAPE[0], self.config.IMAGE_SHAPE[1], eligible)
+
+    def _with_mosaic(self, mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill):
+        """fill(arrays) -> a fill for the same batch with the three mosaic tables staged behind the parameter rows (Net._mosaic_spec): the plan of the
+        batch's image ids, composed with the rows `fill` wrote, checked before the upload is queued.  mosaic=None: `fill` itself."""
+        if mosaic is None:
+            return fill
+        from .augment import check_mosaic_tables
+        lo, hi = gen.batch_bounds(i)
+        src, tiles, centre = self.mosaic_tables(mosaic, no_augmentation_sources, dataset, epoch, [inst[4] for inst in gen.all_info[lo:hi]])
+        check_mosaic_tables(src, centre, hi - lo, self.config.IMAGE_SHAPE[0], self.config.IMAGE_SHAPE[1])
+
+        def both(arrays):
+            fill(arrays[:-3])
+            arrays[-3][...], arrays[-2][...], arrays[-1][...] = src, mosaic.compose(tiles, src, arrays[-4]), centre
+            return arrays
+        return both
+
+    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread: raw bytes, un-augmented masks, class ids and parameter rows go up through the
         engine's staging ring, and the device augmenter runs behind the copies on the copy stream, under the previous step."""
         from .augment import DeviceAugmenter
         if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
-            raise ValueError("train(augmentation=...) needs uint8 images")
-        aug = DeviceAugmenter(self.config, self.net.dev, cval=augmentation.cval)
+            raise ValueError("train(augmentation=...) and train(mosaic=...) need uint8 images")
+        aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
 
         def make(it):
             epoch, i = it
             lo, hi = gen.batch_bounds(i)
-
-            def row_of(inst):
-                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
-            return self.net.stage_augmented(lambda arrays: gen.fill_raw(i, arrays, row_of), hi - lo, aug, yolo=(mode == 'yolo'))
+            row_of = self._row_of(augmentation, no_augmentation_sources, dataset, epoch)
+            fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, lambda arrays: gen.fill_raw(i, arrays, row_of))
+            return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None)
         return make
 
     def _collect_polygons(self, dataset, max_samples=None):
@@ -569,10 +607,10 @@ class MaskYOLO(object):
             info.append([image, class_ids, polys, (rows.astype(np.int32), cols.astype(np.int32)), int(i)])
         return info
 
-    def _polygon_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+    def _polygon_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread on the polygon route: image bytes, outlines, class ids, index tables and
         parameter rows go up through the engine's staging ring; the rasteriser and the device augmenter run behind the copies on the copy stream."""
-        from .augment import DeviceAugmenter, IDENTITY_ROW
+        from .augment import DeviceAugmenter
         if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
             raise ValueError("train() on a dataset with load_polygons needs uint8 images (or device_polygons=False)")
         aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
@@ -580,13 +618,9 @@ class MaskYOLO(object):
         def make(it):
             epoch, i = it
             lo, hi = gen.batch_bounds(i)
-
-            def row_of(inst):
-                if augmentation is None:
-                    return IDENTITY_ROW
-                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
-            fill, n_verts = gen.polygon_batch(i, row_of)
-            db = self.net.stage_polygons(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts)
+            fill, n_verts = gen.polygon_batch(i, self._row_of(augmentation, no_augmentation_sources, dataset, epoch))
+            fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            db = self.net.stage_polygons(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, mosaic=mosaic is not None)
             self.host_times["polygon_batches"] += 1
             return db
         return make
@@ -631,9 +665,9 @@ class MaskYOLO(object):
             info.append([image, class_ids, list(segs), (rows.astype(np.int32), cols.astype(np.int32)), int(i), int(h)])
         return info
 
-    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode):
+    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
         """_polygon_batches on the segment route: Net.stage_segments decodes the segments behind the copies, then the device augmenter runs."""
-        from .augment import DeviceAugmenter, IDENTITY_ROW
+        from .augment import DeviceAugmenter
         if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
             raise ValueError("train() on a dataset with load_segments needs uint8 images (or device_polygons=False)")
         aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
@@ -641,13 +675,10 @@ class MaskYOLO(object):
         def make(it):
             epoch, i = it
             lo, hi = gen.batch_bounds(i)
-
-            def row_of(inst):
-                if augmentation is None:
-                    return IDENTITY_ROW
-                return self.augmentation_rows(augmentation, no_augmentation_sources, dataset, epoch, [inst[4]])[0]
-            fill, n_verts, n_parts, n_bounds = gen.segment_batch(i, row_of)
-            db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds)
+            fill, n_verts, n_parts, n_bounds = gen.segment_batch(i, self._row_of(augmentation, no_augmentation_sources, dataset, epoch))
+            fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds,
+                                         mosaic=mosaic is not None)
             self.host_times["segment_batches"] += 1
             return db
         return make

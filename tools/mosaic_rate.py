@@ -1,0 +1,121 @@
+#!/usr/bin/env python
+"""What mosaic costs on one MI355X (profiles/mosaic_notes.md records a run), one JSON line:
+  kernel   device microseconds per call of myolo_mosaic_batch and of myolo_augment_batch on the same resident batch (224 x 224, batch 32, Shapes,
+           drawn rows): HIP events around LAUNCHES back-to-back calls, the two entries alternating REPS times in this one process; the median
+           and the extremes of each, and mosaic with all-self tables (the augment arithmetic through the mosaic kernels);
+  train    MaskYOLO.train() images/s on a ShapesDataset of N images at 224 x 224 / batch 32, timed between the on_epoch_end callbacks of epochs
+           2..E as bench.py's train_api does, `augmentation` alone and `augmentation` + `mosaic` alternating RUNS times in this one process;
+           and the launch thread's host milliseconds per step: waiting for the prefetched batch, and launching the step.
+  python tools/mosaic_rate.py [KERNEL=1] [TRAIN=1] [N=512] [EPOCHS=4] [RUNS=3] [LAUNCHES=100] [REPS=7]
+"""
+import json
+import os
+import sys
+import time
+
+over = dict(a.split("=", 1) for a in sys.argv[1:])
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "mask-yolo_amd")]
+import numpy as np                                             # noqa: E402
+import torch                                                   # noqa: E402
+from myolo import _ext as X                                    # noqa: E402
+from myolo.augment import Augmentation, DeviceAugmenter, Mosaic  # noqa: E402
+from myolo.config import make_config, ShapesConfig             # noqa: E402
+from myolo.model import MaskYOLO                               # noqa: E402
+from myolo.shapes import ShapesDataset, make_shapes_samples    # noqa: E402
+
+KERNEL, TRAIN = int(over.get("KERNEL", 1)), int(over.get("TRAIN", 1))
+N, EPOCHS, RUNS = int(over.get("N", 512)), int(over.get("EPOCHS", 4)), int(over.get("RUNS", 3))
+LAUNCHES, REPS = int(over.get("LAUNCHES", 100)), int(over.get("REPS", 7))
+assert torch.cuda.is_available(), "mosaic_rate needs a GPU: a rate measured anywhere else says nothing"
+FULL = dict(fliplr=.5, scale=(.7, 1.3), translate=(-.3, .3), rotate=(-30, 30), brightness=(.8, 1.2), offset=(-.1, .1))
+cfg = make_config(ShapesConfig, IMAGE_SHAPE=[224, 224, 3], BATCH_SIZE=32)
+B, H, W, T = cfg.BATCH_SIZE, 224, 224, cfg.TRUE_BOX_BUFFER
+res = {}
+
+
+def spread(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "all": [float(x) for x in v]}
+
+
+if KERNEL:
+    samples = make_shapes_samples(B, cfg)
+    images = np.stack([s[0] for s in samples])
+    masks, ids = np.zeros((B, H, W, T), np.uint8), np.zeros((B, T), np.int32)
+    for b, s in enumerate(samples):
+        ids[b, :len(s[1])] = s[1]
+        masks[b, :, :, :len(s[1])] = s[3]
+    dev = torch.device("cuda:0")
+    aug = DeviceAugmenter(cfg, dev)
+    rows = np.stack([Augmentation(**FULL).params(0, i, H, W) for i in range(B)])
+    plan = Mosaic().plan(0, list(range(B)), H, W)
+    own = Mosaic(p=0.0).plan(0, list(range(B)), H, W)
+    src = [torch.from_numpy(a).to(dev) for a in (images, masks, ids, rows)]
+    out = aug.apply(*src, mosaic=(plan[0], Mosaic.compose(plan[1], plan[0], rows), plan[2]))      # the outputs every timed call writes again
+    dropped = out["mosaic_dropped"]
+    res["instances_per_batch"] = {"mosaic": int((out["gt_ids"] != 0).sum()), "augment": int((aug.apply(*src)["gt_ids"] != 0).sum()),
+                                  "mosaic_dropped": int(dropped.sum())}
+    outs = [X.ptr(out[k]) for k in ("images", "gt_masks", "gt_boxes", "gt_ids", "y_true", "true_boxes")]
+    G, A, C = cfg.GRID_W, cfg.N_BOX, cfg.NUM_CLASSES
+    ws = torch.empty(X.mosaic_ws_bytes(B, T), dtype=torch.uint8, device=dev)
+
+    def augment():
+        X.call("myolo_augment_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[3]), 0.0, X.ptr(aug.anchors), *outs,
+               B, H, W, T, G, A, C, ws.data_ptr(), ws.numel(), X.stream())
+
+    def mosaic_with(p):
+        t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (p[0], Mosaic.compose(p[1], p[0], rows), p[2])]
+
+        def call():
+            X.call("myolo_mosaic_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(t[0]), X.ptr(t[1]), X.ptr(t[2]), 0.0, X.ptr(aug.anchors),
+                   *outs, X.ptr(dropped), B, H, W, T, G, A, C, ws.data_ptr(), ws.numel(), X.stream())
+        return call
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(LAUNCHES):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return 1e3 * e0.elapsed_time(e1) / LAUNCHES
+    calls = {"augment_batch": augment, "mosaic_batch": mosaic_with(plan), "mosaic_batch_all_self": mosaic_with(own)}
+    us = {k: [] for k in calls}
+    for fn in calls.values():
+        timed(fn)                                               # warm-up: code objects, caches
+    for _ in range(REPS):
+        for k, fn in calls.items():
+            us[k].append(timed(fn))
+    res["kernel_us_per_call"] = {k: spread(v) for k, v in us.items()}
+    print("kernel: %r" % {k: round(v["median"], 1) for k, v in res["kernel_us_per_call"].items()}, file=sys.stderr, flush=True)
+
+if TRAIN:
+    ds = ShapesDataset(1234)
+    ds.load_shapes(N, H, W)
+    ds.prepare()
+    rates = {"augmentation": [], "augmentation+mosaic": []}
+    waits, launches = {k: [] for k in rates}, {k: [] for k in rates}
+    for r in range(RUNS):
+        for name in rates:
+            model = MaskYOLO(mode="training", config=cfg)
+            stamps = []
+
+            def cb(ep, logs):
+                torch.cuda.synchronize()
+                stamps.append(time.perf_counter())
+            kw = {"augmentation": Augmentation(seed=r, **FULL)}
+            if name != "augmentation":
+                kw["mosaic"] = Mosaic(seed=r)
+            model.train(ds, None, 1e-4, epochs=EPOCHS, layers="all", verbose=0, custom_callbacks=[cb], **kw)
+            steps = (N + B - 1) // B
+            rates[name].append(B * steps * (len(stamps) - 1) / (stamps[-1] - stamps[0]))
+            ht = model.host_times
+            waits[name].append(1e3 * ht["wait_for_batch_s"] / max(1, ht["steps"]))
+            launches[name].append(1e3 * ht["launch_step_s"] / max(1, ht["steps"]))
+            print("train run %d, %s: %.1f img/s" % (r, name, rates[name][-1]), file=sys.stderr, flush=True)
+            del model
+    res["train_img_per_s"] = {k: spread(v) for k, v in rates.items()}
+    res["wait_for_batch_ms_per_step"] = {k: spread(v) for k, v in waits.items()}
+    res["launch_step_ms_per_step"] = {k: spread(v) for k, v in launches.items()}
+print(json.dumps(res))
