@@ -3,10 +3,12 @@
 MaskYOLO.detect_many as they are, whatever their sizes: they are resized to the network frame on the device and the boxes and masks come back
 in each photograph's own frame.  With --coco-json the masks are asked for as COCO run-length codes (encoded on the device,
 DESIGN section 15: no dense mask is written or downloaded) and every detection goes into one COCO results file.  With --render-dir every
-photograph's overlay -- masks, outlines and boxes drawn over it on the device -- is written there as <name>.png.
+photograph's overlay -- masks, outlines and boxes drawn over it on the device -- is written there as <name>.png.  With
+--via-json the masks are asked for as polygons (traced on the device) and written as a VIA 2.x annotation file: load it in the
+VGG Image Annotator beside the photographs to correct the predictions, or read it back with myolo.via.load_via.
 
   python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame] [--coco-json PATH]
-                                    [--render-dir DIR]
+                                    [--render-dir DIR] [--via-json PATH] [--polygon-tolerance T]
 """
 import argparse
 import glob
@@ -19,7 +21,7 @@ sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 import numpy as np                                   # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
-from myolo import render, rle                        # noqa: E402
+from myolo import render, rle, via                   # noqa: E402
 
 
 def load_rgb(path):
@@ -38,9 +40,17 @@ def main():
     ap.add_argument("--network-frame", action="store_true", help="report boxes and masks in the network frame (cheap for large photographs)")
     ap.add_argument("--coco-json", metavar="PATH", help="write the detections as a COCO results file (image_id = the file's name without extension)")
     ap.add_argument("--render-dir", metavar="DIR", help="write every photograph's overlay (masks, outlines, boxes) as DIR/<name>.png")
+    ap.add_argument("--via-json", metavar="PATH", help="write the detections as a VIA 2.x annotation file (one polygon region per outer outline)")
+    ap.add_argument("--polygon-tolerance", metavar="T", type=float, default=0.0,
+                    help="with --via-json: simplify every outline (Douglas-Peucker), dropping vertices within T pixels of it; 0 keeps every corner")
     a = ap.parse_args()
     if a.render_dir and a.network_frame:
         ap.error("--render-dir draws on the photograph given: it does not go with --network-frame")
+    if a.via_json and a.network_frame:
+        ap.error("--via-json outlines the photograph given: it does not go with --network-frame")
+    if a.polygon_tolerance < 0:
+        ap.error("--polygon-tolerance must be >= 0")
+    mask_format = "polygon" if a.via_json else ("rle" if a.coco_json or a.render_dir else "dense")
 
     paths = sorted(p for ext in ("jpg", "jpeg", "png", "JPG", "JPEG", "PNG") for p in glob.glob(os.path.join(a.images, "*." + ext)))
     if not paths:
@@ -48,14 +58,18 @@ def main():
     config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
     model = MaskYOLO(mode="inference", config=config)
     model.load_weights(a.weights)
-    total, coco = 0, []
+    total, coco, annotations = 0, [], {}
     for lo in range(0, len(paths), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
         chunk = paths[lo:lo + 8 * a.batch]
-        results = model.detect_many([load_rgb(p) for p in chunk], cs_threshold=a.threshold,
-                                    mask_frame="network" if a.network_frame else "image", mask_format="rle" if a.coco_json or a.render_dir else "dense", render=bool(a.render_dir))
+        photos = [load_rgb(p) for p in chunk]
+        results = model.detect_many(photos, cs_threshold=a.threshold, mask_frame="network" if a.network_frame else "image",
+                                    mask_format=mask_format, render=bool(a.render_dir))
+        if a.via_json:
+            annotations.update(via.via_annotations(results, [os.path.basename(p) for p in chunk], class_names=["BG", "rice"],
+                                                   tolerance=a.polygon_tolerance))
         if a.coco_json:
             coco += rle.coco_results(results, [os.path.splitext(os.path.basename(p))[0] for p in chunk])
-        for p, r in zip(chunk, results):
+        for p, r, photo in zip(chunk, results, photos):
             n = len(r["class_ids"])
             total += n
             if a.render_dir:
@@ -63,6 +77,8 @@ def main():
                 render.write_png(os.path.join(a.render_dir, os.path.splitext(os.path.basename(p))[0] + ".png"), r["rendered"])
             if "full_masks" in r:
                 fh, fw = r["full_masks"].shape[:2]
+            elif "polygons" in r:
+                fh, fw = photo.shape[:2]
             else:
                 fh, fw = r["rle_masks"][0]["size"] if n else (0, 0)
             print("%s: %d (mask frame %d x %d%s)" % (os.path.basename(p), n, fh, fw, "".join(", %.2f" % s for s in r["confidence_scores"])))
@@ -71,6 +87,10 @@ def main():
         with open(a.coco_json, "w") as f:
             json.dump(coco, f)
         print("wrote %s" % a.coco_json)
+    if a.via_json:
+        with open(a.via_json, "w") as f:
+            json.dump(annotations, f)
+        print("wrote %s" % a.via_json)
 
 
 if __name__ == "__main__":

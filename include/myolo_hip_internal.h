@@ -325,6 +325,27 @@ int myolo_rle_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,
                     int32_t* run_off /*[B*K+1]*/, uint32_t* bounds /*[cap]*/, int64_t cap,
                     int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection masks as polygons (myolo/contour.py, MaskYOLO.detect(mask_format="polygon"); contract and kernels: DESIGN.md section 21): the closed
+ * loops that bound the PASTED masks of selected detections -- the paste of myolo_unmold_masks, the same device function, pixel for pixel -- as
+ * vertex lists in lattice corner coordinates (pixel (y, x) is the square [x, x+1] x [y, y+1]), traced on the device without writing or downloading
+ * a full-size mask.  Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).
+ * masks, det, sel, sel_host, frames, frames_host as myolo_rle_masks takes them.  verts[vert_off[s] .. vert_off[s + 1]) are the vertices (X, Y) of
+ * slot s = b * K + k in contour.trace's order: loops ascending by their smallest edge key (Y, X, dir), each from the start corner of that edge in
+ * traversal order with the inside on the right; loop_id is the ordinal of each vertex's loop within its slot (from 0, never decreasing inside a
+ * slot).  An empty slot has no vertex.  vert_off [B*K+1] is always written in full; nothing is written at or beyond cap vertices, and when
+ * vert_off[B*K] > cap NO vertex is written: the caller grows verts, loop_id and the workspace and calls again.  Integer work only behind the
+ * paste: bit-identical from run to run.
+ * MYOLO_EINVAL (message "contour_masks: ...", nothing launched) for a null pointer, K > 16, h or w < 1, h * w >= 2^31, 2^30 corners x slots in the
+ * batch, sel >= R, cap outside [0, 2^31), and a workspace that is not 8-byte aligned or lies under myolo_contour_masks_ws_bytes(B, K, max_h,
+ * max_w, cap), max_h / max_w = the tallest / widest frame of the call.  The workspace holds 4 * B * K bytes per row of max_h and 44 bytes per
+ * vertex of cap; it does not grow with the frame's area. */
+size_t myolo_contour_masks_ws_bytes(int B, int K, int max_h, int max_w, int64_t cap);
+int myolo_contour_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,R,6]*/,
+                        const int32_t* sel /*[B,K] device, <0 = empty*/, const int32_t* sel_host,
+                        const int32_t* frames /*[B,2] device: h, w of image b's output frame*/, const int32_t* frames_host,
+                        int32_t* vert_off /*[B*K+1]*/, int32_t* verts /*[cap][2]: X, Y*/, int32_t* loop_id /*[cap]*/, int64_t cap,
+                        int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- overlay of the selected detections (myolo/render.py, MaskYOLO.detect(render=True); the picture and the kernel: DESIGN.md section 16): the
  * three layers of render.render_instances -- every PASTED mask blended into the image, every mask's one-pixel outline, the dashed ring of every
  * paste window, each over the slots in order -- drawn from the uploaded image bytes in one launch.  A mask pixel is the paste of

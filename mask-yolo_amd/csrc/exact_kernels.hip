@@ -662,6 +662,235 @@ __global__ __launch_bounds__(256) void rle_scan_slots_kernel(int32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------
+// Outlines of the pasted masks (myolo/contour.py is the statement of the contract): for every image b (its own frame) and
+// selected detection k, the closed loops of the mask's boundary as vertex lists in lattice corner coordinates.  A pixel is unmold_pixel, so the
+// outline is contour.trace of the dense paste by construction; no dense mask is written, and everything behind unmold_pixel is integer work.
+//
+// The four pixels round corner (X, Y) -- a b in row Y - 1 (columns X - 1, X), c d in row Y -- decide what starts there: the edge leaving east
+// exists when d & ~b, south c & ~d, west a & ~c, north b & ~a, and the edge ARRIVING with a direction when c & ~a, a & ~b, b & ~d, d & ~c.  A
+// leaving edge is a vertex edge unless the edge arriving with its own direction exists (a straight joint); a corner holds 0, 1 or -- between two
+// pixels that touch diagonally -- 2 of them.  Outside the paste window every pixel is 0, so only the window's corners x1 .. x2, y1 .. y2 matter.
+//  1. contour_rows_kernel<false>: one wave per lattice row, 64 corners at a time: ballots of the rows Y - 1 and Y, shifted by one for the
+//     columns X - 1 (the last bits of the previous group carried in), four bitwise expressions, popcounts.  rows [slot][Y] = vertex edges of the row.
+//  2. rle_scan_columns_kernel / rle_scan_slots_kernel: the rows of a slot and the slots, exclusive, vert_off [nslots + 1].
+//  3. contour_rows_kernel<true>: the same walk stores the keys (Y << 33 | X << 2 | dir) compacted: ascending within a slot.
+//  4. contour_link_kernel: one lane per vertex edge walks along its direction (two pixels per step decide right turn / straight / left turn)
+//     to the corner where the direction changes, and finds that vertex edge's index by binary search in the slot's keys: succ.  After
+//     CT_SOLO steps of its own a stretch is walked by the whole wave, 64 steps at a time (one lane walking a window's side of 416 steps was
+//     two thirds of the entry's time on filled windows).
+//  5. contour_rank_kernel: ONE workgroup per slot (a loop never leaves its slot, so __syncthreads() is the only barrier): pointer jumping over
+//     double buffers gives every vertex the smallest index of its loop; with every cycle cut in front of that head a second set of rounds gives
+//     the distance to the loop's end; the heads' lengths and flags are scanned in index (= key) order for the loop offsets and ordinals, and
+//     every vertex is stored at vert_off[slot] + offset of its loop + its rank.
+// Steps 3-5 do nothing when vert_off[nslots] > cap (the caller grows its buffers and calls again); nothing is written at or beyond cap.
+// ---------------------------------------------------------------------------------------
+#define CT_LINK_BLOCKS 8
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void contour_rows_kernel(const float* __restrict__ masks, const float* __restrict__ det,
+                                                           const int32_t* __restrict__ sel, const int32_t* __restrict__ allhigh,
+                                                           const int32_t* __restrict__ frames, int32_t* __restrict__ rows,
+                                                           const int32_t* __restrict__ vert_off, unsigned long long* __restrict__ keys,
+                                                           long long cap, int nslots, int R, int K, int mh, int mw, int C, int max_rows)
+{
+    const int lane = threadIdx.x & 63;
+    const int Y = blockIdx.x * 4 + (threadIdx.x >> 6);            // one lattice row per wave: everything below is uniform over the wave
+    const int slot = blockIdx.y, b = slot / K;
+    if (Y >= max_rows) return;
+    if (WRITE && (long long)vert_off[nslots] > cap) return;
+    const int s = sel[slot];
+    const int H = frames[2 * b], W = frames[2 * b + 1];
+    const long long row = (long long)b * R + max(s, 0);
+    const float* d = det + row * 6;
+    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+    if (s >= 0 && s < R) unmold_window(d, H, W, x1, y1, x2, y2);
+    if (!(s >= 0 && s < R && x1 < x2 && y1 < y2 && Y >= y1 && Y <= y2)) {
+        if (!WRITE && lane == 0) rows[(long long)slot * max_rows + Y] = 0;
+        return;
+    }
+    const float* m0 = masks + row * mh * mw * C;
+    const int ah = allhigh[slot];
+    const long long base = WRITE ? (long long)vert_off[slot] + rows[(long long)slot * max_rows + Y] : 0;
+    unsigned long long carry_t = 0, carry_b = 0;                   // the pixels of column x1 - 1: outside the window
+    int n = 0;
+    for (int x0 = x1; x0 <= x2; x0 += 64) {
+        const int X = x0 + lane;
+        int top = 0, bot = 0;
+        if (X <= x2) {                                             // (column x2 and the rows y1 - 1, y2 lie outside the window: unmold_pixel gives 0)
+            top = unmold_pixel(d, m0, ah, X, Y - 1, mh, mw, C, H, W);
+            bot = unmold_pixel(d, m0, ah, X, Y, mh, mw, C, H, W);
+        }
+        const unsigned long long pb = __ballot(top), pd = __ballot(bot);
+        const unsigned long long pa = (pb << 1) | carry_t, pc = (pd << 1) | carry_b;
+        carry_t = pb >> 63, carry_b = pd >> 63;
+        const unsigned long long vE = (pd & ~pb) & ~(pc & ~pa), vS = (pc & ~pd) & ~(pa & ~pb);
+        const unsigned long long vW = (pa & ~pc) & ~(pb & ~pd), vN = (pb & ~pa) & ~(pd & ~pc);
+        if (WRITE) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            long long at = base + n + __popcll(vE & below) + __popcll(vS & below) + __popcll(vW & below) + __popcll(vN & below);
+            const unsigned long long v[4] = {vE, vS, vW, vN};
+#pragma unroll
+            for (int dir = 0; dir < 4; ++dir)
+                if ((v[dir] >> lane) & 1ull) {
+                    if (at < cap) keys[at] = ((unsigned long long)Y << 33) | ((unsigned long long)X << 2) | (unsigned long long)dir;
+                    ++at;
+                }
+        }
+        n += __popcll(vE) + __popcll(vS) + __popcll(vW) + __popcll(vN);
+    }
+    if (!WRITE && lane == 0) rows[(long long)slot * max_rows + Y] = n;
+}
+
+#define CT_SOLO 8
+__device__ __forceinline__ int ct_dx(int dir) { return dir == 0 ? 1 : (dir == 2 ? -1 : 0); }
+__device__ __forceinline__ int ct_dy(int dir) { return dir == 1 ? 1 : (dir == 3 ? -1 : 0); }
+// corner (X, Y) reached with direction dir along an edge: the direction of the edge that goes on from it when that is a turn, -1 when it goes
+// straight on.  Two pixels ahead of the corner decide: the one on the right of travel (the inside so far) clear -- a right turn; else the one on
+// the left set -- a left turn.
+__device__ __forceinline__ int ct_turn(const float* __restrict__ d, const float* __restrict__ m0, int ah, int X, int Y, int dir, int mh, int mw,
+                                       int C, int H, int W)
+{
+    const int rx = (dir == 1 || dir == 2) ? -1 : 0, ry = (dir == 2 || dir == 3) ? -1 : 0;
+    const int lx = (dir == 2 || dir == 3) ? -1 : 0, ly = (dir == 0 || dir == 3) ? -1 : 0;
+    if (!unmold_pixel(d, m0, ah, X + rx, Y + ry, mh, mw, C, H, W)) return (dir + 1) & 3;
+    if (unmold_pixel(d, m0, ah, X + lx, Y + ly, mh, mw, C, H, W)) return (dir + 3) & 3;
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void contour_link_kernel(const float* __restrict__ masks, const float* __restrict__ det,
+                                                           const int32_t* __restrict__ sel, const int32_t* __restrict__ allhigh,
+                                                           const int32_t* __restrict__ frames, const int32_t* __restrict__ vert_off,
+                                                           const unsigned long long* __restrict__ keys, int32_t* __restrict__ succ,
+                                                           long long cap, int nslots, int R, int K, int mh, int mw, int C)
+{
+    const int slot = blockIdx.y, b = slot / K;
+    if ((long long)vert_off[nslots] > cap) return;
+    const int base = vert_off[slot], V = vert_off[slot + 1] - base;
+    const int s = sel[slot];
+    if (V <= 0 || s < 0 || s >= R) return;
+    const int H = frames[2 * b], W = frames[2 * b + 1];
+    const long long row = (long long)b * R + s;
+    const float* d = det + row * 6;
+    const float* m0 = masks + row * mh * mw * C;
+    const int ah = allhigh[slot];
+    const int lane = threadIdx.x & 63;
+    const int groups = ((H > W ? H : W) + 63) / 64 + 1;             // no straight stretch is longer than a side of the frame
+    // 64 vertex edges per wave at a time (i0 is uniform over the wave): a lane walks its own edge CT_SOLO steps -- a ragged outline's stretches
+    // end there -- and the wave then takes the unfinished ones in turn, 64 steps at a time, the first turn found by a ballot
+    for (int i0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; i0 < V; i0 += CT_LINK_BLOCKS * 256) {
+        const int i = i0 + lane;
+        const bool mine = i < V;
+        const unsigned long long key = mine ? keys[base + i] : 0ull;
+        const int dir = (int)(key & 3ull);
+        int X = (int)((key >> 2) & 0x7fffffffull), Y = (int)(key >> 33);
+        int nd = -1;
+        if (mine) {
+            const int dx = ct_dx(dir), dy = ct_dy(dir);
+            for (int step = 0; step < CT_SOLO && nd < 0; ++step) {
+                X += dx, Y += dy;
+                nd = ct_turn(d, m0, ah, X, Y, dir, mh, mw, C, H, W);
+            }
+        }
+        unsigned long long pending = __ballot(mine && nd < 0);
+        while (pending) {
+            const int src = __ffsll((long long)pending) - 1;
+            pending &= pending - 1ull;
+            const int sdir = __shfl(dir, src), sx = __shfl(X, src), sy = __shfl(Y, src);
+            const int dx = ct_dx(sdir), dy = ct_dy(sdir);
+            for (int g = 0; g < groups; ++g) {
+                const int k = g * 64 + lane + 1;                   // (a lane beyond the turn reads pixels that may lie outside the frame: they are 0)
+                const int t = ct_turn(d, m0, ah, sx + k * dx, sy + k * dy, sdir, mh, mw, C, H, W);
+                const unsigned long long turned = __ballot(t >= 0);
+                if (turned) {
+                    const int first = __ffsll((long long)turned) - 1;
+                    const int tn = __shfl(t, first);
+                    if (lane == src) X = sx + (g * 64 + first + 1) * dx, Y = sy + (g * 64 + first + 1) * dy, nd = tn;
+                    break;
+                }
+            }
+        }
+        if (!mine) continue;
+        int found = i;                                             // (a key that is not there cannot happen; the link then stays inside the slot)
+        if (nd >= 0) {
+            const unsigned long long want = ((unsigned long long)Y << 33) | ((unsigned long long)X << 2) | (unsigned long long)nd;
+            int lo = 0, hi = V - 1;
+            while (lo <= hi) {
+                const int mid = (lo + hi) >> 1;
+                const unsigned long long k = keys[base + mid];
+                if (k == want) { found = mid; break; }
+                if (k < want) lo = mid + 1; else hi = mid - 1;
+            }
+        }
+        succ[base + i] = found;
+    }
+}
+
+// buffers of cap words each, indexed vert_off[slot] + i; the values are indices inside the slot.  No __restrict__: they are exchanged between
+// the waves of the workgroup from round to round.
+__global__ __launch_bounds__(256) void contour_rank_kernel(const int32_t* vert_off, const unsigned long long* keys, const int32_t* succ,
+                                                           int32_t* m0, int32_t* m1, int32_t* n0, int32_t* n1, int32_t* d0, int32_t* d1,
+                                                           int32_t* s0, int32_t* s1, int32_t* verts, int32_t* loop_id, long long cap, int nslots)
+{
+    if ((long long)vert_off[nslots] > cap) return;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const int base = vert_off[slot], V = vert_off[slot + 1] - base;
+    if (V <= 0) return;
+    keys += base, succ += base, m0 += base, m1 += base, n0 += base, n1 += base, d0 += base, d1 += base, s0 += base, s1 += base;
+    int rounds = 0;
+    while ((1ll << rounds) < V) ++rounds;
+    // every vertex's loop head: the smallest index on its cycle
+    for (int i = tid; i < V; i += 256) m0[i] = i, n0[i] = succ[i];
+    __syncthreads();
+    for (int r = 0; r < rounds; ++r) {
+        for (int i = tid; i < V; i += 256) {
+            const int j = n0[i];
+            m1[i] = min(m0[i], m0[j]);
+            n1[i] = n0[j];
+        }
+        __syncthreads();
+        int32_t* t = m0; m0 = m1; m1 = t;
+        t = n0; n0 = n1; n1 = t;
+    }
+    // the distance to the end of the loop, the cycle cut in front of its head (m0 is final and stays)
+    for (int i = tid; i < V; i += 256) {
+        const int j = succ[i];
+        const bool last = j == m0[i];
+        n0[i] = last ? -1 : j;
+        d0[i] = last ? 0 : 1;
+    }
+    __syncthreads();
+    for (int r = 0; r < rounds; ++r) {
+        for (int i = tid; i < V; i += 256) {
+            const int j = n0[i];
+            d1[i] = j < 0 ? d0[i] : d0[i] + d0[j];
+            n1[i] = j < 0 ? -1 : n0[j];
+        }
+        __syncthreads();
+        int32_t* t = d0; d0 = d1; d1 = t;
+        t = n0; n0 = n1; n1 = t;
+    }
+    // loop offsets and ordinals: the heads in index order
+    for (int i = tid; i < V; i += 256) {
+        const bool head = m0[i] == i;
+        s0[i] = head ? d0[i] + 1 : 0;
+        s1[i] = head ? 1 : 0;
+    }
+    __syncthreads();
+    rle_scan_in_place(s0, V);
+    rle_scan_in_place(s1, V);
+    for (int i = tid; i < V; i += 256) {
+        const int h = m0[i];
+        const int at = s0[h] + (d0[h] - d0[i]);
+        if (at >= 0 && at < V && (long long)base + at < cap) {
+            const unsigned long long key = keys[i];
+            verts[2 * ((long long)base + at)] = (int)((key >> 2) & 0x7fffffffull);
+            verts[2 * ((long long)base + at) + 1] = (int)(key >> 33);
+            loop_id[(long long)base + at] = s1[h];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Overlay of the selected detections on the uploaded image bytes (myolo/render.py render_instances is the statement of the picture, DESIGN.md
 // section 16): for every image b of a packed batch (desc [B][3] = byte offset, h, w, the pack_images layout) the three layers of the host
 // renderer -- blend every pasted mask into the canvas, draw the one-pixel outline of every mask, blend the dashed ring of every paste window --
@@ -1069,6 +1298,71 @@ int myolo_rle_masks(const float* masks, const float* det, const int32_t* sel, co
     hipLaunchKernelGGL(rle_scan_slots_kernel, dim3(1), dim3(256), 0, s, run_off, B * K);
     hipLaunchKernelGGL(rle_columns_kernel<true>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, cols,
                        (const int32_t*)run_off, bounds, (long long)cap, R, K, mh, mw, C, max_w);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+// [all-high flags B*K | rows B*K*(max_h + 1)] int32, padded to 16 bytes; then per vertex of cap: the key (8 bytes) and nine int32 words (succ, the
+// double buffers of head / link / distance, the two scan rows).  Nothing grows with the frame's width, 4 * B * K bytes with a row of its height.
+#define CT_WORDS_PER_VERTEX 9
+static size_t contour_head_bytes(int B, int K, int max_h)
+{
+    const size_t words = (size_t)B * K * ((size_t)max_h + 2);
+    return (words * sizeof(int32_t) + 15) / 16 * 16;
+}
+
+size_t myolo_contour_masks_ws_bytes(int B, int K, int max_h, int max_w, int64_t cap)
+{
+    if (B <= 0 || K <= 0 || max_h <= 0 || max_w <= 0 || cap < 0) return 0;
+    return contour_head_bytes(B, K, max_h) + (size_t)cap * (sizeof(unsigned long long) + CT_WORDS_PER_VERTEX * sizeof(int32_t));
+}
+
+int myolo_contour_masks(const float* masks, const float* det, const int32_t* sel, const int32_t* sel_host, const int32_t* frames,
+                        const int32_t* frames_host, int32_t* vert_off, int32_t* verts, int32_t* loop_id, int64_t cap, int B, int R, int K, int mh,
+                        int mw, int C, void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(masks && det && sel && sel_host && frames && frames_host && vert_off && verts && loop_id && ws, "contour_masks: null pointer");
+    MYOLO_REQUIRE(B > 0 && R > 0 && mh > 0 && mw > 0 && C > 0 && cap >= 0 && cap < (1ll << 31), "contour_masks: bad sizes");
+    MYOLO_REQUIRE(K > 0 && K <= OV_MAXK, "contour_masks: need 1 <= K <= %d (got K=%d)", OV_MAXK, K);
+    MYOLO_REQUIRE((long long)B * K <= 65535, "contour_masks: B * K = %lld slots, more than the 65535 of one launch", (long long)B * K);
+    int max_h = 0, max_w = 0;
+    long long corners = 0;                                         // two vertices a corner at the most: vert_off is 32-bit
+    for (int b = 0; b < B; ++b) {
+        const int h = frames_host[2 * b], w = frames_host[2 * b + 1];
+        MYOLO_REQUIRE(h >= 1 && w >= 1, "contour_masks: frame %d is %d x %d (h, w >= 1 needed)", b, h, w);
+        MYOLO_REQUIRE((long long)h * w < (1ll << 31), "contour_masks: frame %d (%d x %d) has 2^31 pixels or more", b, h, w);
+        corners += ((long long)h + 1) * ((long long)w + 1) * K;
+        max_h = h > max_h ? h : max_h;
+        max_w = w > max_w ? w : max_w;
+    }
+    MYOLO_REQUIRE(2 * corners < (1ll << 31), "contour_masks: the frames of the batch hold %lld corners x slots, 2^30 or more", corners);
+    for (long long i = 0; i < (long long)B * K; ++i)
+        MYOLO_REQUIRE(sel_host[i] < R, "contour_masks: sel[%lld] = %d is not a row of the %d detections", i, sel_host[i], R);
+    const size_t need = myolo_contour_masks_ws_bytes(B, K, max_h, max_w, cap);
+    MYOLO_REQUIRE(ws_bytes >= need, "contour_masks: workspace too small (%zu needed for frames up to %d high and %lld vertices, %zu given)", need,
+                  max_h, (long long)cap, ws_bytes);
+    MYOLO_REQUIRE(((uintptr_t)ws & 7) == 0, "contour_masks: the workspace must be 8-byte aligned");
+    const int nslots = B * K, max_rows = max_h + 1;
+    int32_t* allhigh = (int32_t*)ws;
+    int32_t* rows = allhigh + nslots;
+    unsigned long long* keys = (unsigned long long*)((char*)ws + contour_head_bytes(B, K, max_h));
+    int32_t* w32 = (int32_t*)(keys + cap);
+    int32_t* part[CT_WORDS_PER_VERTEX];
+    for (int i = 0; i < CT_WORDS_PER_VERTEX; ++i) part[i] = w32 + (size_t)i * cap;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((max_rows + 3) / 4, nslots);
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(nslots), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
+    hipLaunchKernelGGL(contour_rows_kernel<false>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, rows,
+                       (const int32_t*)vert_off, keys, (long long)cap, nslots, R, K, mh, mw, C, max_rows);
+    hipLaunchKernelGGL(rle_scan_columns_kernel, dim3(nslots), dim3(256), 0, s, rows, vert_off, max_rows);
+    hipLaunchKernelGGL(rle_scan_slots_kernel, dim3(1), dim3(256), 0, s, vert_off, nslots);
+    hipLaunchKernelGGL(contour_rows_kernel<true>, grid, dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames, rows,
+                       (const int32_t*)vert_off, keys, (long long)cap, nslots, R, K, mh, mw, C, max_rows);
+    hipLaunchKernelGGL(contour_link_kernel, dim3(CT_LINK_BLOCKS, nslots), dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh, frames,
+                       (const int32_t*)vert_off, (const unsigned long long*)keys, part[0], (long long)cap, nslots, R, K, mh, mw, C);
+    hipLaunchKernelGGL(contour_rank_kernel, dim3(nslots), dim3(256), 0, s, (const int32_t*)vert_off, (const unsigned long long*)keys,
+                       (const int32_t*)part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7], part[8], verts, loop_id,
+                       (long long)cap, nslots);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -138,6 +138,7 @@ SIGS = {
     "myolo_segment_masks": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
+    "myolo_contour_masks": [P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
     "myolo_render_instances": [P, P, Z, P, P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, P, Z, P],
     "myolo_anchor_kmeans": [P, L, P, P, I, I, P, P, P, P, P, P, Z, P],
     "myolo_set_option": [ctypes.c_char_p, I],
@@ -227,6 +228,8 @@ def load():
     lib.myolo_resize_images_ws_bytes.restype = Z
     lib.myolo_rle_masks_ws_bytes.argtypes = [I, I, I]
     lib.myolo_rle_masks_ws_bytes.restype = Z
+    lib.myolo_contour_masks_ws_bytes.argtypes = [I, I, I, I, L]
+    lib.myolo_contour_masks_ws_bytes.restype = Z
     lib.myolo_anchor_kmeans_ws_bytes.argtypes = [L, I]
     lib.myolo_anchor_kmeans_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
@@ -241,7 +244,7 @@ def exported_symbols():
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
                               "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_mosaic_batch_ws_bytes", "myolo_resize_images_ws_bytes",
-                              "myolo_rle_masks_ws_bytes", "myolo_anchor_kmeans_ws_bytes"]
+                              "myolo_rle_masks_ws_bytes", "myolo_contour_masks_ws_bytes", "myolo_anchor_kmeans_ws_bytes"]
 
 
 def ptr(t):
@@ -460,6 +463,10 @@ def resize_ws_bytes(b):
 
 def rle_masks_ws_bytes(b, k, max_w):
     return int(load().myolo_rle_masks_ws_bytes(int(b), int(k), int(max_w)))
+
+
+def contour_masks_ws_bytes(b, k, max_h, max_w, cap):
+    return int(load().myolo_contour_masks_ws_bytes(int(b), int(k), int(max_h), int(max_w), int(cap)))
 
 
 def anchor_kmeans_ws_bytes(n, runs):

@@ -1,7 +1,8 @@
 """
 ``myolo.detect`` -- the one detection pipeline under MaskYOLO.detect / detect_many / evaluate / evaluate_shapes_stream:
 uint8 images are staged to the device (Stager), run through the forward, up to SLOTS rows per image are selected on the host from the one
-detection download of a batch (Selection), and the selection is handed to a mask consumer: dense_masks, rle_masks, overlap_counts, render.
+detection download of a batch (Selection), and the selection is handed to a mask consumer: dense_masks, rle_masks, polygon_masks, overlap_counts,
+render.
 """
 import numpy as np
 import torch
@@ -18,10 +19,10 @@ def check_args(cfg, images, mask_frame, mask_format, render):
     selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
     if mask_frame not in ("image", "network"):
         raise ValueError("mask_frame must be 'image' or 'network' (got %r)" % (mask_frame,))
-    if mask_format not in ("dense", "rle"):
-        raise ValueError("mask_format must be 'dense' or 'rle' (got %r)" % (mask_format,))
-    if mask_format == "rle" and selected_only:
-        raise ValueError("mask_format='rle' is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
+    if mask_format not in ("dense", "rle", "polygon"):
+        raise ValueError("mask_format must be 'dense', 'rle' or 'polygon' (got %r)" % (mask_format,))
+    if mask_format in ("rle", "polygon") and selected_only:
+        raise ValueError("mask_format=%r is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY" % (mask_format,))
     for im in images:
         assert im.dtype == 'uint8' and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] >= 1 and im.shape[1] >= 1, \
             "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
@@ -177,6 +178,17 @@ def rle_masks(net, det_d, mask_d, selection, frames):
              for s in range(k * K, k * K + len(selection.rows(k)))] for k, (h, w) in enumerate(fr[:selection.n].tolist())]
 
 
+def polygon_masks(net, det_d, mask_d, selection, frames):
+    """polygons of the live images of a batch, one Net.contour_masks call: per image the list, in class_ids order, of each instance's loops (int32
+    [n,2] (X, Y) corner coordinates of the frame frames[k] = (h, w, ...), contour.trace's order)"""
+    K = selection.sel.shape[1]
+    fr = np.ones(selection.sel.shape[:1] + (2,), np.int32)                 # (padding: no slot, a 1 x 1 frame)
+    for k, f in enumerate(frames):
+        fr[k] = (int(f[0]), int(f[1]))
+    loops = net.contour_masks(det_d, mask_d, selection.sel, fr)
+    return [loops[k * K:k * K + len(selection.rows(k))] for k in range(selection.n)]
+
+
 def overlap_counts(stager, det_d, mask_d, selection, gt_d):
     """(inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4]) on the host: one Net.overlap_counts call against gt_d [B,H,W,T]"""
     # (the table goes up from a pinned buffer without blocking; free again by the next batch: the downloads here end with a synchronisation)
@@ -203,6 +215,9 @@ def batch_results(stager, det_d, mask_d, selection, frames, mask_format="dense",
     if mask_format == "rle":
         for r, codes in zip(out, rle_masks(stager.net, det_d, mask_d, selection, frames)):
             r["rle_masks"] = codes
+    elif mask_format == "polygon":
+        for r, loops in zip(out, polygon_masks(stager.net, det_d, mask_d, selection, frames)):
+            r["polygons"] = loops
     else:
         for k, r in enumerate(out):
             r["full_masks"] = dense_masks(stager, det_d[k], None if mask_d is None else mask_d[k], selection.rows(k), frames[k], feature)

@@ -502,6 +502,9 @@ class Net(object):
         self._resize_stage_ev = None
         self._rle_bounds = None           # rle_masks: the device buffer of the boundaries (int32 words, grow-only) and its pinned host staging
         self._rle_pin = None
+        self._contour_verts = None        # contour_masks: [verts cap x 2 | loop_id cap] int32 on the device (grow-only), its workspace, the pinned staging
+        self._contour_ws = None
+        self._contour_pin = None
         self._render_args = None          # render_instances: the pinned buffer of its arguments and the pinned, grow-only one the overlays come down into
         self._render_pin = None
         self._cap_stream = None           # graph capture never happens with the default stream current (see _capture_predict)
@@ -2863,6 +2866,60 @@ class Net(object):
                 break
             self._rle_bounds = torch.empty(max(total, 2 * bounds.numel()), dtype=torch.int32, device=self.dev)
         return run_off, bounds[:total].cpu().numpy().view(np.uint32)
+
+    CONTOUR_VERTS_START = 1 << 16         # contour_masks: first size of the vertex buffer, in vertices (ten 416 x 416 masks hold a few thousand)
+
+    def contour_masks(self, det_d, mask_d, sel, frames):
+        """The pasted masks of selected detections as closed outlines, traced on the device (myolo_contour_masks, include/myolo_hip_internal.h;
+        the contract: myolo/contour.py): det_d, mask_d, sel [B,K] and frames [B,2] as rle_masks takes them.  -> a list of B*K lists, slot
+        s = b*K + k: that mask's loops as int32 [n,2] (X, Y) arrays in lattice corner coordinates, contour.trace's order; an empty slot has none.
+        One upload (sel and frames together) and three small downloads: the offsets, then verts[:total] and loop_id[:total].  The vertices land
+        in ONE device buffer per Net that only grows, the workspace beside them sized from it; when a batch holds more vertices than there is
+        room for, the entry has still written every offset, so the buffer is enlarged to the total and the call repeated."""
+        expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32"
+        sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("contour_masks", expected, det_d, mask_d, sel)
+        sel_h = sel_t.numpy()
+        frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)
+        if frames_h.dtype != np.int32 or tuple(frames_h.shape) != (B, 2):
+            raise ValueError("contour_masks: %s expected" % expected)
+        det_d, mask_d = det_d.contiguous(), mask_d.contiguous()
+        nsel, nslot = B * K, B * K + 1
+        # host side: [sel | frames | vert_off] in one pinned buffer (free again when this call returns: it ends with a synchronising download)
+        if self._contour_pin is None or self._contour_pin.numel() < nsel + 2 * B + nslot:
+            self._contour_pin = torch.empty(nsel + 2 * B + nslot, dtype=torch.int32).pin_memory()
+        pin = self._contour_pin
+        args_h, off_h = pin[:nsel + 2 * B], pin[nsel + 2 * B:nsel + 2 * B + nslot]
+        args_np = args_h.numpy()
+        args_np[:nsel], args_np[nsel:] = sel_h.reshape(-1), frames_h.reshape(-1)
+        args_d = args_h.to(self.dev, non_blocking=True)
+        max_h, max_w = max(int(frames_h[:, 0].max()), 1), max(int(frames_h[:, 1].max()), 1)
+        off_d = torch.empty(nslot, dtype=torch.int32, device=self.dev)
+        if self._contour_verts is None:
+            self._contour_verts = torch.empty(3 * self.CONTOUR_VERTS_START, dtype=torch.int32, device=self.dev)
+        while True:
+            buf = self._contour_verts                                   # [verts cap x 2 | loop_id cap]
+            cap = buf.numel() // 3
+            ws_bytes = X.contour_masks_ws_bytes(B, K, max_h, max_w, cap)
+            if self._contour_ws is None or self._contour_ws.numel() * 8 < ws_bytes:
+                self._contour_ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=self.dev)
+            X.call("myolo_contour_masks", X.ptr(mask_d), X.ptr(det_d), args_d.data_ptr(), args_np.ctypes.data, args_d.data_ptr() + nsel * 4,
+                   args_np.ctypes.data + nsel * 4, off_d.data_ptr(), buf.data_ptr(), buf.data_ptr() + 8 * cap, cap, B, R, K, mh, mw, C,
+                   self._contour_ws.data_ptr(), self._contour_ws.numel() * 8, X.stream())
+            off_h.copy_(off_d, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            vert_off = off_h.numpy().copy()
+            total = int(vert_off[-1])
+            if total <= cap:
+                break
+            self._contour_verts = torch.empty(3 * max(total, 2 * cap), dtype=torch.int32, device=self.dev)
+        verts = buf[:2 * total].cpu().numpy().reshape(total, 2)
+        loop_id = buf[2 * cap:2 * cap + total].cpu().numpy()
+        out = []
+        for s in range(nsel):
+            a, b = int(vert_off[s]), int(vert_off[s + 1])
+            cuts = np.flatnonzero(np.diff(loop_id[a:b])) + 1 if b > a else ()
+            out.append(np.split(verts[a:b], cuts) if b > a else [])
+        return out
 
     def predict_yolo(self, images):
         """'yolo' mode forward (model.py:906-920)."""

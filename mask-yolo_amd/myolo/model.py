@@ -751,7 +751,13 @@ class MaskYOLO(object):
         mask_format="rle": instead of full_masks the dict has rle_masks, a list of COCO run-length dicts {"size": [h, w], "counts": int64 array}
         (myolo/rle.py) in the order of class_ids, size = the frame mask_frame names; rle.decode of each is the full_masks plane bit for bit.  The
         masks are encoded on the device (Net.rle_masks) and no dense mask is written or downloaded.  Not supported together
-        with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).  Any other mask_format raises ValueError.
+        with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).
+        mask_format="polygon": instead of full_masks the dict has polygons, a list in the order of class_ids of each instance's closed loops: int32
+        [n,2] (X, Y) arrays in lattice corner coordinates of the frame mask_frame names (pixel (y, x) is the square [x, x+1] x [y, y+1]), outer
+        loops clockwise on screen, holes the other way, in the order of myolo/contour.py -- contour.trace of the full_masks plane integer for
+        integer.  The masks are traced on the device (Net.contour_masks, DESIGN.md section 21) and no dense mask is written or downloaded;
+        myolo.via.via_annotations and myolo.rle.coco_results write the results out.  Not supported together with
+        config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError).  Any other mask_format raises ValueError.
         render=True: the dict gains "rendered", uint8 [h,w,3]: the overlay the reference's detect() draws (visualize.display_instances without the
         captions) over the image given -- the masks blended in, their outlines, the dashed boxes, instance i of class_ids in colour i of
         render.instance_colors(len(class_ids)) -- drawn on the device from the uploaded bytes (Net.render_instances); with a
@@ -784,6 +790,7 @@ class MaskYOLO(object):
         mask_format="rle" (see detect; ValueError with config.DETECT_MASKS_FOR_SELECTED_ONLY): rle_masks in place of full_masks, and the
         post-processing runs once per BATCH -- the selection of all its images on the host from the one detection download, one [B, K] upload,
         one Net.rle_masks call whose two downloads are a few KB -- where the dense form pastes and downloads per image.
+        mask_format="polygon" (see detect): polygons in place of full_masks, once per batch in the same way (one Net.contour_masks call).
         render=True (see detect; nothing is written to disk here): every dict gains "rendered", drawn once per BATCH on the bytes the batch went
         up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere."""
         cfg = self.config

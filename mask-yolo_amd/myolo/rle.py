@@ -127,7 +127,10 @@ def coco_results(results, image_ids, category_ids=None):
     """detect() / detect_many() result dicts of either mask format -> the list of COCO result dicts
     {"image_id", "category_id", "segmentation": {"size": [h, w], "counts": <compressed string>}, "bbox": [x, y, w, h], "score"}, ready for json.dump.
     image_ids: one id per result dict.  category_ids (None: the class id itself): a mapping or sequence, class id -> COCO category id.  bbox is the
-    detection's box (bboxes, [x1, y1, x2, y2] pixels of the masks' frame) as COCO writes it."""
+    detection's box (bboxes, [x1, y1, x2, y2] pixels of the masks' frame) as COCO writes it.
+    Results of mask_format="polygon" (they carry "polygons") give COCO's polygon form instead: segmentation = the list of the instance's OUTER loops
+    (myolo/contour.py; holes are dropped), each flat [x1, y1, x2, y2, ...] in corner coordinates, which are COCO's; bbox = the loops' own extent and
+    "area" = the pixels they enclose."""
     results, image_ids = list(results), list(image_ids)
     if len(results) != len(image_ids):
         raise ValueError("coco_results: %d results but %d image ids" % (len(results), len(image_ids)))
@@ -135,6 +138,21 @@ def coco_results(results, image_ids, category_ids=None):
     for r, image_id in zip(results, image_ids):
         n = len(r["class_ids"])
         for i in range(n):
+            if "polygons" in r:
+                from .contour import outer_loops, signed_area
+                loops = outer_loops(r["polygons"][i])
+                cls = int(r["class_ids"][i])
+                pts = np.concatenate(loops) if loops else np.zeros((1, 2), np.int32)
+                x1, y1, x2, y2 = (float(t) for t in (pts[:, 0].min(), pts[:, 1].min(), pts[:, 0].max(), pts[:, 1].max()))
+                out.append({
+                    "image_id": image_id.item() if isinstance(image_id, np.generic) else image_id,
+                    "category_id": cls if category_ids is None else int(category_ids[cls]),
+                    "segmentation": [[int(v) for v in np.asarray(l).reshape(-1)] for l in loops],
+                    "bbox": [x1, y1, x2 - x1, y2 - y1],
+                    "area": float(sum(signed_area(l) for l in loops)),
+                    "score": float(r["confidence_scores"][i]),
+                })
+                continue
             m = r["rle_masks"][i] if "rle_masks" in r else encode(np.asarray(r["full_masks"])[:, :, i])
             cls = int(r["class_ids"][i])
             x1, y1, x2, y2 = (float(t) for t in r["bboxes"][i])

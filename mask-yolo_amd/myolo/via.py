@@ -70,6 +70,33 @@ class VIADataset(object):
         return self.image_info[image_id]["path"]
 
 
+def via_annotations(results, filenames, class_names=None, tolerance=0.0):
+    """detect() / detect_many(mask_format="polygon") result dicts -> the VIA 2.x annotation dict, ready for json.dump and for load_via: one entry
+    per image (filenames: one per result dict), one `polygon` region per OUTER loop of every instance -- VIA has no holes, so they are dropped; an
+    instance of several pieces gives several regions.  all_points_x / all_points_y = X - 0.5, Y - 0.5: the pixel-centre convention load_via's
+    fill reads, under which the outline of a hole-free piece fills to exactly its pixels.  region_attributes carries "class" (class_names[class
+    id], a sequence indexed by class id as VIADataset.class_names is; None: the id as a string), "score" and "instance" (the position in
+    class_ids).  tolerance > 0: every loop goes through contour.simplify first (in pixels)."""
+    from .contour import outer_loops, simplify
+    results, filenames = list(results), list(filenames)
+    if len(results) != len(filenames):
+        raise ValueError("via_annotations: %d results but %d filenames" % (len(results), len(filenames)))
+    out = {}
+    for r, name in zip(results, filenames):
+        if "polygons" not in r:
+            raise ValueError("via_annotations: results of mask_format='polygon' are expected (no 'polygons' in the result of %r)" % (name,))
+        regions = []
+        for i, loops in enumerate(r["polygons"]):
+            cid = int(r["class_ids"][i])
+            label = str(cid) if class_names is None else str(class_names[cid])
+            for loop in outer_loops(loops):
+                pts = np.asarray(simplify(loop, tolerance), np.float64) - 0.5
+                regions.append({"shape_attributes": {"name": "polygon", "all_points_x": pts[:, 0].tolist(), "all_points_y": pts[:, 1].tolist()},
+                                "region_attributes": {"class": label, "score": float(r["confidence_scores"][i]), "instance": i}})
+        out["%s-1" % name] = {"filename": str(name), "size": -1, "regions": regions, "file_attributes": {}}
+    return out
+
+
 def load_via(dataset_dir, subset, annotation=None, class_attribute=None, class_names=None):
     """-> a prepared VIADataset of <dataset_dir>/<subset>/<annotation> (default: the one via_*.json there), VIA 1.x (`regions` a dict) or 2.x
     (a list); images without regions are skipped.
