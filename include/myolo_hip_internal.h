@@ -409,18 +409,6 @@ int myolo_mosaic_batch(const uint8_t* src_images,   /* [B,H,W,3] */
                        int B, int H, int W, int T, int G, int A, int C,
                        void* ws, size_t ws_bytes, void* stream);
 
-/* ---- polygon rasteriser (myolo/via.py datasets, csrc/polygon_kernels.hip; arithmetic contract: DESIGN.md "Polygon annotations").  Fills the
- * outlines of a batch into the instance masks myolo_augment_batch reads: masks[b,i,j,t] = 1 when skimage.draw.polygon (0.18.3) lists source pixel
- * (src_row[b,i], src_col[b,j]) for the polygon of slot b*T+t.  The two tables are made on the host by the rule of resize_mask (the identity for an
- * image already at network size); they only name pixels inside the source frame, which is all the frame clipping there is.  No limit on the
- * vertices of a polygon, nor on T. */
-int myolo_polygon_masks(const double* verts,      /* [n_total,2] (row, col), source-image pixels */
-                        const int32_t* poly_off,  /* [B*T+1] offsets into verts; slot k empty when off[k+1]==off[k] */
-                        const int32_t* src_row,   /* [B,H] source row that output row i samples */
-                        const int32_t* src_col,   /* [B,W] */
-                        uint8_t* masks,           /* [B,H,W,T] 0/1, EVERY element written */
-                        int B, int H, int W, int T, void* stream);
-
 /* ---- inference input of any size (MaskYOLO.detect / detect_many, csrc/resize_kernels.hip; arithmetic contract: DESIGN.md section 14).  Declared here
  * rather than in the operator API (myolo_hip.h, held to 70 entries).  B uint8 [h,w,3] images of mixed sizes, packed back to back in src at ANY byte
  * offset, resized to the network frame: per image and channel myolo_utils.resize(image, (H, W), preserve_range=True).astype(uint8) in binary64 --
@@ -436,12 +424,15 @@ int myolo_resize_images_u8(const uint8_t* src, size_t src_bytes,
                            float* out_unit,          /* [B,H,W,3] or NULL; at least one of the two */
                            int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- segment rasteriser (myolo/coco.py datasets, csrc/segment_kernels.hip; contract: DESIGN.md section 18).  Declared here rather than in the
- * operator API (myolo_hip.h, held to 70 entries).  myolo_polygon_masks for COCO segmentations: the slot b*T+t holds any number of polygon parts and /
- * or one run-length code, and masks[b,i,j,t] = 1 when source pixel (r, c) = (src_row[b,i], src_col[b,j]) is ON in any of the slot's parts under the
- * polygon rasteriser's rule (every part with its own start vertex, parities and vertex flag: a union, not even-odd across parts), or when the number
+/* ---- segment rasteriser (myolo/coco.py and myolo/via.py datasets, csrc/segment_kernels.hip; contract: DESIGN.md sections 13 and 18).  Declared
+ * here rather than in the operator API (myolo_hip.h, held to 70 entries).  Fills the annotations of a batch into the instance masks
+ * myolo_augment_batch reads: the slot b*T+t holds any number of polygon parts (a VIA outline is one part) and / or one run-length code, and
+ * masks[b,i,j,t] = 1 when source pixel (r, c) = (src_row[b,i], src_col[b,j]) is ON in any of the slot's parts -- skimage.draw.polygon (0.18.3)
+ * lists it for that part; every part with its own start vertex, parities and vertex flag: a union, not even-odd across parts -- or when the number
  * of the slot's boundaries <= c * src_h[b] + r is odd.  A slot with neither parts nor boundaries is empty (an all-zero code has no boundary, an
- * all-one code the single boundary 0).  No limit on parts, vertices, runs or T; the offsets are trusted.  boxes, when given, receives the tight box of
+ * all-one code the single boundary 0).  The two tables are made on the host by the rule of resize_mask (the identity for an image already at
+ * network size); they only name pixels inside the source frame, which is all the frame clipping there is.  No limit on parts, vertices, runs or T;
+ * the offsets are trusted (the callers build them: myolo_utils.pack_segments).  boxes, when given, receives the tight box of
  * every slot's set pixels in the output frame (integer atomicMin / atomicMax: the same from run to run).
  * MYOLO_EINVAL (message "segment_masks: ...", nothing launched) for a null pointer other than verts, bounds and boxes, and for B, H, W, T <= 0. */
 int myolo_segment_masks(const double* verts,        /* [n_verts,2] (row, col), source-image pixels; may be NULL when there is no part */

@@ -1,9 +1,13 @@
-// Segment rasteriser (myolo/coco.py datasets through Net.stage_segments and MaskYOLO.evaluate): decodes the COCO segmentations of a batch straight
-// into the [B,H,W,T] instance masks the device augmenter and the overlap counter read.  A slot holds any number of polygon parts, whose fills are
-// OR-ed, and / or one run-length code; no mask is built on the host or crosses PCIe.
+// Segment rasteriser (myolo/coco.py and myolo/via.py datasets through Net.stage_segments, MaskYOLO.evaluate and anchors.dataset_boxes): decodes the
+// annotations of a batch straight into the [B,H,W,T] instance masks the device augmenter and the overlap counter read.  A slot holds any number of
+// polygon parts, whose fills are OR-ed, and / or one run-length code (a VIA outline is a slot of one part); no mask is built on the host or
+// crosses PCIe.
 //
-// A part is filled by the rule of csrc/polygon_kernels.hip (skimage.draw.polygon 0.18.3): the same four IEEE binary64
-// operations in the same order, which is why this unit too is compiled with -ffp-contract=off and asks for it again here.  A run-length code is
+// A part is filled as skimage.draw.polygon fills it (scikit-image 0.18.3, restated in myolo/polygon.py): for pixel (y, x) walk the vertices
+// cyclically, count the edges that cross the pixel's row to its right and to its left, and take the pixel when either count is odd or the pixel
+// sits on a vertex.  The arithmetic is a contract: x1*y0, x0*y1, their difference and the quotient by (y0 - y1) are four
+// IEEE binary64 operations in that order.  This unit is compiled with -ffp-contract=off and asks for it again here: with float vertices a fused
+// multiply-add can flip the sign of x1*y0 - x0*y1 for a pixel next to an edge.  A run-length code is
 // given by its boundaries (the running sums of its counts without the final total): pixel (r, c) of a source image of height h sits at
 // p = c * h + r and is set when the number of boundaries <= p is odd.  Integer work: exact, and zero-length runs (equal boundaries) cancel.
 #include "myolo_common.h"
@@ -12,7 +16,7 @@
 
 #define SEG_THREADS 256
 #define SEG_WAVES (SEG_THREADS / 64)
-#define SEG_CHUNK 256        // vertices of one part staged in LDS at a time (POLY_CHUNK of the polygon kernel)
+#define SEG_CHUNK 256        // vertices of one part staged in LDS at a time (tests/golden/polygon_fixture.npz records it: outlines of CHUNK-1, CHUNK, CHUNK+1)
 #define SEG_GROUP 32         // instance slots whose bits a lane gathers in one register; also the parts whose row extents are formed at a time
 #define SEG_EPS 1e-12
 
@@ -23,7 +27,7 @@ __device__ __forceinline__ double seg_wave_min(double v)
     return v;
 }
 
-// The polygon kernel's layout: a workgroup owns SEG_WAVES consecutive output rows x 64 consecutive output columns of one image, one wave per row, so
+// A workgroup owns SEG_WAVES consecutive output rows x 64 consecutive output columns of one image, one wave per row, so
 // the source row y and both straddle tests are wave-uniform.  Per group of up to SEG_GROUP slots:
 //   (A) the group's parts are consecutive in part_off (slot_part ascends); they are taken SEG_GROUP at a time: (1) wave w derives the row extent
 //       [min r, max r] of parts w, w + SEG_WAVES, ... from one coalesced read; (2) a part none of the workgroup's rows can meet is skipped by the

@@ -134,7 +134,6 @@ SIGS = {
     "myolo_u8_to_unit_f32": [P, P, L, P],
     "myolo_augment_batch": [P, P, P, P, D, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
     "myolo_mosaic_batch": [P, P, P, P, P, P, D, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
-    "myolo_polygon_masks": [P, P, P, P, P, I, I, I, I, P],
     "myolo_segment_masks": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],

@@ -45,15 +45,6 @@ def _host_boxes(dataset, config, ids):
     return np.concatenate(boxes).astype(np.int32), np.concatenate(index)
 
 
-def _segments_of(dataset, i):
-    """image i's instances as segments (myolo.coco): load_segments' own, or every outline of load_polygons as a one-part segment"""
-    if hasattr(dataset, "load_segments"):
-        segs, _ = dataset.load_segments(i)
-        return list(segs)
-    polys, _ = dataset.load_polygons(i)
-    return [[np.ascontiguousarray(p, np.float64)] for p in polys]
-
-
 def dataset_boxes(dataset, config, device="cuda:0", max_samples=None, slots=32):
     """-> (boxes int32 [n,4] x1,y1,x2,y2 in the network frame (far corner exclusive), image_index int64 [n] = the dataset's image id of each box):
     the boxes training sees -- the tight box of every instance's mask after resize_mask's sampling, image by image, instances in order.  An instance
@@ -71,7 +62,7 @@ def dataset_boxes(dataset, config, device="cuda:0", max_samples=None, slots=32):
     if device is None or not (hasattr(dataset, "load_segments") or hasattr(dataset, "load_polygons")):
         return _host_boxes(dataset, config, ids)
     import torch
-    from . import _ext as X
+    from .engine import Net
     T = int(slots)
     if T < 1:
         raise ValueError("dataset_boxes: slots=%r; at least 1" % (slots,))
@@ -79,7 +70,7 @@ def dataset_boxes(dataset, config, device="cuda:0", max_samples=None, slots=32):
     for i in ids:
         info = dataset.image_info[i]
         h, w = int(info["height"]), int(info["width"])
-        segs = _segments_of(dataset, i)
+        segs, _ = mutils.segments_of(dataset, i)
         for s in segs:
             if isinstance(s, dict) and ([int(v) for v in s["size"]] != [h, w] or int(np.sum(s["counts"])) != h * w or h * w >= 1 << 31):
                 raise ValueError("image %r: a run-length code does not cover its %d x %d image" % (i, h, w))
@@ -99,19 +90,8 @@ def dataset_boxes(dataset, config, device="cuda:0", max_samples=None, slots=32):
     with torch.cuda.device(dev):
         for lo in range(0, len(rows_of), B):
             grp = rows_of[lo:lo + B]
-            per_image = [g[1] for g in grp]
-            n_verts, n_parts, n_bounds = mutils.segment_sizes(per_image)
-            verts, part_off = np.zeros((max(n_verts, 1), 2), np.float64), np.zeros(n_parts + 1, np.int32)
-            bounds = np.zeros(max(n_bounds, 1), np.int32)
-            slot_part, slot_bound = np.zeros(B * T + 1, np.int32), np.zeros(B * T + 1, np.int32)
-            mutils.pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound)
-            # (the slots of a short last chunk's padding are empty; their tables name pixel (0, 0))
-            src_h, rows, cols = np.ones(B, np.int32), np.zeros((B, H), np.int32), np.zeros((B, W), np.int32)
-            for k, g in enumerate(grp):
-                rows[k], cols[k] = g[2]
-                src_h[k] = g[3]
-            tables = [torch.from_numpy(a).to(dev) for a in (verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols)]
-            X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(scratch), X.ptr(boxes_d), B, H, W, T, X.stream())
+            tables = [torch.from_numpy(a).to(dev) for a in mutils.segment_tables([g[1:] for g in grp], B, T, H, W)]
+            Net.segment_masks(tables, scratch, boxes_d)
             got = boxes_d.cpu().numpy()                      # (synchronises: the tables are free to go)
             for k, g in enumerate(grp):
                 b = got[k, :len(g[1])]

@@ -2018,40 +2018,25 @@ class Net(object):
             return augmenter.apply(out["raw_images"], out["src_masks"], out["src_ids"], out["aug_params"], yolo=yolo, mosaic=self._mosaic_of(out, mosaic))
         return self._stage_upload(spec, fill, finish)
 
-    def stage_polygons(self, fill, n, augmenter, yolo=False, n_verts=0, mosaic=False):
-        """stage_augmented for outlines instead of masks (myolo.via datasets): fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64
-        [cap,2] (row, col) in source-image pixels packed slot after slot, offsets int32 [n*T+1] into them (slot k empty when off[k+1] == off[k]),
-        class ids int32 [n,T] (0 = empty slot), source-row table int32 [n,H], source-column table int32 [n,W] (myolo_utils.mask_index_tables),
-        parameter rows float64 [n,8]] (BatchGenerator.polygon_batch).  Behind the copies, on the copy stream, myolo_polygon_masks fills the
-        outlines into a device [n,H,W,T] buffer and `augmenter` takes it from there: no mask exists on the host or crosses PCIe.
-        n_verts: the vertices fill will write; the pinned vertex buffer holds cap = the next power of two (at least 1024), so that batches of
-        different outlines share a few staging shapes.  mosaic: as stage_augmented."""
-        cfg, dev = self.cfg, self.dev
-        H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
-        cap = 1024
-        while cap < n_verts:
-            cap *= 2
-        spec = [("raw_images", (n, H, W, 3), torch.uint8), ("poly_verts", (cap, 2), torch.float64), ("poly_off", (n * T + 1,), torch.int32),
-                ("src_ids", (n, T), torch.int32), ("src_row", (n, H), torch.int32), ("src_col", (n, W), torch.int32),
-                ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else [])
-
-        def finish(out):
-            masks = torch.empty((n, H, W, T), dtype=torch.uint8, device=dev)
-            X.call("myolo_polygon_masks", X.ptr(out["poly_verts"]), X.ptr(out["poly_off"]), X.ptr(out["src_row"]), X.ptr(out["src_col"]),
-                   X.ptr(masks), n, H, W, T, X.stream())
-            d = augmenter.apply(out["raw_images"], masks, out["src_ids"], out["aug_params"], yolo=yolo, mosaic=self._mosaic_of(out, mosaic))
-            d["_poly_src"] = (out["poly_verts"], out["poly_off"], out["src_row"], out["src_col"])      # read asynchronously, like _src
-            return d
-        return self._stage_upload(spec, fill, finish)
+    @staticmethod
+    def segment_masks(tables, masks, boxes=None):
+        """myolo_segment_masks on the current stream: tables = the eight device arrays (verts, part_off, slot_part, bounds, slot_bound, src_h,
+        src_row, src_col) of myolo_utils.pack_segments / segment_tables -> masks uint8 [B,H,W,T], every element written, and, when given, boxes
+        int32 [B,T,4].  The caller keeps the tables alive until the launch has run."""
+        B, H, W, T = masks.shape
+        X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(masks), X.ptr(boxes), B, H, W, T, X.stream())
 
     def stage_segments(self, fill, n, augmenter, yolo=False, n_verts=0, n_parts=0, n_bounds=0, mosaic=False):
-        """stage_polygons for COCO segments (myolo.coco datasets): fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64 [cap,2], part
-        offsets int32 [cap+1], slot -> part offsets int32 [n*T+1], boundaries int32 [cap], slot -> boundary offsets int32 [n*T+1], source heights
-        int32 [n], class ids int32 [n,T], source-row table int32 [n,H], source-column table int32 [n,W], parameter rows float64 [n,8]]
-        (BatchGenerator.segment_batch).  Behind the copies, on the copy stream, myolo_segment_masks decodes the segments into a device [n,H,W,T]
-        buffer (no boxes: the augmenter derives them from the warped masks) and `augmenter` takes it from there.
+        """stage_augmented for segments instead of masks (myolo.coco datasets, and myolo.via datasets with every outline a one-part segment):
+        fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64 [cap,2] (row, col) in source-image pixels, part offsets int32 [cap+1],
+        slot -> part offsets int32 [n*T+1], boundaries int32 [cap], slot -> boundary offsets int32 [n*T+1], source heights int32 [n], class ids
+        int32 [n,T] (0 = empty slot), source-row table int32 [n,H], source-column table int32 [n,W] (myolo_utils.mask_index_tables), parameter
+        rows float64 [n,8]] (BatchGenerator.segment_batch).  Behind the copies, on the copy stream, myolo_segment_masks decodes the segments into a
+        device [n,H,W,T] buffer (no boxes: the augmenter derives them from the warped masks) and `augmenter` takes it from there: no mask exists
+        on the host or crosses PCIe.
         n_verts, n_parts, n_bounds: what fill will write; each pinned buffer holds the next power of two (at least 1024, 64, 1024), so that
-        batches of different segments share a few staging shapes.  mosaic: as stage_augmented."""
+        batches of different segments share a few staging shapes; with n_bounds = 0 no boundary buffer is staged at all.  mosaic: as
+        stage_augmented."""
         cfg, dev = self.cfg, self.dev
         H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
 
@@ -2064,16 +2049,22 @@ class Net(object):
                 ("seg_bounds", (cap(n_bounds, 1024),), torch.int32), ("seg_slot_bound", (n * T + 1,), torch.int32), ("seg_src_h", (n,), torch.int32),
                 ("src_ids", (n, T), torch.int32), ("src_row", (n, H), torch.int32), ("src_col", (n, W), torch.int32),
                 ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else [])
+        fill_all = fill
+        if n_bounds == 0:
+            # no code in the batch (always so for outlines): nothing is staged for the boundaries -- fill gets an empty array in their place and
+            # the entry a NULL pointer
+            del spec[4]
+            fill_all = lambda arrays: fill(arrays[:4] + [np.zeros(0, np.int32)] + arrays[4:])      # noqa: E731
 
         def finish(out):
             masks = torch.empty((n, H, W, T), dtype=torch.uint8, device=dev)
-            tables = tuple(out[k] for k in ("seg_verts", "seg_part_off", "seg_slot_part", "seg_bounds", "seg_slot_bound", "seg_src_h", "src_row",
-                                            "src_col"))
-            X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(masks), None, n, H, W, T, X.stream())
+            tables = tuple(out.get(k) for k in ("seg_verts", "seg_part_off", "seg_slot_part", "seg_bounds", "seg_slot_bound", "seg_src_h", "src_row",
+                                                "src_col"))
+            self.segment_masks(tables, masks)
             d = augmenter.apply(out["raw_images"], masks, out["src_ids"], out["aug_params"], yolo=yolo, mosaic=self._mosaic_of(out, mosaic))
-            d["_seg_src"] = tables                          # read asynchronously, like _poly_src
+            d["_seg_src"] = tables                          # read asynchronously, like _src
             return d
-        return self._stage_upload(spec, fill, finish)
+        return self._stage_upload(spec, fill_all, finish)
 
     def _stage_upload(self, spec, fill, finish):
         """one staging set of the ring: fill(arrays) into its pinned buffers (one per (name, shape, dtype) of `spec`), the asynchronous copies

@@ -247,7 +247,7 @@ class MaskYOLO(object):
         self.keras_model = _KerasModelShim(self)
         self.epoch = 0
         # train(): where the launch thread's wall time goes; polygon_batches / segment_batches = the batches that came through
-        # Net.stage_polygons / Net.stage_segments
+        # Net.stage_segments from a dataset with load_polygons / with load_segments
         self.host_times = {"wait_for_batch_s": 0.0, "launch_step_s": 0.0, "steps": 0, "polygon_batches": 0, "segment_batches": 0}
 
     # ------------------------------------------------------------------ build
@@ -392,7 +392,8 @@ class MaskYOLO(object):
         same permutation on every data-parallel rank, so that dp_batch_indices really hands out disjoint samples; None =
         the global numpy generator, as the reference (single process only).
         device_polygons: a train_dataset that has load_polygons (myolo.via.VIADataset) is never asked for a mask: its outlines go to the device
-        and are filled there, in front of the device augmenter (identity rows with augmentation=None) -- DESIGN.md section 13.  An outline that
+        as one-part segments and are filled there, in front of the device augmenter (identity rows with augmentation=None) -- DESIGN.md sections 13
+        and 18.  An outline that
         fills no pixel is dropped on the device, AFTER the sub-sampling to TRUE_BOX_BUFFER instances (the host route drops it before).
         A train_dataset that has load_segments (myolo.coco.COCODataset) goes the same way under the same flag -- "annotations decoded on the
         device": its polygon parts and run-length codes are decoded by myolo_segment_masks.
@@ -428,10 +429,8 @@ class MaskYOLO(object):
 
         polygon_route = bool(device_polygons) and hasattr(train_dataset, "load_polygons")
         segment_route = bool(device_polygons) and not polygon_route and hasattr(train_dataset, "load_segments")
-        if polygon_route:
-            train_info = self._collect_polygons(train_dataset, max_samples)
-        elif segment_route:
-            train_info = self._collect_segments(train_dataset, max_samples)
+        if polygon_route or segment_route:
+            train_info = self._collect_segments(train_dataset, max_samples, load="load_polygons" if polygon_route else "load_segments")
         else:
             train_info = collect(train_dataset, tag=device_augmenter)
         val_info = collect(val_dataset) if val_dataset is not None else []
@@ -465,10 +464,9 @@ class MaskYOLO(object):
                       (ep + 1, i + 1, n_steps, out["loss"], out["yolo_sum_loss"], out["mask_loss"], out["recall"]))
 
         make_item = lambda it: make(it[1])             # noqa: E731
-        if polygon_route:
-            make_item = self._polygon_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
-        elif segment_route:
-            make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
+        if polygon_route or segment_route:
+            make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic,
+                                              counter="polygon_batches" if polygon_route else "segment_batches")
         elif device_augmenter:
             make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
 
@@ -578,10 +576,12 @@ class MaskYOLO(object):
             return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None)
         return make
 
-    def _collect_polygons(self, dataset, max_samples=None):
-        """train()'s sample list on the polygon route: per image [image resized to the network frame uint8, class ids int32 [n], outlines (list of
-        float64 [k,2] (row, col) in source-image pixels), (source-row table int32 [H], source-column table int32 [W]), dataset image id].
-        load_image_gt without load_mask: the tables name the source pixel resize_mask would read for every pixel of the network frame."""
+    def _collect_segments(self, dataset, max_samples=None, first=None, load="load_segments"):
+        """train()'s and evaluate()'s sample list on the device route: per image [image resized to the network frame uint8, class ids int32 [n],
+        segments (a list of float64 [k,2] (row, col) parts in source-image pixels, or a run-length code {"size", "counts"}), (source-row table int32
+        [H], source-column table int32 [W]), dataset image id, source image height].  load_image_gt without load_mask: the tables name the source
+        pixel resize_mask would read for every pixel of the network frame.  load: "load_segments" (myolo.coco), or "load_polygons" (myolo.via):
+        every outline is taken as a one-part segment.  first: keep an image's first `first` segments only (evaluate())."""
         cfg = self.config
         if cfg.USE_MINI_MASK:
             raise NotImplementedError("mini-masks are outside the hot path")
@@ -592,57 +592,13 @@ class MaskYOLO(object):
         info = []
         for i in ids:
             image = dataset.load_image(i)
-            polys, class_ids = dataset.load_polygons(i)
-            polys = [np.ascontiguousarray(p, dtype=np.float64) for p in polys]
-            class_ids = np.asarray(class_ids, dtype=np.int32)
-            if len(polys) != class_ids.shape[0] or any(p.ndim != 2 or p.shape[1] != 2 or p.shape[0] == 0 or not np.isfinite(p).all() for p in polys):
-                raise ValueError("load_polygons(%r): need one finite [k,2] (row, col) array with k >= 1 per class id" % (i,))
-            h, w = image.shape[:2]
-            scale = [1, 1]
-            if [h, w] != [H, W]:
-                image, scale = mutils.resize_image(image, cfg.IMAGE_SHAPE)
-            rows, cols = mutils.mask_index_tables(h, w, scale)
-            if rows.shape[0] != H or cols.shape[0] != W:
-                raise ValueError("image %r: %d x %d does not resize to the %d x %d network frame" % (i, h, w, H, W))
-            info.append([image, class_ids, polys, (rows.astype(np.int32), cols.astype(np.int32)), int(i)])
-        return info
-
-    def _polygon_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
-        """-> make((epoch, batch index)) for train()'s prefetch thread on the polygon route: image bytes, outlines, class ids, index tables and
-        parameter rows go up through the engine's staging ring; the rasteriser and the device augmenter run behind the copies on the copy stream."""
-        from .augment import DeviceAugmenter
-        if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
-            raise ValueError("train() on a dataset with load_polygons needs uint8 images (or device_polygons=False)")
-        aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
-
-        def make(it):
-            epoch, i = it
-            lo, hi = gen.batch_bounds(i)
-            fill, n_verts = gen.polygon_batch(i, self._row_of(augmentation, no_augmentation_sources, dataset, epoch))
-            fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
-            db = self.net.stage_polygons(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, mosaic=mosaic is not None)
-            self.host_times["polygon_batches"] += 1
-            return db
-        return make
-
-    def _collect_segments(self, dataset, max_samples=None, first=None):
-        """_collect_polygons for a dataset with load_segments (myolo.coco): per image [image resized to the network frame uint8, class ids int32 [n],
-        segments (a list of float64 [k,2] (row, col) parts, or a run-length code {"size", "counts"}), (source-row table int32 [H], source-column
-        table int32 [W]), dataset image id, source image height].  first: keep an image's first `first` segments only (evaluate())."""
-        cfg = self.config
-        if cfg.USE_MINI_MASK:
-            raise NotImplementedError("mini-masks are outside the hot path")
-        H, W = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1]
-        ids = list(dataset.image_ids)
-        if max_samples is not None:
-            ids = ids[:max_samples]
-        info = []
-        for i in ids:
-            image = dataset.load_image(i)
-            segs, class_ids = dataset.load_segments(i)
+            segs, class_ids = mutils.segments_of(dataset, i, load)
             class_ids = np.asarray(class_ids, dtype=np.int32)
             h, w = image.shape[:2]
-            if len(segs) != class_ids.shape[0]:
+            if load == "load_polygons":
+                if len(segs) != class_ids.shape[0] or any(p.ndim != 2 or p.shape[1] != 2 or p.shape[0] == 0 or not np.isfinite(p).all() for p, in segs):
+                    raise ValueError("load_polygons(%r): need one finite [k,2] (row, col) array with k >= 1 per class id" % (i,))
+            elif len(segs) != class_ids.shape[0]:
                 raise ValueError("load_segments(%r): %d segments but %d class ids" % (i, len(segs), class_ids.shape[0]))
             for s in segs:
                 if isinstance(s, dict):
@@ -665,11 +621,13 @@ class MaskYOLO(object):
             info.append([image, class_ids, list(segs), (rows.astype(np.int32), cols.astype(np.int32)), int(i), int(h)])
         return info
 
-    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
-        """_polygon_batches on the segment route: Net.stage_segments decodes the segments behind the copies, then the device augmenter runs."""
+    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, counter="segment_batches"):
+        """-> make((epoch, batch index)) for train()'s prefetch thread on the device route: image bytes, segments, class ids, index tables and
+        parameter rows go up through the engine's staging ring; Net.stage_segments decodes the segments behind the copies on the copy stream, then
+        the device augmenter runs.  counter: the key of host_times that counts the batches ("polygon_batches" for a dataset with load_polygons)."""
         from .augment import DeviceAugmenter
         if not all(inst[0].dtype == np.uint8 for inst in gen.all_info):
-            raise ValueError("train() on a dataset with load_segments needs uint8 images (or device_polygons=False)")
+            raise ValueError("train() on a dataset with load_%ss needs uint8 images (or device_polygons=False)" % counter[:-len("_batches")])
         aug = DeviceAugmenter(self.config, self.net.dev, cval=0.0 if augmentation is None else augmentation.cval)
 
         def make(it):
@@ -679,7 +637,7 @@ class MaskYOLO(object):
             fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
             db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds,
                                          mosaic=mosaic is not None)
-            self.host_times["segment_batches"] += 1
+            self.host_times[counter] += 1
             return db
         return make
 
@@ -885,7 +843,6 @@ class MaskYOLO(object):
         device -- no mask is filled on the host, no [B,H,W,T] bytes cross PCIe.  A segment that sets no pixel of the network frame is found by its
         area (myolo_mask_overlap_counts' area_gt) and made padding in _evaluate_stream: it is dropped AFTER the cut to MAX_GT_INSTANCES, where
         load_image_gt drops it before (with at most MAX_GT_INSTANCES segments per image the two routes give equal results)."""
-        from . import _ext as X
         cfg = self.config
         B, T = int(cfg.BATCH_SIZE), int(cfg.MAX_GT_INSTANCES)
         H, W = int(cfg.IMAGE_SHAPE[0]), int(cfg.IMAGE_SHAPE[1])
@@ -899,23 +856,14 @@ class MaskYOLO(object):
             for bi, lo in enumerate(range(0, len(info), B)):
                 grp = info[lo:lo + B]
                 x, _ = stager.stage(bi, [r[0] for r in grp])
-                per_image = [r[2] for r in grp]
-                n_verts, n_parts, n_bounds = mutils.segment_sizes(per_image)
-                verts, part_off = np.zeros((max(n_verts, 1), 2), np.float64), np.zeros(n_parts + 1, np.int32)
-                bounds = np.zeros(max(n_bounds, 1), np.int32)
-                slot_part, slot_bound = np.zeros(B * T + 1, np.int32), np.zeros(B * T + 1, np.int32)
-                mutils.pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound)
-                # (the slots of a short last batch's padding are empty; their tables name pixel (0, 0))
-                src_h, rows, cols = np.ones(B, np.int32), np.zeros((B, H), np.int32), np.zeros((B, W), np.int32)
                 gt_ids = np.zeros((B, T), np.int32)
                 for k, r in enumerate(grp):
                     gt_ids[k, :r[1].shape[0]] = r[1]
-                    rows[k], cols[k] = r[3]
-                    src_h[k] = r[5]
-                tables = [torch.from_numpy(a).to(dev) for a in (verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols)]
+                # (the slots of a short last batch's padding are empty)
+                tables = [torch.from_numpy(a).to(dev) for a in mutils.segment_tables([(r[2], r[3], r[5]) for r in grp], B, T, H, W)]
                 gt_masks = torch.empty((B, H, W, T), dtype=torch.uint8, device=dev)
                 gt_boxes = torch.empty((B, T, 4), dtype=torch.int32, device=dev)
-                X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(gt_masks), X.ptr(gt_boxes), B, H, W, T, X.stream())
+                self.net.segment_masks(tables, gt_masks, gt_boxes)
                 truth.append((len(grp), gt_masks, gt_ids, gt_boxes, True))
                 yield x
         return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)

@@ -139,7 +139,7 @@ def zoom_index(n, o):
 
 def mask_index_tables(h, w, scale):
     """-> (src_row [round(h * scale_y)], src_col [round(w * scale_x)]): the source pixel every pixel of resize_mask's output reads.  Shared by
-    resize_mask and by the polygon rasterisers (myolo.polygon.polygon_mask_sampled, myolo_polygon_masks), which evaluate the fill only there."""
+    resize_mask and by the polygon rasterisers (myolo.polygon.polygon_mask_sampled, myolo_segment_masks), which evaluate the fill only there."""
     return zoom_index(h, int(round(h * scale[0]))), zoom_index(w, int(round(w * scale[1])))
 
 
@@ -175,6 +175,17 @@ def load_image_gt(dataset, config, image_id, augment=False, augmentation=None, u
     class_ids = class_ids[keep]
     bbox = extract_bboxes(mask)
     return image, class_ids, bbox, mask
+
+
+def segments_of(dataset, i, load=None):
+    """-> (segments, class ids): image i's instances as segments (myolo.coco) -- load_segments' own, or every outline of load_polygons (myolo.via)
+    as a one-part segment.  load: which of the two to call; None: load_segments where the dataset has it."""
+    if load is None:
+        load = "load_segments" if hasattr(dataset, "load_segments") else "load_polygons"
+    segs, class_ids = getattr(dataset, load)(i)
+    if load == "load_polygons":
+        segs = [[np.ascontiguousarray(p, dtype=np.float64)] for p in segs]
+    return list(segs), class_ids
 
 
 def segment_sizes(per_image):
@@ -224,6 +235,24 @@ def pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound):
                     part_off[p] = v
     slot_part[len(per_image) * T:] = p
     slot_bound[len(per_image) * T:] = q
+
+
+def segment_tables(group, B, T, H, W):
+    """The eight arrays myolo_segment_masks reads, freshly made for a group of at most B images (the callers that stage nothing: dataset_boxes,
+    evaluate()): group = [(segments, at most T; (source-row table [H], source-column table [W]); source height), ...] -> (verts, part_off,
+    slot_part, bounds, slot_bound, src_h, rows, cols).  Every array has at least one element, whatever the group holds; the rows past len(group) --
+    the padding of a short last group -- have empty slots, source height 1 and tables that name pixel (0, 0)."""
+    per_image = [g[0] for g in group]
+    n_verts, n_parts, n_bounds = segment_sizes(per_image)
+    verts, part_off = np.zeros((max(n_verts, 1), 2), np.float64), np.zeros(n_parts + 1, np.int32)
+    bounds = np.zeros(max(n_bounds, 1), np.int32)
+    slot_part, slot_bound = np.zeros(B * T + 1, np.int32), np.zeros(B * T + 1, np.int32)
+    pack_segments(per_image, T, verts, part_off, slot_part, bounds, slot_bound)
+    src_h, rows, cols = np.ones(B, np.int32), np.zeros((B, H), np.int32), np.zeros((B, W), np.int32)
+    for k, (_, tables, h) in enumerate(group):
+        rows[k], cols[k] = tables
+        src_h[k] = h
+    return verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols
 
 
 class BatchGenerator(object):
@@ -327,53 +356,15 @@ class BatchGenerator(object):
             rows[k] = row_of(inst)
         return out
 
-    def polygon_batch(self, idx, row_of):
-        """The polygon route's form of fill_raw (Net.stage_polygons): the samples are [resized image uint8, class ids int32 [n], outlines (list of
-        float64 [k,2] (row, col) in source-image pixels), (source-row table [H], source-column table [W]), ...] and no mask exists on the host.
-        -> (fill, n_verts): fill(out) writes batch idx INTO out = [raw images uint8 [n,H,W,3], vertices float64 [cap >= n_verts,2], offsets int32
-        [n*T+1], class ids int32 [n,T], source rows int32 [n,H], source columns int32 [n,W], parameter rows float64 [n,8]].  More than T outlines
-        are sub-sampled with the one np.random.choice draw fill_raw makes -- BEFORE anything is rasterised, so an outline that fills no pixel of
-        the network frame can take a slot here that the host route would have given to another instance."""
-        l_bound, r_bound = self.batch_bounds(idx)
-        T = self.config.TRUE_BOX_BUFFER
-        picked = []
-        for inst in self.all_info[l_bound:r_bound]:
-            class_ids, polys = inst[1], inst[2]
-            if inst[0].dtype != np.uint8:
-                raise ValueError("the polygon route needs uint8 images, got %s" % inst[0].dtype)
-            if class_ids.shape[0] > T:
-                ids = np.random.choice(np.arange(class_ids.shape[0]), T, replace=False)
-                class_ids, polys = class_ids[ids], [polys[j] for j in ids]
-            picked.append((inst, class_ids, polys))
-        n_verts = sum(p.shape[0] for _, _, polys in picked for p in polys)
-
-        def fill(out):
-            images, verts, off, ids_b, rows_t, cols_t, rows = out
-            if n_verts > verts.shape[0]:
-                raise ValueError("polygon_batch: %d vertices do not fit the %d staged" % (n_verts, verts.shape[0]))
-            ids_b.fill(0)
-            o = 0
-            for k, (inst, class_ids, polys) in enumerate(picked):
-                images[k] = inst[0]
-                ids_b[k, :class_ids.shape[0]] = class_ids
-                rows_t[k], cols_t[k] = inst[3]
-                for j in range(T):
-                    off[k * T + j] = o
-                    if j < len(polys):
-                        verts[o:o + polys[j].shape[0]] = polys[j]
-                        o += polys[j].shape[0]
-                rows[k] = row_of(inst)
-            off[len(picked) * T] = o
-            return out
-        return fill, n_verts
-
     def segment_batch(self, idx, row_of):
-        """polygon_batch for segments (myolo.coco datasets, Net.stage_segments): the samples are [resized image uint8, class ids int32 [n], segments,
-        (source-row table [H], source-column table [W]), dataset image id, source image height].  -> (fill, n_verts, n_parts, n_bounds): fill(out)
+        """The segment route's form of fill_raw (myolo.coco and myolo.via datasets, Net.stage_segments): the samples are [resized image uint8, class
+        ids int32 [n], segments, (source-row table [H], source-column table [W]), dataset image id, source image height]
+        (MaskYOLO._collect_segments) and no mask exists on the host.  -> (fill, n_verts, n_parts, n_bounds): fill(out)
         writes batch idx INTO out = [raw images uint8 [n,H,W,3], vertices float64 [>= n_verts,2], part offsets int32 [>= n_parts+1], slot -> part
         offsets int32 [n*T+1], boundaries int32 [>= n_bounds], slot -> boundary offsets int32 [n*T+1], source heights int32 [n], class ids int32
         [n,T], source rows int32 [n,H], source columns int32 [n,W], parameter rows float64 [n,8]] (pack_segments).  More than T segments are
-        sub-sampled with the one np.random.choice draw fill_raw makes, before anything is rasterised (polygon_batch's caveat)."""
+        sub-sampled with the one np.random.choice draw fill_raw makes -- BEFORE anything is rasterised, so a segment that fills no pixel of the
+        network frame can take a slot here that the host route would have given to another instance (DESIGN.md sections 13 and 18)."""
         l_bound, r_bound = self.batch_bounds(idx)
         T = self.config.TRUE_BOX_BUFFER
         picked = []
@@ -389,7 +380,6 @@ class BatchGenerator(object):
 
         def fill(out):
             images, verts, part_off, slot_part, bounds, slot_bound, src_h, ids_b, rows_t, cols_t, rows = out
-            pack_segments([segs for _, _, segs in picked], T, verts, part_off, slot_part, bounds, slot_bound)
             ids_b.fill(0)
             for k, (inst, class_ids, _) in enumerate(picked):
                 images[k] = inst[0]
@@ -397,6 +387,9 @@ class BatchGenerator(object):
                 rows_t[k], cols_t[k] = inst[3]
                 src_h[k] = inst[5]
                 rows[k] = row_of(inst)
+            # (after the image copies, which release the interpreter lock: train()'s launch thread is waiting for it when this fill starts, and
+            # the tables are a few hundred microseconds of pure Python)
+            pack_segments([segs for _, _, segs in picked], T, verts, part_off, slot_part, bounds, slot_bound)
             return out
         return fill, n_verts, n_parts, n_bounds
 

@@ -15,7 +15,7 @@ sits on a vertex or an edge as inside.  For pixel (y, x) and vertices (r[i], c[i
         x0, y0 = x1, y1
     ON if r_cross and l_cross differ in parity (edge), or r_cross is odd (inside)  ==  either parity is odd
 
-This is the arithmetic contract of the device rasteriser too (csrc/polygon_kernels.hip): the two products, their
+This is the arithmetic contract of the device rasteriser too (csrc/segment_kernels.hip): the two products, their
 difference and the quotient are single binary64 operations in that order.  Pinned by tests/golden/polygon_fixture.npz (outputs of the real
 function).
 """

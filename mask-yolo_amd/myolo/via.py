@@ -5,7 +5,7 @@ datasets (example/rice/rice_dataset.py:89-167, RiceDataset.load_rice / load_mask
 VIADataset has ShapesDataset's duck-typed surface, so load_image_gt, the host route of MaskYOLO.train() and evaluate() take it as it is:
 load_mask fills every outline with myolo.polygon.polygon_mask (skimage.draw.polygon restated bit for bit).  It also has load_polygons, and
 that is what lets train() keep the masks off the host altogether: the outlines go to the device and are rasterised there
-(myolo_polygon_masks).
+as one-part segments (myolo_segment_masks, DESIGN.md sections 13 and 18).
 
 Differences from the reference: the image size is read from the file header (PIL, no decode) where the reference decodes every image to
 learn it; a region may be mapped to a class by one of its region attributes (the reference has one class); a region that is not a polygon

@@ -10,7 +10,7 @@ Cases, in order (`names[k]`, vertices `verts[off[k]:off[k+1]]` as (row, col) flo
                                          outside the frame on every side, vertices on pixel centres, horizontal edges through pixel rows,
                                          self-intersecting outlines, 1 / 2 / 3-collinear vertices, a closed ring (first vertex repeated), one
                                          outline of 1500 vertices, outlines of LDS_CHUNK - 1, LDS_CHUNK and LDS_CHUNK + 1 vertices (the vertex
-                                         chunk of csrc/polygon_kernels.hip), one polygon wholly outside its frame.
+                                         chunk of csrc/segment_kernels.hip), one polygon wholly outside its frame.
 `bits` = np.packbits of all masks (row-major, case after case).  For every case the generator checks that skimage's (rr, cc) come in row-major
 order, i.e. equal np.nonzero of the mask; the first cases' (rr, cc) are stored as they came (`rr`, `cc`, `rc_off`) so that a test can see it."""
 import glob

@@ -233,12 +233,41 @@ def test_segment_batch_packs_what_the_kernel_reads():
     assert list(src_h) == [64, 80] and list(ids_b[0]) == [1, 2, 0] and (ids_b[1] != 0).all()
     assert np.array_equal(verts[0:3], tri[0]) and np.array_equal(verts[3:7], quad)
     np.random.seed(4)
-    ids = np.random.choice(np.arange(5), T, replace=False)                                # the one draw, as fill_raw / polygon_batch make it
+    ids = np.random.choice(np.arange(5), T, replace=False)                                # the one draw, as fill_raw makes it
     assert np.array_equal(verts[7:16], np.concatenate([tri[j] for j in ids])) and list(ids_b[1]) == [[1, 1, 2, 1, 2][j] for j in ids]
     assert images[1, 0, 0, 0] == 9 and np.array_equal(cols_t[0], tables[1]) and np.array_equal(rows[1], np.arange(8.) + 1)
     for short in (dict(nv=15), dict(npart=4), dict(nb=3)):
         with pytest.raises(ValueError, match="do not fit"):
             fill(buffers(**short))
+
+
+def test_segment_tables_builds_what_dataset_boxes_and_evaluate_hand_the_kernel():
+    """a group of 2 images in B = 3 rows (one padding row), T = 3: a two-part segment, a code and an empty slot; then a group without a part or a
+    code -- the arrays anchors.dataset_boxes and MaskYOLO._evaluate_segments used to build each for itself"""
+    from myolo.myolo_utils import segment_tables
+    B, T, H, W = 3, 3, 5, 7
+    tri = np.array([[1., 2.], [9., 3.], [4., 12.]])
+    quad = np.array([[1., 1.], [1., 5.], [5., 5.], [5., 1.]])
+    code = rle_segment(40, 30, [10, 5, 0, 7, 40 * 30 - 22])
+    t0 = (np.arange(H, dtype=np.int32) * 3, np.arange(W, dtype=np.int32)[::-1] * 2)
+    t1 = (np.arange(H, dtype=np.int32) + 30, np.arange(W, dtype=np.int32) + 4)
+    group = [([[tri, quad], code], t0, 40), ([[tri + 1]], t1, 57)]
+    verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols = segment_tables(group, B, T, H, W)
+    assert verts.dtype == np.float64 and all(a.dtype == np.int32 for a in (part_off, slot_part, bounds, slot_bound, src_h, rows, cols))
+    assert verts.shape == (10, 2) and np.array_equal(verts, np.concatenate([tri, quad, tri + 1])) and list(part_off) == [0, 3, 7, 10]
+    assert list(bounds) == [10, 15, 15, 22]
+    # image 0: two parts, a code, an empty slot; image 1: one part and two empty slots; constant past the last image
+    assert list(slot_part) == [0, 2, 2, 2, 3, 3] + [3] * (T + 1) and list(slot_bound) == [0, 0, 4, 4, 4, 4] + [4] * (T + 1)
+    assert list(src_h) == [40, 57, 1]
+    assert np.array_equal(rows[0], t0[0]) and np.array_equal(cols[0], t0[1]) and np.array_equal(rows[1], t1[0]) and np.array_equal(cols[1], t1[1])
+    assert rows.shape == (B, H) and cols.shape == (B, W) and not rows[2].any() and not cols[2].any()
+    # no part and no code: at least one element everywhere, every slot empty
+    verts, part_off, slot_part, bounds, slot_bound, src_h, rows, cols = segment_tables([([], t1, 57)], B, T, H, W)
+    assert verts.shape == (1, 2) and not verts.any() and list(part_off) == [0] and list(bounds) == [0]
+    assert slot_part.shape == slot_bound.shape == (B * T + 1,) and not slot_part.any() and not slot_bound.any()
+    assert list(src_h) == [57, 1, 1] and np.array_equal(rows[0], t1[0]) and not rows[1:].any() and not cols[1:].any()
+    with pytest.raises(ValueError, match="for 3 slots"):
+        segment_tables([([[tri]] * 4, t1, 57)], B, T, H, W)
 
 
 # ---------------------------------------------------------------- the binding

@@ -294,8 +294,9 @@ def test_train_end_to_end_with_mosaic():
 
 
 def test_polygon_and_segment_routes_give_the_dense_routes_mosaic():
-    """outlines of the Shapes instances (the box of each mask with one corner cut off) through the polygon route and, as one-part segments, through
-    the segment route, and their host fill through the dense route: the same plan, the same mosaicked batch"""
+    """outlines of the Shapes instances (the box of each mask with one corner cut off) as one-part segments through the device route, counted once as
+    a load_polygons dataset's and once as a load_segments dataset's batch, and their host fill through the dense route: the same plan, the same
+    mosaicked batch"""
     import torch
     from myolo.augment import Augmentation, Mosaic
     from myolo.model import MaskYOLO
@@ -311,14 +312,14 @@ def test_polygon_and_segment_routes_give_the_dense_routes_mosaic():
         filled = np.stack([polygon_mask(o[:, 0], o[:, 1], (64, 64)) for o in outlines], axis=-1)
         assert filled.any(axis=(0, 1)).all()
         dense.append([image, class_ids, boxes, filled, 40 + k])
-        poly.append([image, np.asarray(class_ids, np.int32), outlines, tables, 40 + k])
+        poly.append([image, np.asarray(class_ids, np.int32), [[o] for o in outlines], tables, 40 + k, 64])
         seg.append([image, np.asarray(class_ids, np.int32), [[o] for o in outlines], tables, 40 + k, 64])
     model = MaskYOLO(mode="training", config=cfg)
     aug, mosaic = Augmentation(seed=2, **FULL), Mosaic(seed=6)
     gen_d = BatchGenerator(dense, cfg, 'training', shuffle=False, norm=True)
     gen_p = BatchGenerator(poly, cfg, 'training', shuffle=False, norm=True)
     a = model._augmented_batches(aug, None, None, gen_d, 'training', mosaic)((3, 0))
-    b = model._polygon_batches(aug, None, None, gen_p, 'training', mosaic)((3, 0))
+    b = model._segment_batches(aug, None, None, gen_p, 'training', mosaic, counter="polygon_batches")((3, 0))
     c = model._segment_batches(aug, None, None, BatchGenerator(seg, cfg, 'training', shuffle=False, norm=True), 'training', mosaic)((3, 0))
     torch.cuda.synchronize()
     assert (a["_src"][6].cpu().numpy() != 64).all()             # every sample is mosaicked

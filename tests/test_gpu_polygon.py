@@ -1,13 +1,14 @@
-"""The device polygon rasteriser (csrc/polygon_kernels.hip: myolo_polygon_masks) against the host restatement and against the real scikit-image
-output of the fixture, bit for bit; the route through Net.stage_polygons against the host-mask route through Net.stage_augmented; and
-MaskYOLO.train() on a VIADataset without a single load_mask call."""
+"""VIA outlines through the device rasteriser as one-part segments (csrc/segment_kernels.hip: myolo_segment_masks) against the host restatement and
+against the real scikit-image output of the fixture, bit for bit; the route through Net.stage_segments against the host-mask route through
+Net.stage_augmented; and MaskYOLO.train() on a VIADataset without a single load_mask call."""
 import json
 import os
 
 import numpy as np
 import pytest
 
-from test_polygon_host import GOLDEN, _write_dataset, fixture_cases
+from test_gpu_segments import _pack as pack_segments, _run_kernel as run_segments
+from test_polygon_host import _write_dataset, fixture_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -15,28 +16,16 @@ KEYS = ("images", "true_boxes", "y_true", "gt_ids", "gt_boxes", "gt_masks")
 
 
 def _pack(slots, B, T):
-    """slots[b][t] = [k,2] array or None -> (verts [n,2], off int32 [B*T+1])"""
-    verts, off = [], [0]
-    for b in range(B):
-        for t in range(T):
-            p = slots[b][t]
-            if p is not None:
-                verts.append(np.asarray(p, np.float64))
-            off.append(off[-1] + (0 if p is None else len(p)))
-    return np.concatenate(verts), np.array(off, np.int32)
+    """slots[b][t] = [k,2] array or None -> the five tables of myolo_segment_masks with every outline a one-part segment"""
+    tables = pack_segments([[None if p is None else ([p], None) for p in row] for row in slots], B, T)
+    assert len(tables[1]) - 1 == sum(p is not None for row in slots for p in row) and tables[3].size == 0          # one part per outline, no code
+    return tables
 
 
-def _run_kernel(verts, off, rows, cols, B, H, W, T, prefill=9):
-    import torch
-    from myolo import _ext as X
-    dev = torch.device("cuda:0")
-    assert off[-1] == len(verts) and (np.diff(off) >= 0).all()                      # what the kernel trusts
-    assert rows.shape == (B, H) and cols.shape == (B, W) and rows.dtype == np.int32 and cols.dtype == np.int32
-    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (verts, off, rows, cols)]
-    out = torch.full((B, H, W, T), prefill, dtype=torch.uint8, device=dev)
-    X.call("myolo_polygon_masks", X.ptr(d[0]), X.ptr(d[1]), X.ptr(d[2]), X.ptr(d[3]), X.ptr(out), B, H, W, T, X.stream())
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
+def _run_kernel(tables, src, rows, cols, B, H, W, T):
+    """src: the (h, w) of every source image.  boxes = NULL, as Net.stage_segments calls the entry; the output starts as 9s"""
+    got, _ = run_segments(tables, np.array([h for h, _ in src], np.int32), rows, cols, B, H, W, T, boxes=False)
+    return got
 
 
 @pytest.mark.parametrize("T", [5, 34])
@@ -44,7 +33,6 @@ def test_kernel_equals_the_host_fill_on_synthetic_outlines(T):
     """B = 3, H = 40, W = 56: rows of 56 pixels (no multiple of 64), 40 rows in workgroups of 4, a non-square frame.  Image 0 has identity tables,
     image 1 is sampled down from 97 x 131, image 2 up from 17 x 23.  T = 5: byte stores; T = 34: halfword stores and a second group of slots
     (the kernel gathers 32 slots per register).  The output starts as 9s: an element nobody wrote shows."""
-    from myolo import _ext as X
     from myolo.myolo_utils import mask_index_tables
     from myolo.polygon import polygon_mask_sampled
     c = fixture_cases()
@@ -72,20 +60,12 @@ def test_kernel_equals_the_host_fill_on_synthetic_outlines(T):
             if slots[b][t] is not None:
                 want[b, :, :, t] = polygon_mask_sampled(slots[b][t][:, 0], slots[b][t][:, 1], rows[b], cols[b])
     assert want[0, :, :, 0].any() and want[1, :, :, 3].any() and want[2, :, :, 3].any() and not want[1, :, :, 2].any()
-    verts, off = _pack(slots, B, T)
-    got = _run_kernel(verts, off, rows, cols, B, H, W, T)
+    got = _run_kernel(_pack(slots, B, T), src, rows, cols, B, H, W, T)
     assert got.max() <= 1, "an element was left unwritten"
     for b in range(B):
         for t in range(T):
             assert np.array_equal(got[b, :, :, t], want[b, :, :, t]), (b, t, int((got[b, :, :, t] != want[b, :, :, t]).sum()))
-    # argument checks
-    import torch
-    lib = X.load()
-    buf = torch.zeros(64, dtype=torch.uint8, device="cuda:0")
-    p = X.ptr(buf)
-    assert lib.myolo_polygon_masks(p, p, p, p, None, 1, 1, 1, 1, X.stream()) == -1 and b"null" in lib.myolo_last_error_string()
-    assert lib.myolo_polygon_masks(p, p, p, p, p, 1, 1, 1, 0, X.stream()) == -1 and b"T=0" in lib.myolo_last_error_string()
-    assert lib.myolo_polygon_masks(p, p, p, p, p, 0, 1, 1, 1, X.stream()) == -1
+    # (the argument checks -- null masks, T = 0, B = 0 -- stand in tests/test_gpu_segments.py::test_argument_checks)
 
 
 def test_kernel_equals_scikit_image_on_the_food_validation_annotations():
@@ -94,13 +74,14 @@ def test_kernel_equals_scikit_image_on_the_food_validation_annotations():
     from myolo.myolo_utils import mask_index_tables
     c = fixture_cases()
     B, H, W, T = 7, 64, 64, 8
-    slots, rows, cols = [], [], []
+    slots, rows, cols, src = [], [], [], []
     want = np.zeros((B, H, W, T), np.uint8)
     total = 0
     for b in range(B):
         ks = [k for k, n in enumerate(c["names"]) if n.startswith("real/food/val/%d/" % b)]
         assert 1 <= len(ks) <= T
         h, w = [int(v) for v in c["frames"][ks[0]]]
+        src.append((h, w))
         r, cc = mask_index_tables(h, w, [H / h, W / w])
         rows.append(r)
         cols.append(cc)
@@ -110,8 +91,7 @@ def test_kernel_equals_scikit_image_on_the_food_validation_annotations():
         slots.append([c["verts"][k] for k in ks] + [None] * (T - len(ks)))
         total += len(ks)
     assert total == 21
-    verts, off = _pack(slots, B, T)
-    got = _run_kernel(verts, off, np.stack(rows).astype(np.int32), np.stack(cols).astype(np.int32), B, H, W, T)
+    got = _run_kernel(_pack(slots, B, T), src, np.stack(rows).astype(np.int32), np.stack(cols).astype(np.int32), B, H, W, T)
     assert got.tobytes() == want.tobytes(), int((got != want).sum())
 
 
@@ -143,8 +123,8 @@ def _via_dataset(tmp_path, n_images, tiny_in=None):
 
 
 def test_polygon_route_equals_the_host_mask_route(tmp_path):
-    """Net.stage_polygons (outlines up, masks filled on the device) against Net.stage_augmented fed load_mask's output for the same samples:
-    the six device arrays, bit for bit, with identity rows and with drawn rows (flip and rotation)."""
+    """Net.stage_segments (outlines up as one-part segments, masks filled on the device) against Net.stage_augmented fed load_mask's output for the
+    same samples: the six device arrays, bit for bit, with identity rows and with drawn rows (flip and rotation)."""
     import torch
     from myolo.augment import Augmentation, DeviceAugmenter, IDENTITY_ROW
     from myolo.model import MaskYOLO
@@ -154,7 +134,9 @@ def test_polygon_route_equals_the_host_mask_route(tmp_path):
     model = MaskYOLO(mode="training", config=cfg)
     net = model.net
     host = [list(load_image_gt(ds, cfg, i)) + [int(i)] for i in ds.image_ids]
-    poly = model._collect_polygons(ds)
+    poly = model._collect_segments(ds, load="load_polygons")
+    assert all(len(s) == 1 and np.array_equal(s[0], p) for inst in poly for s, p in zip(inst[2], ds.load_polygons(inst[4])[0]))
+    assert [inst[5] for inst in poly] == [ds.image_info[i]["height"] for i in ds.image_ids]         # the real source heights
     # the tiny outline: one pixel at full resolution, nothing in the network frame -- load_image_gt has dropped it, the polygon samples still hold it
     n1 = len(kept[1]["regions"])
     assert ds.load_mask(1)[0][:, :, 1].sum() == 1 and len(poly[1][2]) == n1 + 1 and len(host[1][1]) == n1 >= 2
@@ -165,8 +147,9 @@ def test_polygon_route_equals_the_host_mask_route(tmp_path):
     for name, rows in (("identity", [IDENTITY_ROW, IDENTITY_ROW]), ("drawn", [drawn.params(0, i, 64, 64) for i in range(2)])):
         row_of = lambda inst: rows[inst[4]]                                          # noqa: E731
         a = net.stage_augmented(lambda arrays: gen_h.fill_raw(0, arrays, row_of), 2, aug)
-        fill, n_verts = gen_p.polygon_batch(0, row_of)
-        b = net.stage_polygons(fill, 2, aug, n_verts=n_verts)
+        fill, n_verts, n_parts, n_bounds = gen_p.segment_batch(0, row_of)
+        assert n_parts == len(poly[0][2]) + len(poly[1][2]) and n_bounds == 0
+        b = net.stage_segments(fill, 2, aug, n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds)
         torch.cuda.synchronize()
         for k in KEYS:
             x, y = a[k].cpu().numpy(), b[k].cpu().numpy()

@@ -1,5 +1,5 @@
 """The device segment rasteriser (csrc/segment_kernels.hip: myolo_segment_masks) against its host restatement (myolo.coco.segment_mask_sampled)
-and against myolo_polygon_masks on the committed VIA outlines, bit for bit; Net.stage_segments against the host-mask route; MaskYOLO.train() and
+and against the real scikit-image masks of the committed VIA outlines, bit for bit; Net.stage_segments against the host-mask route; MaskYOLO.train() and
 MaskYOLO.evaluate() on a COCODataset without a single load_mask call.
 
 (Not here: a COCO ground truth fed back as the prediction scoring 1.0.  tests/test_gpu_evaluate.py builds that case inline in one test function,
@@ -159,9 +159,7 @@ def test_argument_checks():
 @pytest.mark.parametrize("size", [64, 224])
 def test_single_part_segments_equal_the_polygon_kernel_on_the_via_outlines(size):
     """the 228 committed VIA outlines, one image per annotated image and one slot per outline, recast as single-part segments: myolo_segment_masks
-    writes what myolo_polygon_masks writes"""
-    import torch
-    from myolo import _ext as X
+    writes the fixture's real scikit-image mask of every outline, sampled by the image's tables (the reference was the retired polygon kernel)"""
     from myolo.myolo_utils import mask_index_tables
     c = fixture_cases()
     n_real = int(c["fx"]["n_real"])
@@ -172,28 +170,23 @@ def test_single_part_segments_equal_the_polygon_kernel_on_the_via_outlines(size)
         images.setdefault(c["names"][k].rsplit("/", 1)[0], []).append(k)
     B, T = len(images), max(len(v) for v in images.values())
     H = W = size
+    assert (B, T) == (116, 8)
     slots, rows, cols, src_h = [], [], [], []
-    for ks in images.values():
+    ref = np.zeros((B, H, W, T), np.uint8)
+    for b, ks in enumerate(images.values()):
         h, w = [int(v) for v in c["frames"][ks[0]]]
         r, cc = mask_index_tables(h, w, [H / h, W / w])
         rows.append(r)
         cols.append(cc)
         src_h.append(h)
         slots.append([([c["verts"][k]], None) for k in ks] + [None] * (T - len(ks)))
+        for t, k in enumerate(ks):
+            ref[b, :, :, t] = c["masks"][k][r][:, cc]
     rows, cols, src_h = np.stack(rows).astype(np.int32), np.stack(cols).astype(np.int32), np.array(src_h, np.int32)
     packed = _pack(slots, B, T)
-    verts, part_off, slot_part = packed[:3]
-    assert len(part_off) - 1 == n_real
+    assert len(packed[1]) - 1 == n_real
     got, _ = _run_kernel(packed, src_h, rows, cols, B, H, W, T)
-    # the polygon kernel's offsets: per slot, not per part
-    poly_off = part_off[slot_part]
-    dev = torch.device("cuda:0")
-    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (verts, poly_off, rows, cols)]
-    ref = torch.full((B, H, W, T), 9, dtype=torch.uint8, device=dev)
-    X.call("myolo_polygon_masks", X.ptr(d[0]), X.ptr(d[1]), X.ptr(d[2]), X.ptr(d[3]), X.ptr(ref), B, H, W, T, X.stream())
-    torch.cuda.synchronize()
-    ref = ref.cpu().numpy()
-    assert ref.max() == 1 and ref.any(axis=(1, 2)).sum() >= n_real // 2
+    assert ref.max() == 1 and ref.any(axis=(1, 2)).sum() == n_real          # every outline sets a sampled pixel at both sizes
     assert got.tobytes() == ref.tobytes(), int((got != ref).sum())
 
 

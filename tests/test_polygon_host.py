@@ -34,8 +34,8 @@ def test_fixture_holds_what_it_should():
     assert str(fx["skimage_version"]) == "0.18.3"
     assert int(fx["n_real"]) == 228 and len(c["names"]) >= 228 + 190
     chunk = int(fx["lds_chunk"])
-    src = open(os.path.join(os.path.dirname(GOLDEN), "..", "mask-yolo_amd", "csrc", "polygon_kernels.hip")).read()
-    assert "#define POLY_CHUNK %d " % chunk in src                  # the chunk the long outlines were cut for is the kernel's
+    src = open(os.path.join(os.path.dirname(GOLDEN), "..", "mask-yolo_amd", "csrc", "segment_kernels.hip")).read()
+    assert "#define SEG_CHUNK %d " % chunk in src                 # the chunk the long outlines were cut for is the kernel's
     lens = {n: len(v) for n, v in zip(c["names"], c["verts"])}
     for d in (-1, 0, 1):
         assert lens["syn/chunk%+d/0" % d] == chunk + d
@@ -202,28 +202,34 @@ def test_via_class_mapping_and_errors(tmp_path):
 
 
 def test_polygon_batch_packs_what_the_kernel_reads():
-    """BatchGenerator.polygon_batch: offsets, empty slots, the sub-sampling to T outlines and the capacity check -- no GPU."""
+    """BatchGenerator.segment_batch on outlines as one-part segments: offsets, empty slots, the sub-sampling to T outlines and the capacity check
+    -- no GPU."""
     from myolo.config import RiceConfig, make_config
     from myolo.myolo_utils import BatchGenerator
     cfg = make_config(RiceConfig, IMAGE_SHAPE=[64, 64, 3], BATCH_SIZE=2, TRUE_BOX_BUFFER=3, MAX_GT_INSTANCES=3)
     T = 3
     tables = (np.arange(64, dtype=np.int32), np.arange(64, dtype=np.int32)[::-1].copy())
     tri = [np.array([[1., 2.], [9., 3.], [4., 12.]]) + k for k in range(5)]
-    info = [[np.full((64, 64, 3), 7, np.uint8), np.array([1, 2], np.int32), tri[:2], tables, 0],
-            [np.full((64, 64, 3), 9, np.uint8), np.array([1, 1, 2, 1, 2], np.int32), tri, tables, 1]]
+    info = [[np.full((64, 64, 3), 7, np.uint8), np.array([1, 2], np.int32), [[p] for p in tri[:2]], tables, 0, 64],
+            [np.full((64, 64, 3), 9, np.uint8), np.array([1, 1, 2, 1, 2], np.int32), [[p] for p in tri], tables, 1, 80]]
     gen = BatchGenerator(info, cfg, 'training', shuffle=False, norm=True)
     np.random.seed(4)
-    fill, n_verts = gen.polygon_batch(0, lambda inst: np.arange(8.) + inst[4])
-    assert n_verts == 3 * (2 + T)
-    out = [np.zeros((2, 64, 64, 3), np.uint8), np.full((32, 2), -1.), np.full(2 * T + 1, -1, np.int32), np.full((2, T), -1, np.int32),
+    fill, n_verts, n_parts, n_bounds = gen.segment_batch(0, lambda inst: np.arange(8.) + inst[4])
+    assert n_verts == 3 * (2 + T) == 15 and n_parts == 2 + T == 5 and n_bounds == 0
+    out = [np.zeros((2, 64, 64, 3), np.uint8), np.full((32, 2), -1.), np.full(8 + 1, -1, np.int32), np.full(2 * T + 1, -1, np.int32),
+           np.full(4, -1, np.int32), np.full(2 * T + 1, -1, np.int32), np.full(2, -1, np.int32), np.full((2, T), -1, np.int32),
            np.zeros((2, 64), np.int32), np.zeros((2, 64), np.int32), np.zeros((2, 8))]
     fill(out)
-    assert list(out[2]) == [0, 3, 6, 6, 9, 12, 15] and (out[1][15:] == -1).all()
-    assert list(out[3][0]) == [1, 2, 0] and (out[3][1] != 0).all()
-    assert np.array_equal(out[1][0:3], tri[0]) and np.array_equal(out[1][3:6], tri[1])
+    images, verts, part_off, slot_part, bounds, slot_bound, src_h, ids_b, rows_t, cols_t, rows = out
+    # the vertex offset of every slot, as the kernel derives it: one part per live slot, none for the empty one
+    assert list(part_off[slot_part]) == [0, 3, 6, 6, 9, 12, 15] and list(slot_part) == [0, 1, 2, 2, 3, 4, 5] and (verts[15:] == -1).all()
+    assert list(part_off[:6]) == [0, 3, 6, 9, 12, 15] and not slot_bound.any() and (bounds == -1).all() and list(src_h) == [64, 80]
+    assert list(ids_b[0]) == [1, 2, 0] and (ids_b[1] != 0).all()
+    assert np.array_equal(verts[0:3], tri[0]) and np.array_equal(verts[3:6], tri[1])
     np.random.seed(4)
     ids = np.random.choice(np.arange(5), T, replace=False)
-    assert np.array_equal(out[1][6:15], np.concatenate([tri[j] for j in ids])) and list(out[3][1]) == [[1, 1, 2, 1, 2][j] for j in ids]
-    assert out[0][1, 0, 0, 0] == 9 and np.array_equal(out[5][0], tables[1]) and np.array_equal(out[6][1], np.arange(8.) + 1)
+    assert np.array_equal(verts[6:15], np.concatenate([tri[j] for j in ids])) and list(ids_b[1]) == [[1, 1, 2, 1, 2][j] for j in ids]
+    assert images[1, 0, 0, 0] == 9 and np.array_equal(cols_t[0], tables[1]) and np.array_equal(rows_t[1], tables[0])
+    assert np.array_equal(rows[1], np.arange(8.) + 1)
     with pytest.raises(ValueError, match="do not fit"):
-        fill([out[0], np.zeros((8, 2))] + out[2:])
+        fill([images, np.zeros((8, 2))] + out[2:])

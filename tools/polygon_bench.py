@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """What the on-device polygon rasteriser costs and saves (profiles/polygon_notes.md records a run), one JSON line:
-  kernel   microseconds per myolo_polygon_masks at 224 x 224 / batch 32 / T 10 on the food outlines of tests/golden/via (cycled to fill the
-           batch, each image sampled from its own frame), HIP events around LAUNCHES back-to-back calls; the 16 MB it writes over that time as a
+  kernel   microseconds per myolo_segment_masks at 224 x 224 / batch 32 / T 10 on the food outlines of tests/golden/via as single-part segments
+           with boxes = NULL, as Net.stage_segments calls it (cycled to fill the batch, each image sampled from its own frame), HIP events
+           around LAUNCHES back-to-back calls; the 16 MB it writes over that time as a
            fraction of the copy bandwidth (_ext.measure_hbm_copy_gbs, "float4", same process); and the time of the H2D copy of those 16 MB of
            masks from pinned memory, which is what the host-mask route pays instead;
   train    per step of MaskYOLO.train() over the same VIADataset (N images written as PNGs into a temporary directory), device_polygons True
@@ -25,6 +26,7 @@ import torch                                                   # noqa: E402
 from myolo import _ext as X                                    # noqa: E402
 from myolo import myolo_utils as mutils                        # noqa: E402
 from myolo.config import make_config, ShapesConfig             # noqa: E402
+from myolo.engine import Net                                   # noqa: E402
 from myolo.model import MaskYOLO                               # noqa: E402
 from myolo.via import load_via                                 # noqa: E402
 
@@ -67,22 +69,17 @@ def timed(fn, n):
 imgs = food_images()
 if KERNEL:
     dev = torch.device("cuda:0")
-    verts, off, rows, cols = [], [0], [], []
+    group = []
     for b in range(B):
         h, w, polys, _ = imgs[b % len(imgs)]
         r, c = mutils.mask_index_tables(h, w, [H / h, W / w])
-        rows.append(r)
-        cols.append(c)
-        for t in range(T):
-            if t < len(polys):
-                verts.append(polys[t])
-            off.append(off[-1] + (len(polys[t]) if t < len(polys) else 0))
-    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in
-         (np.concatenate(verts), np.array(off, np.int32), np.stack(rows).astype(np.int32), np.stack(cols).astype(np.int32))]
+        group.append(([[p] for p in polys[:T]], (r.astype(np.int32), c.astype(np.int32)), h))
+    n_verts, n_outlines, _ = mutils.segment_sizes([g[0] for g in group])
+    d = [torch.from_numpy(a).to(dev) for a in mutils.segment_tables(group, B, T, H, W)]
     masks = torch.empty((B, H, W, T), dtype=torch.uint8, device=dev)
 
     def call():
-        X.call("myolo_polygon_masks", X.ptr(d[0]), X.ptr(d[1]), X.ptr(d[2]), X.ptr(d[3]), X.ptr(masks), B, H, W, T, X.stream())
+        Net.segment_masks(d, masks)
     timed(call, 20)
     us = sorted(1e3 * timed(call, LAUNCHES) / LAUNCHES for _ in range(5))
     pinned = torch.empty((B, H, W, T), dtype=torch.uint8, pin_memory=True)
@@ -91,7 +88,7 @@ if KERNEL:
     h2d = sorted(1e3 * timed(lambda: masks.copy_(pinned, non_blocking=True), 20) / 20 for _ in range(5))
     copy = X.measure_hbm_copy_gbs(device="cuda:0")
     nbytes = B * H * W * T
-    res["kernel"] = {"outlines": len(verts), "vertices": int(off[-1]), "set_fraction": float(masks.float().mean().item()),
+    res["kernel"] = {"outlines": n_outlines, "vertices": n_verts, "set_fraction": float(masks.float().mean().item()),
                      "us_per_launch_runs": us, "us_per_launch": us[2], "bytes_written": nbytes,
                      "write_gbs": nbytes / us[2] / 1e3, "hbm_copy_float4_gbs": copy["float4"],
                      "fraction_of_copy": nbytes / us[2] / 1e3 / copy["float4"],
@@ -115,21 +112,23 @@ if TRAIN:
         json.dump(ann, open(os.path.join(folder, "via_food_annotation.json"), "w"))
         ds = load_via(tmp, "train")
 
-        def held(info):
-            tot = 0
-            for inst in info:
-                for v in inst:
-                    for a in (v if isinstance(v, (list, tuple)) else [v]):
-                        tot += a.nbytes if isinstance(a, np.ndarray) else 0
-            return tot
+        def held(v):
+            if isinstance(v, (list, tuple)):
+                return sum(held(a) for a in v)
+            return v.nbytes if isinstance(v, np.ndarray) else 0
         probe = MaskYOLO(mode="training", config=cfg)
         t0 = time.perf_counter()
         host_info = [list(mutils.load_image_gt(ds, cfg, i)) for i in ds.image_ids]
         t1 = time.perf_counter()
-        poly_info = probe._collect_polygons(ds)
+        poly_info = probe._collect_segments(ds, load="load_polygons")
         t2 = time.perf_counter()
         G, A, C = cfg.GRID_W, cfg.N_BOX, cfg.NUM_CLASSES
-        nv = max(1024, 1 << int(np.ceil(np.log2(max(1, sum(p.shape[0] for inst in poly_info[:B] for p in inst[2][:T]))))))
+
+        def cap(need, least):                                                           # Net.stage_segments' staging shapes
+            while least < need:
+                least *= 2
+            return least
+        nv, npart, nb = mutils.segment_sizes([inst[2][:T] for inst in poly_info[:B]])
         res["train"] = {
             "images": N, "steps_per_epoch": (N + B - 1) // B,
             "collect_seconds": {"host_masks": t1 - t0, "polygons": t2 - t1},
@@ -137,7 +136,8 @@ if TRAIN:
             "bytes_staged_per_step": {
                 "host_masks": B * H * W * 3 + B * T * 4 * 4 + B * G * G * A * (5 + C) * 4 + B * T * 4 + B * T * 4 * 4 + B * H * W * T,
                 "host_masks_augmented": B * H * W * 3 + B * H * W * T + B * T * 4 + B * 8 * 8,
-                "polygons": B * H * W * 3 + nv * 16 + (B * T + 1) * 4 + B * T * 4 + B * H * 4 + B * W * 4 + B * 8 * 8}}
+                "polygons": B * H * W * 3 + cap(nv, 1024) * 16 + (cap(npart, 64) + 1) * 4 + 2 * (B * T + 1) * 4 + (cap(nb, 1024) * 4 if nb else 0) + B * 4 +
+                B * T * 4 + B * H * 4 + B * W * 4 + B * 8 * 8}}
         del probe, host_info, poly_info
         for name, flag in (("polygons", True), ("host_masks", False)) * RUNS:           # alternating: other work shares the host
             model = MaskYOLO(mode="training", config=cfg)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """What the on-device segment rasteriser costs (profiles/segment_notes.md records a run), one JSON line.  224 x 224, batch 32, T 10, on the food
-outlines of tests/golden/via (cycled to fill the batch, each image sampled from its own frame), three cases, microseconds per launch:
-  polygon        myolo_polygon_masks (unchanged) on the outlines;
-  segment_parts  myolo_segment_masks on the same outlines as single-part segments (boxes = NULL, as Net.stage_segments calls it);
+outlines of tests/golden/via (cycled to fill the batch, each image sampled from its own frame), two cases, microseconds per launch:
+  segment_parts  myolo_segment_masks on the outlines as single-part segments (boxes = NULL, as Net.stage_segments calls it);
   segment_rle    myolo_segment_masks on the same masks, each filled at full resolution on the host and handed over as a run-length code.
-After a warm-up the three cases run REPS = 5 repetitions of LAUNCHES back-to-back launches each, alternating case by case (so that a drift of the
-clock falls on all three alike), HIP events around every repetition; reported: every repetition, the median, and the ratios of the medians with the
-spread (max / min) of the repetitions beside them.  The three outputs are compared byte for byte before anything is timed.
+After a warm-up the two cases run REPS = 5 repetitions of LAUNCHES back-to-back launches each, alternating case by case (so that a drift of the
+clock falls on both alike), HIP events around every repetition; reported: every repetition, the median, and the ratio of the medians with the
+spread (max / min) of the repetitions beside them.  The two outputs are compared byte for byte before anything is timed.  (The recorded run had a
+third case, the polygon kernel that has since been retired: the same outlines took 0.994 of its time as single-part segments.)
   python tools/segment_rate.py [LAUNCHES=200] [REPS=5]
 """
 import json
@@ -18,9 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mask-yolo_amd")]
 import numpy as np                                             # noqa: E402
 import torch                                                   # noqa: E402
-from myolo import _ext as X                                    # noqa: E402
 from myolo import myolo_utils as mutils                        # noqa: E402
 from myolo import rle                                          # noqa: E402
+from myolo.engine import Net                                   # noqa: E402
 from myolo.polygon import polygon_mask                         # noqa: E402
 
 LAUNCHES, REPS = int(over.get("LAUNCHES", 200)), int(over.get("REPS", 5))
@@ -57,52 +57,28 @@ def timed(fn, n):
 
 
 imgs = food_images()
-per_image_parts, per_image_codes, rows, cols, src_h, poly_verts, poly_off = [], [], [], [], [], [], [0]
+group_parts, group_codes = [], []
 codes_of = {}
 for b in range(B):
     k = b % len(imgs)
     h, w, polys = imgs[k]
     polys = polys[:T]
     r, c = mutils.mask_index_tables(h, w, [H / h, W / w])
-    rows.append(r)
-    cols.append(c)
-    src_h.append(h)
     if k not in codes_of:
         codes_of[k] = [rle.encode(polygon_mask(p[:, 0], p[:, 1], (h, w))) for p in polys]
-    per_image_parts.append([[p] for p in polys])
-    per_image_codes.append(codes_of[k])
-    for t in range(T):
-        if t < len(polys):
-            poly_verts.append(polys[t])
-        poly_off.append(poly_off[-1] + (len(polys[t]) if t < len(polys) else 0))
-rows, cols, src_h = np.stack(rows).astype(np.int32), np.stack(cols).astype(np.int32), np.array(src_h, np.int32)
-
-
-def tables(per_image):
-    nv, npart, nb = mutils.segment_sizes(per_image)
-    a = [np.zeros((max(nv, 1), 2)), np.zeros(npart + 1, np.int32), np.zeros(B * T + 1, np.int32), np.zeros(max(nb, 1), np.int32),
-         np.zeros(B * T + 1, np.int32)]
-    mutils.pack_segments(per_image, T, *a)
-    return [torch.from_numpy(x).to(dev) for x in a + [src_h, rows, cols]], (nv, npart, nb)
-
-
-def up(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-d_poly = [up(np.concatenate(poly_verts)), up(np.array(poly_off, np.int32)), up(rows), up(cols)]
-d_parts, n_parts = tables(per_image_parts)
-d_codes, n_codes = tables(per_image_codes)
-out = {name: torch.full((B, H, W, T), 9, dtype=torch.uint8, device=dev) for name in ("polygon", "segment_parts", "segment_rle")}
-calls = {
-    "polygon": lambda: X.call("myolo_polygon_masks", *[X.ptr(t) for t in d_poly], X.ptr(out["polygon"]), B, H, W, T, X.stream()),
-    "segment_parts": lambda: X.call("myolo_segment_masks", *[X.ptr(t) for t in d_parts], X.ptr(out["segment_parts"]), None, B, H, W, T, X.stream()),
-    "segment_rle": lambda: X.call("myolo_segment_masks", *[X.ptr(t) for t in d_codes], X.ptr(out["segment_rle"]), None, B, H, W, T, X.stream()),
-}
+    index = (r.astype(np.int32), c.astype(np.int32))
+    group_parts.append(([[p] for p in polys], index, h))
+    group_codes.append((codes_of[k], index, h))
+sizes = {"segment_parts": mutils.segment_sizes([g[0] for g in group_parts]), "segment_rle": mutils.segment_sizes([g[0] for g in group_codes])}
+d_parts = [torch.from_numpy(a).to(dev) for a in mutils.segment_tables(group_parts, B, T, H, W)]
+d_codes = [torch.from_numpy(a).to(dev) for a in mutils.segment_tables(group_codes, B, T, H, W)]
+out = {name: torch.full((B, H, W, T), 9, dtype=torch.uint8, device=dev) for name in ("segment_parts", "segment_rle")}
+calls = {"segment_parts": lambda: Net.segment_masks(d_parts, out["segment_parts"]),
+         "segment_rle": lambda: Net.segment_masks(d_codes, out["segment_rle"])}
 for fn in calls.values():
     fn()
 torch.cuda.synchronize()
-ref = out["polygon"].cpu().numpy()
+ref = out["segment_parts"].cpu().numpy()
 same = {name: bool(np.array_equal(out[name].cpu().numpy(), ref)) for name in out}
 assert all(same.values()), same
 for fn in calls.values():                                      # warm-up: clocks, caches, code objects
@@ -112,9 +88,9 @@ for _ in range(REPS):
     for name, fn in calls.items():                             # alternating
         us[name].append(1e3 * timed(fn, LAUNCHES) / LAUNCHES)
 med = {name: float(np.median(v)) for name, v in us.items()}
-res = {"shape": {"B": B, "H": H, "W": W, "T": T}, "outlines": len(poly_verts), "vertices": int(poly_off[-1]), "rle_boundaries": n_codes[2],
+res = {"shape": {"B": B, "H": H, "W": W, "T": T}, "outlines": sizes["segment_parts"][1], "vertices": sizes["segment_parts"][0],
+       "rle_boundaries": sizes["segment_rle"][2],
        "set_fraction": float(ref.mean()), "launches_per_repetition": LAUNCHES, "us_per_launch_repetitions": us, "us_per_launch_median": med,
        "spread_max_over_min": {name: float(max(v) / min(v)) for name, v in us.items()},
-       "segment_parts_over_polygon": med["segment_parts"] / med["polygon"], "segment_rle_over_polygon": med["segment_rle"] / med["polygon"],
-       "outputs_equal": same}
+       "segment_rle_over_segment_parts": med["segment_rle"] / med["segment_parts"], "outputs_equal": same}
 print(json.dumps(res))
