@@ -6,7 +6,7 @@ written as a COCO results file, category ids mapped back through the dataset.
 
   python example/coco/train_coco.py TRAIN_JSON TRAIN_IMAGES [--val-json PATH --val-images DIR] [--categories 1,3,17] [--keep-crowd]
                                     [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--results PATH]
-                                    [--fit-anchors K] [--mosaic P]
+                                    [--fit-anchors K] [--mosaic P] [--copy-paste P]
 
 --fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
 Config's, which were fitted to UECFOOD100 at 224 x 224.
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 from myolo import rle                                # noqa: E402
 from myolo.anchors import fit_anchors                # noqa: E402
-from myolo.augment import Augmentation, Mosaic       # noqa: E402
+from myolo.augment import Augmentation, CopyPaste, Mosaic       # noqa: E402
 from myolo.coco import load_coco                     # noqa: E402
 from myolo.config import Config, make_config         # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P", help="mosaic a training sample with probability P: four images of the batch "
                                                                             "per sample, on the device (default: 0, off)")
+    ap.add_argument("--copy-paste", type=float, default=0.0, metavar="P", help="paste instances of another sample of the batch into a training "
+                                                                                "sample with probability P, on the device (default: 0, off)")
     ap.add_argument("--host-masks", action="store_true", help="decode the segmentations on the host (load_mask) for the training batches")
     ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: Config's anchors)")
     ap.add_argument("--results", default=None, help="where the validation detections go as a COCO results file (default: LOGS/coco_results.json)")
@@ -61,7 +63,8 @@ def main():
                                                           brightness=(.8, 1.2))
     model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)
     hist = model.train(train, val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all', augmentation=augmentation,
-                       device_polygons=not a.host_masks, mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None)
+                       device_polygons=not a.host_masks, mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None,
+                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None)
     print("epoch losses:", ["%.4f" % h for h in hist])
     print("batches decoded on the device: %d of %d" % (model.host_times["segment_batches"], model.host_times["steps"]))
     os.makedirs(a.logs, exist_ok=True)

@@ -5,7 +5,7 @@ via_*_annotation.json, MaskYOLO(mode="training"), model.train(...)).  The outlin
 is built on the host.
 
   python example/rice/train_rice.py DATASET_DIR [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--fit-anchors K]
-                                             [--mosaic P]
+                                             [--mosaic P] [--copy-paste P]
 
 --fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
 RiceConfig's.
@@ -17,7 +17,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 from myolo.anchors import fit_anchors                # noqa: E402
-from myolo.augment import Augmentation, Mosaic       # noqa: E402
+from myolo.augment import Augmentation, CopyPaste, Mosaic       # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
 from myolo.via import load_via                       # noqa: E402
@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P", help="mosaic a training sample with probability P: four images of the batch "
                                                                             "per sample, on the device (default: 0, off)")
+    ap.add_argument("--copy-paste", type=float, default=0.0, metavar="P", help="paste instances of another sample of the batch into a training "
+                                                                                "sample with probability P, on the device (default: 0, off)")
     ap.add_argument("--host-masks", action="store_true", help="fill the outlines on the host (load_mask) instead of on the device")
     ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: RiceConfig's anchors)")
     a = ap.parse_args()
@@ -50,7 +52,8 @@ def main():
     model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)
     hist = model.train(dataset_train, dataset_val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all',
                        augmentation=augmentation, device_polygons=not a.host_masks,
-                       mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None)
+                       mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None,
+                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None)
     print("epoch losses:", ["%.4f" % h for h in hist])
     print("batches rasterised on the device: %d of %d" % (model.host_times["polygon_batches"], model.host_times["steps"]))
     os.makedirs(a.logs, exist_ok=True)

@@ -409,6 +409,30 @@ int myolo_mosaic_batch(const uint8_t* src_images,   /* [B,H,W,3] */
                        int B, int H, int W, int T, int G, int A, int C,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- copy-paste (myolo/augment.py: CopyPaste; contract: DESIGN.md "Copy-paste").  A second stage behind myolo_augment_batch / myolo_mosaic_batch,
+ * on their outputs: image b receives instances of image d = donor[b] of the same batch.  live(i,t) = src_class_ids[i][t] != 0; S = the slots t,
+ * ascending, with bit t of select[b] set and live(d,t) (empty when d is outside [0, B): the index never becomes an address); A = the first
+ * F = T - #{t: live(b,t)} of S; dropped[b] = |S| - |A|, and a rejected instance is not pasted at all.  U(x,y) = some t in A has src_masks[d,y,x,t]
+ * != 0.  Pixel (x,y) of images[b] is the three floats of src_images[d] under U and of src_images[b] elsewhere, copied bit for bit.  The 2T
+ * candidates are the own slots (live(b,t); pixels src_masks[b,y,x,t] != 0 outside U), then the donor's (t in A; pixels src_masks[d,y,x,t] != 0); one
+ * with no pixel is dropped (not counted), the survivors fill slots 0.. in order.  Masks are 0/1, unused slots zero; boxes, ids and targets as above.
+ * With select all zero, and inputs as the first stage writes them, every output equals the input byte for byte.  No output may lie over an input: a
+ * donor is read in its state before the paste.  The tables are device memory and are NOT read on the host (augment.check_paste_tables).
+ * MYOLO_EINVAL (message "copy_paste_batch: ...", nothing launched or written) for a null pointer (y_true and true_boxes: together or not at all),
+ * bad sizes, T > 32, an output over an input and a workspace under myolo_copy_paste_batch_ws_bytes(B, T). */
+size_t myolo_copy_paste_batch_ws_bytes(int B, int T);
+int myolo_copy_paste_batch(const float*   src_images,   /* [B,H,W,3] */
+                           const uint8_t* src_masks,    /* [B,H,W,T] 0/1 */
+                           const int32_t* src_class_ids,/* [B,T], 0 = empty slot */
+                           const int32_t* donor,        /* [B] batch positions */
+                           const int32_t* select,       /* [B] bit t: donor slot t is selected */
+                           const double* anchors /* [2A] */,
+                           float* images, uint8_t* gt_masks, int32_t* gt_boxes, int32_t* gt_class_ids,
+                           float* y_true /* [B,G,G,A,5+C], or NULL with true_boxes */, float* true_boxes /* [B,T,4] */,
+                           int32_t* dropped /* [B] */,
+                           int B, int H, int W, int T, int G, int A, int C,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ---- inference input of any size (MaskYOLO.detect / detect_many, csrc/resize_kernels.hip; arithmetic contract: DESIGN.md section 14).  Declared here
  * rather than in the operator API (myolo_hip.h, held to 70 entries).  B uint8 [h,w,3] images of mixed sizes, packed back to back in src at ANY byte
  * offset, resized to the network frame: per image and channel myolo_utils.resize(image, (H, W), preserve_range=True).astype(uint8) in binary64 --

@@ -3,6 +3,7 @@
 // image, and writes the warped image (bilinear), the warped instance masks (nearest) with empty instances dropped and the survivors compacted,
 // their tight boxes (extract_bboxes) and BatchGenerator._encode's YOLO targets of those boxes.
 // myolo_mosaic_batch (below the three passes it extends) does the same with four tiles per output image, each read from an image of the batch.
+// myolo_copy_paste_batch is a second stage behind either: it pastes instances of one augmented image of the batch into another.
 //
 // The arithmetic is a contract ("On-device augmentation"): every operation below is ONE IEEE binary64 operation in the order
 // written -- this unit is compiled with -ffp-contract=off and asks for it again here -- so a numpy restatement reproduces every output bit.
@@ -407,6 +408,223 @@ __global__ __launch_bounds__(AUG_THREADS) void mosaic_render_kernel(const uint8_
     aug_write_runs(s_img, s_msk, images, masks, b, HW, pix0, nv, T, words_ok, tid);
 }
 
+// ---- copy-paste ("Copy-paste"): a second stage behind the passes above.  Image b receives the accepted instances of image d = donor[b]
+// of the same, already augmented batch: their pixels replace the image's, their masks occlude its own.  The instance candidates of an image are the 2T
+// pairs (own, t) then (donor, t); masks, boxes and targets are re-derived from the pasted masks by the same three passes.
+#define CP_SIDES 2
+
+// what a workgroup needs of the plan, derived by its first wave from the two id rows and select[b] (T <= 32: every set is one word)
+struct CpPlan {
+    int d;                   // the donor image, b itself when donor[b] lies outside [0, B) (nothing is accepted then: the index never becomes an address)
+    uint32_t own;            // live own slots
+    uint32_t acc;            // accepted donor slots: the lowest F = T - popcount(own) of the selected live ones
+    int dropped;             // selected live donor slots beyond F
+};
+
+// Called by every thread of a workgroup of at least 64 threads; ends in a barrier.
+__device__ __forceinline__ CpPlan cp_plan(const int32_t* __restrict__ ids, const int32_t* __restrict__ donor, const int32_t* __restrict__ select,
+                                          int b, int B, int T, int* s_plan)
+{
+    if (threadIdx.x < 64) {
+        const int t = threadIdx.x;
+        const int d = donor[b];
+        const bool valid = (unsigned)d < (unsigned)B;
+        const uint32_t own = (uint32_t)__ballot(t < T && ids[(long long)b * T + t] != 0);
+        const uint32_t dlive = (uint32_t)__ballot(t < T && valid && ids[(long long)(valid ? d : b) * T + t] != 0);
+        if (t == 0) {
+            const uint32_t sel = (uint32_t)select[b] & dlive;
+            const int room = T - __popc(own);
+            uint32_t acc = sel;
+            while (__popc(acc) > room) acc &= ~(1u << (31 - __clz(acc)));     // the highest slots go first
+            s_plan[0] = valid ? d : b; s_plan[1] = (int)own; s_plan[2] = (int)acc; s_plan[3] = __popc(sel) - __popc(acc);
+        }
+    }
+    __syncthreads();
+    CpPlan p;
+    p.d = s_plan[0]; p.own = (uint32_t)s_plan[1]; p.acc = (uint32_t)s_plan[2]; p.dropped = s_plan[3];
+    return p;
+}
+
+// the statistics of one candidate over a wave's AUG_SPT pixels each: ballot + popcount, shuffles, then the wave's LDS row (zeroed before)
+#define CP_REDUCE(cand_, in_)                                                                                                                \
+    do {                                                                                                                                     \
+        int cnt = 0, a = 0, c = 0, d_ = 0, e = 0;                                                                                            \
+        _Pragma("unroll") for (int j = 0; j < AUG_SPT; ++j) {                                                                                \
+            const bool in = (in_);                                                                                                           \
+            cnt += __popcll(__ballot(in));                                                                                                   \
+            if (in) { a = max(a, W - px[j]); c = max(c, px[j] + 1); d_ = max(d_, H - py[j]); e = max(e, py[j] + 1); }                         \
+        }                                                                                                                                    \
+        if (cnt) {                                             /* wave-uniform: it comes from ballots */                                     \
+            a = aug_wave_max(a); c = aug_wave_max(c); d_ = aug_wave_max(d_); e = aug_wave_max(e);                                             \
+            if (lane == 0) { int* r = red[wave][cand_]; r[0] = cnt; r[1] = a; r[2] = c; r[3] = d_; r[4] = e; }                                \
+        }                                                                                                                                    \
+    } while (0)
+
+// pass 1 of the copy-paste: augment_stats_kernel over the candidates (side, t) with no warp -- the donor's accepted slots first, which also gives the
+// paste region U of the thread's pixels, then the own slots outside U.  A word none of whose slots is accepted (own: live) is not read: an image
+// with nothing accepted reads no donor byte.
+template <int V>
+__global__ __launch_bounds__(AUG_THREADS) void copy_paste_stats_kernel(const uint8_t* __restrict__ masks, const int32_t* __restrict__ ids,
+                                                                       const int32_t* __restrict__ donor, const int32_t* __restrict__ select,
+                                                                       int* __restrict__ stats, int B, int H, int W, int T)
+{
+    __shared__ int red[AUG_WAVES][CP_SIDES * AUG_MAXT][AUG_STAT_INTS];
+    __shared__ int s_plan[4];
+    const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long long HW = (long long)H * W;
+    for (int i = tid; i < AUG_WAVES * CP_SIDES * AUG_MAXT * AUG_STAT_INTS; i += AUG_THREADS) (&red[0][0][0])[i] = 0;
+    const CpPlan plan = cp_plan(ids, donor, select, b, B, T, s_plan);          // (its barrier also covers the zeroed table)
+    const uint8_t* mb = masks + (long long)b * HW * T;
+    const uint8_t* md = masks + (long long)plan.d * HW * T;
+    int px[AUG_SPT], py[AUG_SPT];
+    long long off[AUG_SPT];                                    // byte offset of the pixel's slots, or -1: no pixel (the ragged last workgroup)
+    bool pasted[AUG_SPT];                                      // U
+#pragma unroll
+    for (int j = 0; j < AUG_SPT; ++j) {
+        const long long pix = ((long long)blockIdx.x * AUG_SPT + j) * AUG_THREADS + tid;
+        py[j] = (int)(pix / W); px[j] = (int)(pix - (long long)py[j] * W);
+        off[j] = pix < HW ? pix * T : -1;
+        pasted[j] = false;
+    }
+    const uint32_t lanes_of_word = V == 4 ? 0xfu : V == 2 ? 0x3u : 0x1u;
+    for (int w = 0; w < T; w += V) {
+        if (!((plan.acc >> w) & lanes_of_word)) continue;      // workgroup-uniform
+        uint32_t word[AUG_SPT];
+#pragma unroll
+        for (int j = 0; j < AUG_SPT; ++j) word[j] = off[j] >= 0 ? aug_load<V>(md + off[j] + w) : 0u;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int t = w + k;
+            if (!((plan.acc >> t) & 1u)) continue;
+#pragma unroll
+            for (int j = 0; j < AUG_SPT; ++j) pasted[j] = pasted[j] || ((word[j] >> (8 * k)) & 0xffu) != 0;
+            CP_REDUCE(T + t, ((word[j] >> (8 * k)) & 0xffu) != 0);
+        }
+    }
+    for (int w = 0; w < T; w += V) {
+        if (!((plan.own >> w) & lanes_of_word)) continue;
+        uint32_t word[AUG_SPT];
+#pragma unroll
+        for (int j = 0; j < AUG_SPT; ++j) word[j] = off[j] >= 0 ? aug_load<V>(mb + off[j] + w) : 0u;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int t = w + k;
+            if (!((plan.own >> t) & 1u)) continue;
+            CP_REDUCE(t, !pasted[j] && ((word[j] >> (8 * k)) & 0xffu) != 0);
+        }
+    }
+    __syncthreads();
+    if (tid < CP_SIDES * T) {
+        int cnt = 0, v[4] = {0, 0, 0, 0};
+        for (int w = 0; w < AUG_WAVES; ++w) {
+            cnt += red[w][tid][0];
+            for (int k = 0; k < 4; ++k) v[k] = max(v[k], red[w][tid][1 + k]);
+        }
+        if (cnt) {
+            int* st = stats + ((long long)b * CP_SIDES * T + tid) * AUG_STAT_INTS;
+            atomicAdd(st, cnt);
+            for (int k = 0; k < 4; ++k) atomicMax(st + 1 + k, v[k]);
+        }
+    }
+}
+#undef CP_REDUCE
+
+// pass 2 of the copy-paste (one wave per image): the candidates own first; a live one with no pixel left is dropped and the survivors are compacted
+// in order -- at most popcount(own) + popcount(acc) <= T of them.  The rejected donor slots were counted by the plan.
+__global__ void copy_paste_encode_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ donor, const int32_t* __restrict__ select,
+                                         const int* __restrict__ stats, int* __restrict__ slotmap, int32_t* __restrict__ gt_ids,
+                                         int32_t* __restrict__ gt_boxes, float* __restrict__ y_true, float* __restrict__ true_boxes,
+                                         int32_t* __restrict__ dropped, const double* __restrict__ anchors, int B, int H, int W, int T, int G, int A,
+                                         int C)
+{
+    __shared__ int s_plan[4];
+    const int b = blockIdx.x;
+    const CpPlan plan = cp_plan(ids, donor, select, b, B, T, s_plan);
+    if (threadIdx.x != 0) return;
+    const double cell_w = (double)W / G, cell_h = (double)H / G;
+    int m = 0, tbi = 0;
+    for (int k = 0; k < CP_SIDES * T; ++k) {
+        const long long cand = (long long)b * CP_SIDES * T + k;
+        const int* st = stats + cand * AUG_STAT_INTS;
+        const int t = k < T ? k : k - T;
+        const bool live = ((k < T ? plan.own : plan.acc) >> t) & 1u;
+        slotmap[cand] = -1;
+        if (!live || st[0] <= 0 || m == T) continue;           // (m == T cannot happen: the plan accepted no more than the free slots)
+        slotmap[cand] = m;
+        const int cls = ids[(long long)(k < T ? b : plan.d) * T + t];
+        const int x1 = W - st[1], x2 = st[2], y1 = H - st[3], y2 = st[4];     // extract_bboxes: x2, y2 exclusive
+        gt_ids[b * T + m] = cls;
+        int32_t* gb = gt_boxes + ((long long)b * T + m) * 4;
+        gb[0] = x1; gb[1] = y1; gb[2] = x2; gb[3] = y2;
+        if (y_true) aug_encode_target(b, cls, x1, y1, x2, y2, cell_w, cell_h, anchors, y_true, true_boxes, tbi, T, G, A, C);
+        ++m;
+    }
+    dropped[b] = plan.dropped;
+}
+
+// pass 3 of the copy-paste: a workgroup owns AUG_THREADS consecutive pixels; each thread finds U of its pixel from the donor's accepted slots, takes
+// the pixel's three floats from the donor under U and from the image itself elsewhere (a copy, bit for bit), and writes its mask bytes through the
+// slot map into LDS; then the contiguous runs leave as in the first stage.
+template <int V>
+__global__ __launch_bounds__(AUG_THREADS) void copy_paste_render_kernel(const float* __restrict__ src_images, const uint8_t* __restrict__ src_masks,
+                                                                        const int32_t* __restrict__ ids, const int32_t* __restrict__ donor,
+                                                                        const int32_t* __restrict__ select, const int* __restrict__ slotmap,
+                                                                        float* __restrict__ images, uint8_t* __restrict__ masks,
+                                                                        int B, int H, int W, int T, int words_ok)
+{
+    __shared__ float s_img[AUG_THREADS * 3];
+    __shared__ __attribute__((aligned(4))) uint8_t s_msk[AUG_THREADS * AUG_MAXT];
+    __shared__ int s_slot[CP_SIDES * AUG_MAXT];
+    __shared__ int s_plan[4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const long long HW = (long long)H * W;
+    const long long pix0 = (long long)blockIdx.x * AUG_THREADS, pix = pix0 + tid;
+    const int nv = (int)((HW - pix0) < AUG_THREADS ? (HW - pix0) : AUG_THREADS);      // pixels of this workgroup inside the image
+    if (tid < CP_SIDES * T) s_slot[tid] = slotmap[b * CP_SIDES * T + tid];
+    const CpPlan plan = cp_plan(ids, donor, select, b, B, T, s_plan);
+    const uint32_t lanes_of_word = V == 4 ? 0xfu : V == 2 ? 0x3u : 0x1u;
+    if (tid < nv) {
+        uint8_t* sm = s_msk + tid * T;
+        for (int t = 0; t < T; ++t) sm[t] = 0;
+        bool pasted = false;
+        const uint8_t* mp = src_masks + ((long long)plan.d * HW + pix) * T;
+        for (int w = 0; w < T; w += V) {
+            if (!((plan.acc >> w) & lanes_of_word)) continue;
+            const uint32_t word = aug_load<V>(mp + w);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                if (!((plan.acc >> (w + k)) & 1u) || ((word >> (8 * k)) & 0xffu) == 0) continue;
+                pasted = true;
+                const int slot = s_slot[T + w + k];
+                if (slot >= 0) sm[slot] = 1;
+            }
+        }
+        if (!pasted) {
+            mp = src_masks + ((long long)b * HW + pix) * T;
+            for (int w = 0; w < T; w += V) {
+                if (!((plan.own >> w) & lanes_of_word)) continue;
+                const uint32_t word = aug_load<V>(mp + w);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const int slot = s_slot[w + k];
+                    if (((plan.own >> (w + k)) & 1u) && slot >= 0 && ((word >> (8 * k)) & 0xffu) != 0) sm[slot] = 1;
+                }
+            }
+        }
+        const float* ip = src_images + ((long long)(pasted ? plan.d : b) * HW + pix) * 3;
+        s_img[tid * 3] = ip[0]; s_img[tid * 3 + 1] = ip[1]; s_img[tid * 3 + 2] = ip[2];
+    }
+    __syncthreads();
+    aug_write_runs(s_img, s_msk, images, masks, b, HW, pix0, nv, T, words_ok, tid);
+}
+
+// [p, p + n) and [q, q + m) share a byte
+static bool cp_overlap(const void* p, size_t n, const void* q, size_t m)
+{
+    const uintptr_t a = (uintptr_t)p, c = (uintptr_t)q;
+    return p && q && a < c + m && c < a + n;
+}
+
 extern "C" {
 
 size_t myolo_augment_batch_ws_bytes(int B, int T)
@@ -507,6 +725,68 @@ int myolo_mosaic_batch(const uint8_t* src_images, const uint8_t* src_masks, cons
     else if (V == 2) MOS_LAUNCH(2);
     else MOS_LAUNCH(1);
 #undef MOS_LAUNCH
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+size_t myolo_copy_paste_batch_ws_bytes(int B, int T)
+{
+    if (B <= 0 || T <= 0) return 0;
+    return (size_t)B * CP_SIDES * T * (AUG_STAT_INTS + 1) * sizeof(int);
+}
+
+int myolo_copy_paste_batch(const float* src_images, const uint8_t* src_masks, const int32_t* src_class_ids, const int32_t* donor,
+                           const int32_t* select, const double* anchors, float* images, uint8_t* gt_masks, int32_t* gt_boxes,
+                           int32_t* gt_class_ids, float* y_true, float* true_boxes, int32_t* dropped, int B, int H, int W, int T, int G, int A, int C,
+                           void* ws, size_t ws_bytes, void* stream)
+{
+    MYOLO_REQUIRE(src_images && src_masks && src_class_ids && donor && select && images && gt_masks && gt_boxes && gt_class_ids && dropped,
+                  "copy_paste_batch: null pointer");
+    MYOLO_REQUIRE((y_true != nullptr) == (true_boxes != nullptr), "copy_paste_batch: y_true and true_boxes are given together or not at all");
+    MYOLO_REQUIRE(!y_true || anchors, "copy_paste_batch: targets need the anchors");
+    MYOLO_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31) - AUG_THREADS * AUG_SPT, "copy_paste_batch: bad sizes (B=%d, H=%d, W=%d)", B, H, W);
+    MYOLO_REQUIRE(T > 0 && T <= AUG_MAXT, "copy_paste_batch: need 1 <= T <= %d (got %d)", AUG_MAXT, T);
+    MYOLO_REQUIRE(!y_true || (G > 0 && A > 0 && C > 0), "copy_paste_batch: bad target sizes (G=%d, A=%d, C=%d)", G, A, C);
+    const long long HW = (long long)H * W;
+    {   // a donor is read in its state before the paste, while other images of the batch are being written: no output may lie over an input
+        const void* in[5] = {src_images, src_masks, src_class_ids, donor, select};
+        const size_t in_bytes[5] = {(size_t)B * HW * 3 * sizeof(float), (size_t)B * HW * T, (size_t)B * T * sizeof(int32_t), (size_t)B * sizeof(int32_t),
+                                    (size_t)B * sizeof(int32_t)};
+        const void* out[7] = {images, gt_masks, gt_boxes, gt_class_ids, y_true, true_boxes, dropped};
+        const size_t out_bytes[7] = {in_bytes[0], in_bytes[1], (size_t)B * T * 4 * sizeof(int32_t), in_bytes[2],
+                                     y_true ? (size_t)B * G * G * A * (5 + C) * sizeof(float) : 0, (size_t)B * T * 4 * sizeof(float), in_bytes[3]};
+        for (int i = 0; i < 5; ++i)
+            for (int o = 0; o < 7; ++o)
+                MYOLO_REQUIRE(!cp_overlap(in[i], in_bytes[i], out[o], out_bytes[o]), "copy_paste_batch: output %d lies over input %d", o, i);
+    }
+    MYOLO_REQUIRE(ws && ws_bytes >= myolo_copy_paste_batch_ws_bytes(B, T), "copy_paste_batch: workspace too small (%zu bytes, need %zu)", ws_bytes,
+                  myolo_copy_paste_batch_ws_bytes(B, T));
+    const size_t cands = (size_t)B * CP_SIDES * T;
+    int* stats = (int*)ws;
+    int* slotmap = stats + cands * AUG_STAT_INTS;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipMemsetAsync(stats, 0, cands * AUG_STAT_INTS * sizeof(int), s);
+    (void)hipMemsetAsync(gt_boxes, 0, (size_t)B * T * 4 * sizeof(int32_t), s);
+    (void)hipMemsetAsync(gt_class_ids, 0, (size_t)B * T * sizeof(int32_t), s);
+    if (y_true) {
+        (void)hipMemsetAsync(y_true, 0, (size_t)B * G * G * A * (5 + C) * sizeof(float), s);
+        (void)hipMemsetAsync(true_boxes, 0, (size_t)B * T * 4 * sizeof(float), s);
+    }
+    const dim3 grid((unsigned)((HW + AUG_THREADS - 1) / AUG_THREADS), B), grid1((unsigned)((HW + AUG_THREADS * AUG_SPT - 1) / (AUG_THREADS * AUG_SPT)), B);
+    const int V = (T % 4 == 0 && ((uintptr_t)src_masks & 3) == 0) ? 4 : (T % 2 == 0 && ((uintptr_t)src_masks & 1) == 0) ? 2 : 1;
+    const int words_ok = (((uintptr_t)gt_masks & 3) == 0 && ((HW * T) & 3) == 0) ? 1 : 0;
+#define CP_LAUNCH(V_)                                                                                                                        \
+    do {                                                                                                                                     \
+        hipLaunchKernelGGL(copy_paste_stats_kernel<V_>, grid1, dim3(AUG_THREADS), 0, s, src_masks, src_class_ids, donor, select, stats, B, H, W, T); \
+        hipLaunchKernelGGL(copy_paste_encode_kernel, dim3(B), dim3(64), 0, s, src_class_ids, donor, select, (const int*)stats, slotmap,       \
+                           gt_class_ids, gt_boxes, y_true, true_boxes, dropped, anchors, B, H, W, T, G, A, C);                               \
+        hipLaunchKernelGGL(copy_paste_render_kernel<V_>, grid, dim3(AUG_THREADS), 0, s, src_images, src_masks, src_class_ids, donor, select,  \
+                           (const int*)slotmap, images, gt_masks, B, H, W, T, words_ok);                                                     \
+    } while (0)
+    if (V == 4) CP_LAUNCH(4);
+    else if (V == 2) CP_LAUNCH(2);
+    else CP_LAUNCH(1);
+#undef CP_LAUNCH
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

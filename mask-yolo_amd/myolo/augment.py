@@ -9,6 +9,10 @@ in DESIGN.md ("On-device augmentation") and restated in numpy by tests/augment_r
 
 Mosaic (MaskYOLO.train(mosaic=Mosaic(...))) composes every sample from four images of its batch: the host plans three small tables per batch
 (Mosaic.plan, Mosaic.compose) and the same augmenter runs myolo_mosaic_batch on them -- DESIGN.md ("Mosaic"), tests/mosaic_ref.py.
+
+Copy-paste (MaskYOLO.train(copy_paste=CopyPaste(...))) pastes instances of one augmented sample of the batch into another: the host plans two
+small tables per batch (CopyPaste.plan) and the augmenter runs myolo_copy_paste_batch behind either entry -- DESIGN.md ("Copy-paste"),
+tests/copy_paste_ref.py.
 """
 import math
 
@@ -207,6 +211,76 @@ def check_mosaic_tables(quad_src, centre, B, H, W):
         raise ValueError("mosaic tables: a centre lies in [0, %d] x [0, %d]" % (W, H))
 
 
+class CopyPaste(object):
+    """What MaskYOLO.train(copy_paste=...) takes: a sample receives instances of another sample of its batch -- their pixels replace its own, their
+    masks occlude its instances -- after both have been augmented ("Copy-paste").
+
+    p          probability that a sample receives a paste
+    instances  probability that each instance slot of the donor is selected
+    seed       plan() is a pure function of (seed, epoch, image ids, eligible, T)"""
+
+    DRAWS = 34           # per sample: pasted?, the donor, one per instance slot (32 at the most)
+
+    def __init__(self, p=0.5, instances=0.5, seed=0):
+        p, instances = float(p), float(instances)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p is a probability in [0, 1], got %r" % (p,))
+        if not 0.0 <= instances <= 1.0:
+            raise ValueError("instances is a probability in [0, 1], got %r" % (instances,))
+        self.p, self.instances = p, instances
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError("seed must be in [0, 2**32), got %r" % (seed,))
+        self.seed = seed
+
+    def plan(self, epoch, image_ids, T, eligible=None):
+        """-> (donor int32 [B], select int32 [B]) for a batch whose position b holds dataset image image_ids[b] in T instance slots.
+        donor[b]: the batch position whose instances b receives; bit t of select[b]: the donor's slot t is selected (a bit pattern: bit 31 is the
+        sign bit when T = 32).  The slots are those of the donor AFTER the first stage -- the host cannot know which survive the warp -- and the
+        device ignores selected slots that are empty.  eligible: the batch positions that may receive and donate, in batch order (default: all).
+        Position b always takes the same DRAWS draws in the same order from RandomState([seed, epoch, image_ids[b], 2]) -- the fourth element keeps
+        the stream apart from Augmentation's and Mosaic's: u0 < p turns the paste on, u1 picks the donor others[floor(u1 * len(others))], others =
+        eligible without b, and bit t < T is set iff u[2+t] < instances.  A sample that is not eligible, did not draw u0 < p or has nobody else to
+        take from gets donor[b] = b, select[b] = 0."""
+        B, T = len(image_ids), int(T)
+        if not 1 <= T <= 32:
+            raise ValueError("T is the number of instance slots, 1..32, got %r" % (T,))
+        eligible = list(range(B)) if eligible is None else [int(e) for e in eligible]
+        if any(not 0 <= e < B for e in eligible):
+            raise ValueError("eligible holds batch positions in [0, %d), got %r" % (B, eligible))
+        donor = np.arange(B, dtype=np.int32)
+        select = np.zeros(B, np.uint32)
+        rs = np.random.RandomState(0)          # re-seeded per sample, as in Mosaic.plan
+        for b in range(B):
+            rs.seed([self.seed, int(epoch), int(image_ids[b]), 2])
+            u = rs.random_sample(self.DRAWS)
+            others = [e for e in eligible if e != b]
+            if b not in eligible or not u[0] < self.p or not others:
+                continue
+            donor[b] = others[min(int(u[1] * len(others)), len(others) - 1)]
+            select[b] = sum(1 << t for t in range(T) if u[2 + t] < self.instances)
+        return donor, select.view(np.int32)
+
+    def __repr__(self):
+        return "CopyPaste(p=%r, instances=%r, seed=%r)" % (self.p, self.instances, self.seed)
+
+
+def check_paste_tables(donor, select, B, T):
+    """myolo_copy_paste_batch does not read its tables on the host, so they are checked here, on the host arrays, before they are uploaded: donors in
+    [0, B), no selected slot at or above T."""
+    donor, select = np.asarray(donor), np.asarray(select)
+    if donor.shape != (B,) or select.shape != (B,):
+        raise ValueError("copy-paste tables: expected donor [%d] and select [%d], got %s and %s" % (B, B, donor.shape, select.shape))
+    if donor.dtype.kind not in "iu" or select.dtype.kind not in "iu":
+        raise ValueError("copy-paste tables: integer arrays, got %s and %s" % (donor.dtype, select.dtype))
+    if ((donor < 0) | (donor >= B)).any():
+        raise ValueError("copy-paste tables: donor holds batch positions in [0, %d)" % B)
+    if select.dtype.itemsize > 4 and ((select < -(1 << 31)) | (select >= (1 << 32))).any():
+        raise ValueError("copy-paste tables: select holds 32-bit patterns")
+    if (((select.astype(np.int64) & 0xffffffff) >> T) != 0).any():
+        raise ValueError("copy-paste tables: select names a slot at or above T = %d" % T)
+
+
 class DeviceAugmenter(object):
     """Runs myolo_augment_batch: raw bytes, un-augmented instance masks and class ids, one parameter row per image -> the device batch dict
     Net.forward_backward consumes.  T = cfg.TRUE_BOX_BUFFER (= cfg.MAX_GT_INSTANCES) slots per image; a class id of 0 marks an empty slot."""
@@ -232,7 +306,7 @@ class DeviceAugmenter(object):
             raise ValueError("DeviceAugmenter: expected shape %s, got %s" % (tuple(shape), tuple(a.shape)))
         return a.to(self.dev).contiguous()
 
-    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None, mosaic=None):
+    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None, mosaic=None, copy_paste=None):
         """raw_images [B,H,W,3] uint8, gt_masks [B,H,W,T] uint8 / bool 0-1, gt_ids [B,T] int32 (0 = empty slot), params [B,8] float64 --
         numpy arrays (uploaded here) or device tensors.  -> dict(images, true_boxes, y_true, gt_ids, gt_boxes, gt_masks), the first three
         with yolo=True.  stream / consumer: as ShapesProducer.batch -- produce on `stream`, the dict carries the event `_ready` and its
@@ -240,12 +314,15 @@ class DeviceAugmenter(object):
         mosaic = (quad_src int32 [B,4], quad_rows float64 [B,4,8], centre int32 [B,2]) (Mosaic.plan / Mosaic.compose): myolo_mosaic_batch instead,
         which reads quad_rows in place of params; the dict gains "mosaic_dropped" int32 [B], the survivors beyond T that were discarded.  Tables
         given as numpy arrays are checked here (check_mosaic_tables); device tensors must have been checked before their upload, as
-        MaskYOLO.train() does."""
+        MaskYOLO.train() does.
+        copy_paste = (donor int32 [B], select int32 [B]) (CopyPaste.plan): myolo_copy_paste_batch runs behind either entry on the same stream, on
+        that entry's images, masks and class ids (its targets are not encoded), and its outputs are the dict's, which gains "paste_dropped" int32
+        [B], the selected instances that found no free slot.  Numpy tables are checked here (check_paste_tables); device tensors as above."""
         import torch
         from . import _ext as X
         if stream is not None:
             with torch.cuda.stream(stream):
-                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo, mosaic=mosaic)
+                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo, mosaic=mosaic, copy_paste=copy_paste)
                 ev = torch.cuda.Event()
                 ev.record(stream)
             if consumer is not None:
@@ -266,12 +343,16 @@ class DeviceAugmenter(object):
             raise ValueError("DeviceAugmenter needs uint8 images, got %s" % raw_images.dtype)
         if mosaic is not None and not (isinstance(mosaic[0], torch.Tensor) and isinstance(mosaic[2], torch.Tensor)):
             check_mosaic_tables(mosaic[0], mosaic[2], B, H, W)
+        if copy_paste is not None and not (isinstance(copy_paste[0], torch.Tensor) and isinstance(copy_paste[1], torch.Tensor)):
+            check_paste_tables(copy_paste[0], copy_paste[1], B, T)
         src = (self._dev(raw_images, torch.uint8, (B, H, W, 3)), self._dev(gt_masks, torch.uint8, (B, H, W, T)),
                self._dev(gt_ids, torch.int32, (B, T)), self._dev(params, torch.float64, (B, 8)))
         if mosaic is not None:
             src += (self._dev(mosaic[0], torch.int32, (B, 4)), self._dev(mosaic[1], torch.float64, (B, 4, 8)),
                     self._dev(mosaic[2], torch.int32, (B, 2)))
         need = X.augment_ws_bytes(B, T) if mosaic is None else X.mosaic_ws_bytes(B, T)
+        if copy_paste is not None:
+            need = max(need, X.copy_paste_ws_bytes(B, T))      # (one workspace: the second stage runs behind the first on the same stream)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.dev)
         d = dict(images=torch.empty(B, H, W, 3, device=self.dev),
@@ -281,6 +362,11 @@ class DeviceAugmenter(object):
                  gt_boxes=torch.empty(B, T, 4, dtype=torch.int32, device=self.dev),
                  gt_masks=torch.empty(B, H, W, T, dtype=torch.uint8, device=self.dev))
         outs = (X.ptr(d["images"]), X.ptr(d["gt_masks"]), X.ptr(d["gt_boxes"]), X.ptr(d["gt_ids"]), X.ptr(d["y_true"]), X.ptr(d["true_boxes"]))
+        if copy_paste is not None:
+            # the first stage writes four intermediate arrays and encodes no target; the second stage writes the dict's six
+            final = outs
+            mid = (torch.empty_like(d["images"]), torch.empty_like(d["gt_masks"]), torch.empty_like(d["gt_boxes"]), torch.empty_like(d["gt_ids"]))
+            outs = tuple(X.ptr(t) for t in mid) + (None, None)
         if mosaic is None:
             X.call("myolo_augment_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[3]), self.cval, X.ptr(self.anchors), *outs,
                    B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
@@ -288,10 +374,18 @@ class DeviceAugmenter(object):
             dropped = torch.empty(B, dtype=torch.int32, device=self.dev)
             X.call("myolo_mosaic_batch", X.ptr(src[0]), X.ptr(src[1]), X.ptr(src[2]), X.ptr(src[4]), X.ptr(src[5]), X.ptr(src[6]), self.cval,
                    X.ptr(self.anchors), *outs, X.ptr(dropped), B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
+        if copy_paste is not None:
+            tables = (self._dev(copy_paste[0], torch.int32, (B,)), self._dev(copy_paste[1], torch.int32, (B,)))
+            paste_dropped = torch.empty(B, dtype=torch.int32, device=self.dev)
+            X.call("myolo_copy_paste_batch", X.ptr(mid[0]), X.ptr(mid[1]), X.ptr(mid[3]), X.ptr(tables[0]), X.ptr(tables[1]), X.ptr(self.anchors),
+                   *final, X.ptr(paste_dropped), B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
         if yolo:
             # the step reads three arrays; the other three stay on the dict's side until the kernels that wrote them have run
             d = dict(images=d["images"], true_boxes=d["true_boxes"], y_true=d["y_true"], _gt=(d["gt_ids"], d["gt_boxes"], d["gt_masks"]))
         if mosaic is not None:
             d["mosaic_dropped"] = dropped
+        if copy_paste is not None:
+            d["paste_dropped"] = paste_dropped
+            d["_paste_src"] = mid + tables      # the first stage's images, masks, boxes and ids, then donor and select: read asynchronously too
         d["_src"] = src            # the kernels read them asynchronously
         return d

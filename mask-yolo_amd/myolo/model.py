@@ -385,7 +385,7 @@ class MaskYOLO(object):
 
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers,
               augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0,
-              device_polygons=True, mosaic=None):
+              device_polygons=True, mosaic=None, *, copy_paste=None):
         """model.py:943-1060.  Returns the list of per-epoch mean training losses; ``self.history`` holds
         {"loss": [...], "val_loss": [...]} like the Keras History the reference's fit_generator produces.
         shuffle_seed: the generators' one-off shuffle (myolo_utils.py:711-712) draws from RandomState(shuffle_seed) -- the
@@ -401,7 +401,10 @@ class MaskYOLO(object):
         mosaic: a myolo.augment.Mosaic -- every training sample it picks is cut into four tiles that show the sample and three others of the same
         batch, on the device, on every route, with or without `augmentation` (without: identity rows; on the host route the
         device augmenter then runs all the same).  Samples whose source is in no_augmentation_sources are neither mosaicked nor used as partners;
-        validation batches never are."""
+        validation batches never are.
+        copy_paste (keyword only): a myolo.augment.CopyPaste -- every training sample it picks receives instances of another sample of its batch,
+        pasted on the device after both have been augmented / mosaicked, on every route, with or without `augmentation`
+        and `mosaic`.  Samples whose source is in no_augmentation_sources neither receive nor donate; validation batches are never pasted."""
         layer_regex = {"all": ".*"}
         if layers in layer_regex:
             layers = layer_regex[layers]
@@ -415,7 +418,11 @@ class MaskYOLO(object):
             from .augment import Mosaic
             if not isinstance(mosaic, Mosaic):
                 raise TypeError("mosaic must be a myolo.augment.Mosaic, got %r" % type(mosaic).__name__)
-        device_augmenter = augmentation is not None or mosaic is not None
+        if copy_paste is not None:
+            from .augment import CopyPaste
+            if not isinstance(copy_paste, CopyPaste):
+                raise TypeError("copy_paste must be a myolo.augment.CopyPaste, got %r" % type(copy_paste).__name__)
+        device_augmenter = augmentation is not None or mosaic is not None or copy_paste is not None
 
         def collect(ds, tag=False):
             ids = list(ds.image_ids)
@@ -466,9 +473,9 @@ class MaskYOLO(object):
         make_item = lambda it: make(it[1])             # noqa: E731
         if polygon_route or segment_route:
             make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic,
-                                              counter="polygon_batches" if polygon_route else "segment_batches")
+                                              counter="polygon_batches" if polygon_route else "segment_batches", copy_paste=copy_paste)
         elif device_augmenter:
-            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic)
+            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic, copy_paste=copy_paste)
 
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
         # are encoded and uploaded while epoch e finishes
@@ -560,7 +567,30 @@ class MaskYOLO(object):
             return arrays
         return both
 
-    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None):
+    def paste_tables(self, copy_paste, no_augmentation_sources, dataset, epoch, image_ids):
+        """-> (donor [n], select [n]): the plan train() draws for a batch that holds these dataset image ids, in this order, in this epoch
+        (CopyPaste.plan).  A sample whose source is in no_augmentation_sources neither receives nor donates."""
+        skip = set(no_augmentation_sources or [])
+        eligible = [k for k, i in enumerate(image_ids) if not (skip and dataset.image_info[i]['source'] in skip)]
+        return copy_paste.plan(epoch, image_ids, self.config.TRUE_BOX_BUFFER, eligible)
+
+    def _with_paste(self, copy_paste, no_augmentation_sources, dataset, gen, epoch, i, fill):
+        """fill(arrays) -> a fill for the same batch with the two copy-paste tables staged last (Net._paste_spec): the plan of the batch's image
+        ids, checked before the upload is queued.  copy_paste=None: `fill` itself."""
+        if copy_paste is None:
+            return fill
+        from .augment import check_paste_tables
+        lo, hi = gen.batch_bounds(i)
+        donor, select = self.paste_tables(copy_paste, no_augmentation_sources, dataset, epoch, [inst[4] for inst in gen.all_info[lo:hi]])
+        check_paste_tables(donor, select, hi - lo, self.config.TRUE_BOX_BUFFER)
+
+        def both(arrays):
+            fill(arrays[:-2])
+            arrays[-2][...], arrays[-1][...] = donor, select
+            return arrays
+        return both
+
+    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, copy_paste=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread: raw bytes, un-augmented masks, class ids and parameter rows go up through the
         engine's staging ring, and the device augmenter runs behind the copies on the copy stream, under the previous step."""
         from .augment import DeviceAugmenter
@@ -573,7 +603,8 @@ class MaskYOLO(object):
             lo, hi = gen.batch_bounds(i)
             row_of = self._row_of(augmentation, no_augmentation_sources, dataset, epoch)
             fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, lambda arrays: gen.fill_raw(i, arrays, row_of))
-            return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None)
+            fill = self._with_paste(copy_paste, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None, copy_paste=copy_paste is not None)
         return make
 
     def _collect_segments(self, dataset, max_samples=None, first=None, load="load_segments"):
@@ -621,7 +652,7 @@ class MaskYOLO(object):
             info.append([image, class_ids, list(segs), (rows.astype(np.int32), cols.astype(np.int32)), int(i), int(h)])
         return info
 
-    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, counter="segment_batches"):
+    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, counter="segment_batches", copy_paste=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread on the device route: image bytes, segments, class ids, index tables and
         parameter rows go up through the engine's staging ring; Net.stage_segments decodes the segments behind the copies on the copy stream, then
         the device augmenter runs.  counter: the key of host_times that counts the batches ("polygon_batches" for a dataset with load_polygons)."""
@@ -635,8 +666,9 @@ class MaskYOLO(object):
             lo, hi = gen.batch_bounds(i)
             fill, n_verts, n_parts, n_bounds = gen.segment_batch(i, self._row_of(augmentation, no_augmentation_sources, dataset, epoch))
             fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            fill = self._with_paste(copy_paste, no_augmentation_sources, dataset, gen, epoch, i, fill)
             db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds,
-                                         mosaic=mosaic is not None)
+                                         mosaic=mosaic is not None, copy_paste=copy_paste is not None)
             self.host_times[counter] += 1
             return db
         return make
