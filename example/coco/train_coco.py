@@ -6,10 +6,11 @@ written as a COCO results file, category ids mapped back through the dataset.
 
   python example/coco/train_coco.py TRAIN_JSON TRAIN_IMAGES [--val-json PATH --val-images DIR] [--categories 1,3,17] [--keep-crowd]
                                     [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--results PATH]
-                                    [--fit-anchors K] [--mosaic P] [--copy-paste P]
+                                    [--fit-anchors K] [--mosaic P] [--copy-paste P] [--max-detections N]
 
 --fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
-Config's, which were fitted to UECFOOD100 at 224 x 224.
+Config's, which were fitted to UECFOOD100 at 224 x 224.  --max-detections N scores and writes up to N detections per validation image (1 .. 128,
+selected on the device: DESIGN section 23) instead of ten -- on pictures with more than ten objects recall, and every AP, stops at 10 / n without it.
 """
 import argparse
 import json
@@ -46,7 +47,11 @@ def main():
     ap.add_argument("--host-masks", action="store_true", help="decode the segmentations on the host (load_mask) for the training batches")
     ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: Config's anchors)")
     ap.add_argument("--results", default=None, help="where the validation detections go as a COCO results file (default: LOGS/coco_results.json)")
+    ap.add_argument("--max-detections", metavar="N", type=int, default=None,
+                    help="evaluate and write up to N detections per validation image (1 .. 128), selected on the device (default: ten, on the host)")
     a = ap.parse_args()
+    if a.max_detections is not None and not 1 <= a.max_detections <= 128:
+        ap.error("--max-detections must be in 1 .. 128")
 
     cats = [int(c) for c in a.categories.split(",")] if a.categories else None
     crowd = "keep" if a.keep_crowd else "skip"
@@ -74,13 +79,13 @@ def main():
     if val is not None:
         infer = MaskYOLO(mode="inference", config=config)
         infer.load_weights(weights)
-        r = infer.evaluate(val)
+        r = infer.evaluate(val, max_detections=a.max_detections)
         print("validation: mask AP50 %.4f, mask AP %.4f, box AP50 %.4f, box AP %.4f over %d images (%d instances, %d detections)" %
               (r["mask_ap50"], r["mask_ap"], r["box_ap50"], r["box_ap"], r["n_images"], r["n_gt"], r["n_det"]))
         out, ids = [], list(val.image_ids)
         for lo in range(0, len(ids), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
             chunk = ids[lo:lo + 8 * a.batch]
-            results = infer.detect_many([val.load_image(i) for i in chunk], mask_format="rle")
+            results = infer.detect_many([val.load_image(i) for i in chunk], mask_format="rle", max_detections=a.max_detections)
             out += rle.coco_results(results, [val.image_info[i]["id"] for i in chunk], category_ids=val.category_ids)
         path = a.results or os.path.join(a.logs, "coco_results.json")
         with open(path, "w") as f:

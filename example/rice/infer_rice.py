@@ -5,10 +5,11 @@ in each photograph's own frame.  With --coco-json the masks 
 DESIGN section 15: no dense mask is written or downloaded) and every detection goes into one COCO results file.  With --render-dir every
 photograph's overlay -- masks, outlines and boxes drawn over it on the device -- is written there as <name>.png.  With
 --via-json the masks are asked for as polygons (traced on the device) and written as a VIA 2.x annotation file: load it in the
-VGG Image Annotator beside the photographs to correct the predictions, or read it back with myolo.via.load_via.
+VGG Image Annotator beside the photographs to correct the predictions, or read it back with myolo.via.load_via.  With --max-detections N up to
+N instances (1 .. 128) are reported per photograph instead of ten, selected on the device; an overlay holds at most 16.
 
   python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame] [--coco-json PATH]
-                                    [--render-dir DIR] [--via-json PATH] [--polygon-tolerance T]
+                                    [--render-dir DIR] [--via-json PATH] [--polygon-tolerance T] [--max-detections N]
 """
 import argparse
 import glob
@@ -43,7 +44,13 @@ def main():
     ap.add_argument("--via-json", metavar="PATH", help="write the detections as a VIA 2.x annotation file (one polygon region per outer outline)")
     ap.add_argument("--polygon-tolerance", metavar="T", type=float, default=0.0,
                     help="with --via-json: simplify every outline (Douglas-Peucker), dropping vertices within T pixels of it; 0 keeps every corner")
+    ap.add_argument("--max-detections", metavar="N", type=int, default=None,
+                    help="report up to N instances per photograph (1 .. 128), selected on the device; default: the ten of the host selection")
     a = ap.parse_args()
+    if a.max_detections is not None and not 1 <= a.max_detections <= 128:
+        ap.error("--max-detections must be in 1 .. 128")
+    if a.render_dir and a.max_detections is not None and a.max_detections > 16:
+        ap.error("--render-dir draws at most 16 instances per photograph: it does not go with --max-detections above 16")
     if a.render_dir and a.network_frame:
         ap.error("--render-dir draws on the photograph given: it does not go with --network-frame")
     if a.via_json and a.network_frame:
@@ -63,7 +70,7 @@ def main():
         chunk = paths[lo:lo + 8 * a.batch]
         photos = [load_rgb(p) for p in chunk]
         results = model.detect_many(photos, cs_threshold=a.threshold, mask_frame="network" if a.network_frame else "image",
-                                    mask_format=mask_format, render=bool(a.render_dir))
+                                    mask_format=mask_format, render=bool(a.render_dir), max_detections=a.max_detections)
         if a.via_json:
             annotations.update(via.via_annotations(results, [os.path.basename(p) for p in chunk], class_names=["BG", "rice"],
                                                    tolerance=a.polygon_tolerance))

@@ -491,6 +491,25 @@ int    myolo_anchor_kmeans(const int32_t* wh /*[n,2] device*/, int64_t n, const 
                            int32_t* iterations /*[runs]*/, int32_t* converged /*[runs]*/, double* mean_iou /*[runs]*/,
                            int32_t* assign /*[runs,n] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detect()'s selection on the device (myolo/detect.py: select with its 10 replaced by K; csrc/select_kernels.hip; contract: DESIGN.md section
+ * 23).  Declared here rather than in the operator API (myolo_hip.h, held to 70 entries).  det [B,R,6] float32 as the inference graph returns it
+ * (x1, y1, x2, y2 normalised, score, class id); one workgroup per image, every decision the host's, bit for bit:
+ *   1. a row is live when (x2 - x1) * (y2 - y1) > 0 in binary32 (two subtractions and a product, not contracted; both extents negative is live);
+ *   2. the live rows in descending score, ties by the HIGHER row first (np.argsort(scores, kind="stable")[::-1]); the first K of them;
+ *   3. of those the rows with (double)score >= cs_threshold, in order: the list L;
+ *   4. entry j of L is dropped when ANY earlier entry i of L, dropped or not, has the same class, (int32)det[5] by truncation, and
+ *      IoU >= nms_threshold: myolo_utils.bbox_iou_2 in binary64 -- corners (double)x * shape0 and (double)y * shape1 (image_shape[0] and [1], in
+ *      that order), _interval_overlap's branches as written, inter / ((w1 * h1 + w2 * h2) - inter); a zero denominator (the host raises) does not
+ *      suppress;
+ *   5. the survivors, in order.
+ * sel [B,K] int32 = their rows of det[b], -1 in the empty slots; picked [B,K,6] = det[b, sel[b,k]] bit for bit, zeros in the empty slots;
+ * count [B] = survivors per image.  An image b >= n_live only gets its -1s, zeros and count 0.  Scores are finite by construction (a sigmoid
+ * product): a non-finite score is outside the contract.  Nothing is read back: no synchronisation.
+ * MYOLO_EINVAL (message "select_detections: ...", nothing launched) for a null pointer, B < 1, K outside 1 .. 128, R outside 1 .. 4096 and
+ * n_live outside 0 .. B. */
+int myolo_select_detections(const float* det /*[B,R,6]*/, int B, int R, int n_live, int K, double cs_threshold, double nms_threshold,
+                            int shape0, int shape1, int32_t* sel /*[B,K]*/, float* picked /*[B,K,6]*/, int32_t* count /*[B]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

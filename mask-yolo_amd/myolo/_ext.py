@@ -141,6 +141,7 @@ SIGS = {
     "myolo_contour_masks": [P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
     "myolo_render_instances": [P, P, Z, P, P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, P, Z, P],
     "myolo_anchor_kmeans": [P, L, P, P, I, I, P, P, P, P, P, P, Z, P],
+    "myolo_select_detections": [P, I, I, I, I, D, D, I, I, P, P, P, P],
     "myolo_set_option": [ctypes.c_char_p, I],
     "myolo_get_option": [ctypes.c_char_p, P],
     "myolo_comm_unique_id": [P],

@@ -2,7 +2,8 @@
 ``myolo.detect`` -- the one detection pipeline under MaskYOLO.detect / detect_many / evaluate / evaluate_shapes_stream:
 uint8 images are staged to the device (Stager), run through the forward, up to SLOTS rows per image are selected on the host from the one
 detection download of a batch (Selection), and the selection is handed to a mask consumer: dense_masks, rle_masks, polygon_masks, overlap_counts,
-render.
+render.  With max_detections=K the same record is filled on the device instead, K <= MAX_SLOTS rows per image (Selection.from_device, DESIGN.md
+section 23); no consumer learns where a selection came from.
 """
 import numpy as np
 import torch
@@ -14,9 +15,29 @@ from .engine import packed_bytes
 SLOTS = 10            # detect() keeps at most the top 10 detections of an image
 
 
-def check_args(cfg, images, mask_frame, mask_format, render):
+MAX_SLOTS = 128       # ... or, with max_detections=K, at most K <= 128, selected on the device
+RENDER_SLOTS = 16     # the instances of an image myolo_render_instances draws in its one pass
+
+
+def check_max_detections(cfg, max_detections, render=False):
+    """the max_detections argument of detect / detect_many / evaluate / evaluate_shapes_stream: None (the host selection of SLOTS rows) or an int
+    in 1 .. MAX_SLOTS"""
+    if max_detections is None:
+        return
+    if isinstance(max_detections, (bool, np.bool_)) or not isinstance(max_detections, (int, np.integer)) or not 1 <= max_detections <= MAX_SLOTS:
+        raise ValueError("max_detections must be None or an int in 1 .. %d (got %r)" % (MAX_SLOTS, max_detections))
+    if bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False)):
+        raise ValueError("max_detections is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
+    if render and max_detections > RENDER_SLOTS:
+        raise ValueError("render=True draws at most %d instances per image: the overlay kernel blends, outlines and boxes all instances of an "
+                         "image in one pass and its layers cannot be split into blocks (got max_detections=%d); rendering more is out of scope"
+                         % (RENDER_SLOTS, max_detections))
+
+
+def check_args(cfg, images, mask_frame, mask_format, render, max_detections=None):
     """detect() / detect_many()'s argument checks, before anything is uploaded"""
     selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
+    check_max_detections(cfg, max_detections, render)
     if mask_frame not in ("image", "network"):
         raise ValueError("mask_frame must be 'image' or 'network' (got %r)" % (mask_frame,))
     if mask_format not in ("dense", "rle", "polygon"):
@@ -121,6 +142,24 @@ class Selection(object):
             self.sel[k, :len(nmb)] = keep[nmb]
             self.picked.append((boxes[nmb], class_ids[nmb], scores[nmb]))
 
+    @classmethod
+    def from_device(cls, sel, picked, n_live):
+        """the same record from Net.select_detections' (sel [B,K] int32, picked [B,K,6] float32): any K, nothing selected on the host"""
+        self = cls.__new__(cls)
+        self.n, self.sel, self.picked = int(n_live), sel, []
+        for k in range(self.n):
+            m = int((sel[k] >= 0).sum())                         # (the survivors fill the leading slots)
+            self.picked.append((picked[k, :m, :4].copy(), picked[k, :m, 5].astype(np.int32), picked[k, :m, 4].copy()))
+        return self
+
+    @classmethod
+    def of_batch(cls, net, det_d, n_live, cs_threshold, image_shape, max_detections=None):
+        """the selection of one batch's det_d [B,R,6] (device): max_detections None -- the host selection of SLOTS rows from the batch's one
+        detection download; an int -- K = max_detections slots filled on the device (Net.select_detections), det_d stays there"""
+        if max_detections is None:
+            return cls(det_d.cpu().numpy(), n_live, cs_threshold, image_shape)
+        return cls.from_device(*net.select_detections(det_d, n_live, max_detections, cs_threshold, image_shape), n_live=n_live)
+
     def rows(self, k):
         return self.sel[k, :len(self.picked[k][1])]
 
@@ -155,7 +194,7 @@ def dense_masks(stager, det_img, mask_img, rows, frame, feature=None):
         return np.empty((int(frame[0]), int(frame[1]), 0), dtype=bool)
     # (the few indices go up from a pinned buffer without blocking; the download of the pasted masks ends every image with a synchronisation, so
     # the buffer is free again by the next one)
-    pin = stager.pinned("rows", 1, (64,), torch.int64)[0][:len(rows)]
+    pin = stager.pinned("rows", 1, (MAX_SLOTS,), torch.int64)[0][:len(rows)]
     pin.copy_(torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)))
     idx = pin.to(det_img.device, non_blocking=True)
     det_s = det_img.index_select(0, idx).contiguous()
@@ -192,7 +231,8 @@ def polygon_masks(net, det_d, mask_d, selection, frames):
 def overlap_counts(stager, det_d, mask_d, selection, gt_d):
     """(inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4]) on the host: one Net.overlap_counts call against gt_d [B,H,W,T]"""
     # (the table goes up from a pinned buffer without blocking; free again by the next batch: the downloads here end with a synchronisation)
-    pin = stager.pinned("sel", 1, selection.sel.shape, torch.int32)[0]
+    # (kept flat: K differs between calls with and without max_detections)
+    pin = stager.pinned("sel", 1, (selection.sel.size,), torch.int32)[0][:selection.sel.size].view(selection.sel.shape)
     pin.numpy()[:] = selection.sel
     return [t.cpu().numpy() for t in stager.net.overlap_counts(det_d, mask_d, pin, gt_d)]
 

@@ -54,6 +54,45 @@ def packed_bytes(images, n_slots=None):
     return n * 24 + sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images)
 
 
+# ---- more than 16 slots per image: myolo_rle_masks, myolo_contour_masks and myolo_mask_overlap_counts take K <= 16, so a
+# wider sel goes through them in column blocks and the documented outputs are put together again by the pure functions below
+SEL_BLOCK = 16            # the slots per image of one call of those entry points
+SEL_MAX = 128             # the slots per image myolo_select_detections fills, and Net.rle_masks / contour_masks / overlap_counts take
+
+
+def sel_width(sel):
+    return int(sel.shape[1]) if len(getattr(sel, "shape", ())) == 2 else 0
+
+
+def sel_column_blocks(sel, width=SEL_BLOCK):
+    """sel [B,K] -> its column blocks [B,<=width], left to right, each contiguous"""
+    return [np.ascontiguousarray(sel[:, c:c + width]) for c in range(0, sel.shape[1], width)]
+
+
+def join_rle_blocks(blocks, B):
+    """[(run_off [B*k_j+1], bounds)] of the column blocks of one sel [B,K], K = sum k_j, as Net.rle_masks returns each -> (run_off [B*K+1] int32,
+    bounds uint32) of the whole: slot s = b*K + k, image b's slots the blocks' slots of image b side by side"""
+    widths = [(len(off) - 1) // B for off, _ in blocks]
+    lens = np.concatenate([np.diff(off.astype(np.int64)).reshape(B, w) for (off, _), w in zip(blocks, widths)], axis=1)
+    run_off = np.zeros(lens.size + 1, np.int32)
+    run_off[1:] = np.cumsum(lens.reshape(-1))
+    parts = [bounds[off[b * w]:off[(b + 1) * w]] for b in range(B) for (off, bounds), w in zip(blocks, widths)]
+    return run_off, np.concatenate(parts).astype(np.uint32, copy=False)
+
+
+def join_loop_blocks(blocks, B):
+    """[list of B*k_j loop lists] of the column blocks, as Net.contour_masks returns each -> the list of B*K, slot s = b*K + k"""
+    widths = [len(blk) // B for blk in blocks]
+    return [loops for b in range(B) for blk, w in zip(blocks, widths) for loops in blk[b * w:(b + 1) * w]]
+
+
+def join_overlap_blocks(blocks):
+    """[(inter [B,k_j,T], area_pred [B,k_j], area_gt [B,T], win [B,k_j,4])] of the column blocks, as Net.overlap_counts returns each (device
+    tensors; numpy arrays are taken too) -> the four of the whole; area_gt, the same in every block, is the first one's"""
+    cat = torch.cat if torch.is_tensor(blocks[0][0]) else np.concatenate
+    return (cat([blk[0] for blk in blocks], 1), cat([blk[1] for blk in blocks], 1), blocks[0][2], cat([blk[3] for blk in blocks], 1))
+
+
 def pack_images(images, out, n_slots=None):
     """Pack uint8 [h,w,3] images of mixed sizes into the byte array `out` the way myolo_resize_images_u8 reads them: out[:n_slots * 24] holds the
     descriptor, int64 [n_slots,3] = (byte offset of the image behind the descriptor, h, w), and the images follow back to back with no padding
@@ -507,6 +546,7 @@ class Net(object):
         self._contour_pin = None
         self._render_args = None          # render_instances: the pinned buffer of its arguments and the pinned, grow-only one the overlays come down into
         self._render_pin = None
+        self._select_pin = None           # select_detections: the pinned buffer [sel | picked] comes down into (grow-only)
         self._cap_stream = None           # graph capture never happens with the default stream current (see _capture_predict)
         self._fm_stream = None            # inference: feature_map's conv beside the YOLO head (trunk_fwd)
         self.infer_fork_feature_map = False   # opt-in, and then only forwards that run alone: measured +0.0-0.5 % alone, -9 % with several batches in flight (forked graphs, 1150 -> 1055 img/s at Rice-416); and the extra stream it brings into a process moved the lanes' hardware-queue mapping in the full bench run (three lanes 1152 -> 1086)
@@ -2739,6 +2779,36 @@ class Net(object):
             raise ValueError("%s: %s expected" % (who, expected))
         return sel_t.contiguous(), (B, R, K) + tuple(int(v) for v in mask_d.shape[2:])
 
+    def _sel_blocks(self, who, expected, det_d, mask_d, sel):
+        """rle_masks / contour_masks / overlap_counts with more than SEL_BLOCK slots per image: -> (B, the column blocks of sel) for one call of
+        the existing entry point each (sel_column_blocks); ValueError, in the name `who`, for what _selected_sizes refuses and for K > SEL_MAX"""
+        sel_t, sizes = self._selected_sizes(who, expected, det_d, mask_d, sel)
+        if sizes[2] > SEL_MAX:
+            raise ValueError("%s: at most %d slots per image (got K=%d)" % (who, SEL_MAX, sizes[2]))
+        return sizes[0], sel_column_blocks(sel_t.numpy())
+
+    def select_detections(self, det_d, n_live, K, cs_threshold, image_shape, nms_threshold=0.7):
+        """detect()'s selection of a batch on the device (myolo_select_detections, include/myolo_hip_internal.h; the contract: DESIGN.md section
+        23): det_d [B,R,6] float32 as predict returns it, the first n_live images of it live, K in 1 .. 128 slots per image, image_shape =
+        config.IMAGE_SHAPE.  -> (sel [B,K] int32, picked [B,K,6] float32) numpy arrays (copies): sel[b] = the rows of det_d[b] image b reports, in
+        reporting order, -1 in the empty slots and for b >= n_live; picked[b,k] = det_d[b, sel[b,k]], zeros in the empty slots.
+        One launch and one download of B*K*7 words into a pinned buffer the Net keeps; det_d itself stays on the device."""
+        if det_d.dtype != torch.float32 or det_d.dim() != 3 or int(det_d.shape[2]) != 6 or not det_d.is_cuda:
+            raise ValueError("select_detections: det [B,R,6] f32 on the device expected")
+        det_d = det_d.contiguous()
+        B, R, K = int(det_d.shape[0]), int(det_d.shape[1]), int(K)
+        n = max(B * K, 0)
+        buf = torch.empty(7 * n + B, dtype=torch.int32, device=self.dev)                       # [sel | picked | count]
+        X.call("myolo_select_detections", X.ptr(det_d), B, R, int(n_live), K, float(cs_threshold), float(nms_threshold), int(image_shape[0]),
+               int(image_shape[1]), buf.data_ptr(), buf.data_ptr() + 4 * n, buf.data_ptr() + 28 * n, X.stream())
+        if self._select_pin is None or self._select_pin.numel() < 7 * n:
+            self._select_pin = torch.empty(7 * n, dtype=torch.int32).pin_memory()
+        pin = self._select_pin[:7 * n]
+        pin.copy_(buf[:7 * n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        host = pin.numpy()
+        return host[:n].reshape(B, K).copy(), host[n:].view(np.float32).reshape(B, K, 6).copy()
+
     RENDER_BLEND, RENDER_OUTLINE, RENDER_BOX = 1, 2, 4         # the layers of myolo_render_instances' flags word
 
     def render_instances(self, images_d, desc, det_d, mask_d, sel, colors=None, alpha=0.5, box_alpha=0.7, show_mask=True, show_outline=True,
@@ -2807,9 +2877,13 @@ class Net(object):
         """Pixel overlaps of the pasted masks of selected detections with ground-truth planes, counted on the device
         (myolo_mask_overlap_counts, include/myolo_hip_internal.h): det_d [B,R,6], mask_d [B,R,mh,mw,C] as predict returns them,
         sel [B,K] int32 in HOST memory (a numpy array or a CPU tensor; a pinned tensor goes up without blocking) = rows of det_d per image,
-        -1 = empty slot, K <= 16; gt_masks [B,H,W,T] uint8 0 / 1 device tensor, T <= 32.
+        -1 = empty slot, K <= 128 (the entry takes 16: a wider sel goes through it in column blocks of 16, one call each, and the results are
+        concatenated); gt_masks [B,H,W,T] uint8 0 / 1 device tensor, T <= 32.
         -> device int32 tensors inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4] ([x1,y1,x2,y2) of the paste)."""
         expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, gt_masks [B,H,W,T] u8"
+        if sel_width(sel) > SEL_BLOCK:                # (more slots than the entry takes: one call per column block, DESIGN.md section 23)
+            _, blocks = self._sel_blocks("overlap_counts", expected, det_d, mask_d, sel)
+            return join_overlap_blocks([self.overlap_counts(det_d, mask_d, blk, gt_masks) for blk in blocks])
         sel_h, (B, R, K, mh, mw, C) = self._selected_sizes("overlap_counts", expected, det_d, mask_d,
                                                             sel if torch.is_tensor(sel) else np.asarray(sel, dtype=np.int32))
         if gt_masks.dtype != torch.uint8 or gt_masks.dim() != 4 or int(gt_masks.shape[0]) != B:
@@ -2831,13 +2905,17 @@ class Net(object):
     def rle_masks(self, det_d, mask_d, sel, frames):
         """The pasted masks of selected detections as run boundaries of COCO's run-length form, encoded on the device (myolo_rle_masks,
         include/myolo_hip_internal.h; the format: myolo/rle.py): det_d [B,R,6], mask_d [B,R,mh,mw,C] as predict returns them, sel [B,K] int32 in
-        HOST memory = rows of det_d per image, -1 = empty slot, K <= 16; frames [B,2] int32 in host memory = (h, w) of the frame image b's masks
+        HOST memory = rows of det_d per image, -1 = empty slot, K <= 128 (the entry takes 16: a wider sel goes through this method in column
+        blocks of 16 and join_rle_blocks puts the outputs together); frames [B,2] int32 in host memory = (h, w) of the frame image b's masks
         are pasted into.  -> (run_off [B*K+1] int32, bounds [run_off[-1]] uint32) numpy arrays: bounds[run_off[s]:run_off[s+1]] are the boundaries
         of slot s = b*K + k, and rle.counts_from_boundaries(those, h*w) its counts.
         One upload (sel and frames together) and two small downloads: the offsets, then bounds[:total].  The boundaries land in ONE device buffer
         per Net that only grows; when a batch holds more than it has room for, the entry has still written every offset, so the buffer is
         enlarged to the total and the call repeated."""
         expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32"
+        if sel_width(sel) > SEL_BLOCK:                # (more slots than the entry takes: one call per column block, DESIGN.md section 23)
+            B, blocks = self._sel_blocks("rle_masks", expected, det_d, mask_d, sel)
+            return join_rle_blocks([self.rle_masks(det_d, mask_d, blk, frames) for blk in blocks], B)
         sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("rle_masks", expected, det_d, mask_d, sel)
         sel_h = sel_t.numpy()
         frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)
@@ -2875,12 +2953,16 @@ class Net(object):
 
     def contour_masks(self, det_d, mask_d, sel, frames):
         """The pasted masks of selected detections as closed outlines, traced on the device (myolo_contour_masks, include/myolo_hip_internal.h;
-        the contract: myolo/contour.py): det_d, mask_d, sel [B,K] and frames [B,2] as rle_masks takes them.  -> a list of B*K lists, slot
+        the contract: myolo/contour.py): det_d, mask_d, sel [B,K] and frames [B,2] as rle_masks takes them (K > 16: column blocks of 16, put
+        together by join_loop_blocks).  -> a list of B*K lists, slot
         s = b*K + k: that mask's loops as int32 [n,2] (X, Y) arrays in lattice corner coordinates, contour.trace's order; an empty slot has none.
         One upload (sel and frames together) and three small downloads: the offsets, then verts[:total] and loop_id[:total].  The vertices land
         in ONE device buffer per Net that only grows, the workspace beside them sized from it; when a batch holds more vertices than there is
         room for, the entry has still written every offset, so the buffer is enlarged to the total and the call repeated."""
         expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32"
+        if sel_width(sel) > SEL_BLOCK:                # (more slots than the entry takes: one call per column block, DESIGN.md section 23)
+            B, blocks = self._sel_blocks("contour_masks", expected, det_d, mask_d, sel)
+            return join_loop_blocks([self.contour_masks(det_d, mask_d, blk, frames) for blk in blocks], B)
         sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("contour_masks", expected, det_d, mask_d, sel)
         sel_h = sel_t.numpy()
         frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)

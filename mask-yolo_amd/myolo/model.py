@@ -733,7 +733,7 @@ class MaskYOLO(object):
         return [im.shape if mask_frame == "image" else self.config.IMAGE_SHAPE for im in images]
 
     def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image",
-               mask_format="dense", render=False):
+               mask_format="dense", render=False, *, max_detections=None):
         """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ].  An image of another size than config.IMAGE_SHAPE
         is resized to it on the device (Net.resize_to_frame: myolo_utils.resize_image's result, bit for bit) and reported in
         the frame mask_frame names: "image" -- bboxes in pixels of the image given, full_masks [h,w,n] pasted at that size -- or "network" --
@@ -753,9 +753,14 @@ class MaskYOLO(object):
         render.instance_colors(len(class_ids)) -- drawn on the device from the uploaded bytes (Net.render_instances); with a
         save_path that is not None it is also written to save_path/InferMaskYOLO-0.png (the directory is created).
         ValueError with mask_frame="network" for an image of another size than IMAGE_SHAPE (the canvas is the image given) and with
-        config.DETECT_MASKS_FOR_SELECTED_ONLY.  Without render, save_path and display are ignored."""
+        config.DETECT_MASKS_FOR_SELECTED_ONLY.  Without render, save_path and display are ignored.
+        max_detections=K, an int in 1 .. 128 (keyword only): up to K instances per image instead of ten, selected on the device
+        (Net.select_detections, DESIGN.md section 23: detect.select with its 10 replaced by K, every decision bit for bit the host's; K = 10 gives
+        the results of None wherever no two candidates tie in score -- among equal scores the device takes the higher row first, a stable
+        argsort reversed, where the host's default argsort promises no order).  ValueError for any other value, with config.DETECT_MASKS_FOR_SELECTED_ONLY, and with render=True above 16 (the
+        overlay kernel draws all instances of an image in one pass)."""
         cfg = self.config
-        D.check_args(cfg, [image], mask_frame, mask_format, render)
+        D.check_args(cfg, [image], mask_frame, mask_format, render, max_detections)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -766,11 +771,12 @@ class MaskYOLO(object):
         else:
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
             _, det_d, mask_d = predict(x)                                  # device tensors
-        selection = D.Selection(det_d.cpu().numpy(), 1, cs_threshold, cfg.IMAGE_SHAPE)
+        selection = D.Selection.of_batch(self.net, det_d, 1, cs_threshold, cfg.IMAGE_SHAPE, max_detections)
         out = D.batch_results(self._stager(), det_d, mask_d, selection, self._frames([image], mask_frame), mask_format, canvas, feature)
         return self._save_rendered(out, save_path) if render else out
 
-    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense", render=False):
+    def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense", render=False, *,
+                    max_detections=None):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
         config.BATCH_SIZE with `in_flight` batches running at once (one stream / hipGraph / scratch per lane: the launch-bound trunk of one
         batch under the matrix-pipe-bound mask head of another), and every image gets detect()'s own selection and unmolding
@@ -782,10 +788,12 @@ class MaskYOLO(object):
         one Net.rle_masks call whose two downloads are a few KB -- where the dense form pastes and downloads per image.
         mask_format="polygon" (see detect): polygons in place of full_masks, once per batch in the same way (one Net.contour_masks call).
         render=True (see detect; nothing is written to disk here): every dict gains "rendered", drawn once per BATCH on the bytes the batch went
-        up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere."""
+        up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere.
+        max_detections=K (see detect): the selection of every batch runs on the device -- one launch, B * K * 7 words down -- and the batch's
+        [B,R,6] detections are not downloaded."""
         cfg = self.config
         images = list(images)
-        D.check_args(cfg, images, mask_frame, mask_format, render)
+        D.check_args(cfg, images, mask_frame, mask_format, render, max_detections)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -801,7 +809,7 @@ class MaskYOLO(object):
                 yield x
         out = []
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
-            selection = D.Selection(det_d.cpu().numpy(), len(groups[bi]), cs_threshold, cfg.IMAGE_SHAPE)
+            selection = D.Selection.of_batch(self.net, det_d, len(groups[bi]), cs_threshold, cfg.IMAGE_SHAPE, max_detections)
             out += D.batch_results(stager, det_d, mask_d, selection, self._frames(groups[bi], mask_frame), mask_format, canvases.pop(bi))
         return out
 
@@ -824,17 +832,19 @@ class MaskYOLO(object):
                                [image_shape], feature=feature)[0]
 
     # ------------------------------------------------------------------ evaluation
-    def evaluate(self, dataset, cs_threshold=0.35, max_samples=None, in_flight=3):
+    def evaluate(self, dataset, cs_threshold=0.35, max_samples=None, in_flight=3, *, max_detections=None):
         """Mask and box average precision of detect()'s output on a dataset (myolo/evaluate.py) -> Evaluator.result().
         dataset: an object load_image_gt reads (as train() takes), or a sequence of (image, class_ids, boxes, masks) rows as load_image_gt
         returns them.  The images stream through the inference graph exactly as in detect_many and every image gets detect()'s own selection;
         the overlap of each selected detection's PASTED mask with each ground-truth mask is counted on the device (myolo_mask_overlap_counts:
         the paste of myolo_unmold_masks, pixel for pixel) -- K x T integers come down per image, no full-size mask is written or downloaded.
-        An image's ground truth is its first MAX_GT_INSTANCES instances (what a training batch carries)."""
+        An image's ground truth is its first MAX_GT_INSTANCES instances (what a training batch carries).
+        max_detections=K (see detect): up to K detections per image are scored instead of ten, selected on the device."""
         cfg = self.config
         assert self.mode == 'inference'
+        D.check_max_detections(cfg, max_detections)
         if hasattr(dataset, "load_segments"):          # (myolo.coco: the ground truth is decoded on the device, load_mask is never called)
-            return self._evaluate_segments(dataset, cs_threshold, max_samples, in_flight)
+            return self._evaluate_segments(dataset, cs_threshold, max_samples, in_flight, max_detections)
         if hasattr(dataset, "image_ids"):
             ids = list(dataset.image_ids)
             if max_samples is not None:
@@ -867,9 +877,9 @@ class MaskYOLO(object):
                         gm[k, :, :, j] = masks[:, :, j]
                 truth.append((len(grp), gstage.to(self.net.dev, non_blocking=True), gt_ids, gt_boxes))
                 yield x
-        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight, max_detections)
 
-    def _evaluate_segments(self, dataset, cs_threshold, max_samples, in_flight):
+    def _evaluate_segments(self, dataset, cs_threshold, max_samples, in_flight, max_detections=None):
         """evaluate() on a dataset with load_segments (myolo.coco): per batch the image bytes, the segments of every image's
         first MAX_GT_INSTANCES annotations and the index tables go up, and myolo_segment_masks writes the ground-truth masks and their boxes on the
         device -- no mask is filled on the host, no [B,H,W,T] bytes cross PCIe.  A segment that sets no pixel of the network frame is found by its
@@ -898,15 +908,16 @@ class MaskYOLO(object):
                 self.net.segment_masks(tables, gt_masks, gt_boxes)
                 truth.append((len(grp), gt_masks, gt_ids, gt_boxes, True))
                 yield x
-        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight, max_detections)
 
-    def evaluate_shapes_stream(self, n_images, seed=0, start_index=0, cs_threshold=0.35, in_flight=3):
+    def evaluate_shapes_stream(self, n_images, seed=0, start_index=0, cs_threshold=0.35, in_flight=3, *, max_detections=None):
         """evaluate() on images start_index .. start_index + n_images - 1 of the synthetic Shapes stream with the inputs AND the ground truth
         produced on the device (myolo.shapes.ShapesProducer: bit-identical to ShapesDataset / load_image_gt): nothing but the detections' rows and
-        the overlap counts crosses PCIe, so this runs at the speed of the inference forward."""
+        the overlap counts crosses PCIe, so this runs at the speed of the inference forward.  max_detections: see evaluate."""
         from .shapes import ShapesProducer
         cfg = self.config
         assert self.mode == 'inference'
+        D.check_max_detections(cfg, max_detections)
         B = int(cfg.BATCH_SIZE)
         prod = ShapesProducer(cfg, seed=seed, device=self._device)
         truth = collections.deque()
@@ -916,9 +927,9 @@ class MaskYOLO(object):
                 d = prod.batch(list(range(start_index + lo, start_index + lo + B)))     # (a short last batch runs into the next images; ignored below)
                 truth.append((min(B, n_images - lo), d["gt_masks"], d["gt_ids"], d["gt_boxes"]))
                 yield d["images"]
-        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight)
+        return self._evaluate_stream(batches(), truth, cs_threshold, in_flight, max_detections)
 
-    def _evaluate_stream(self, batches, truth, cs_threshold, in_flight):
+    def _evaluate_stream(self, batches, truth, cs_threshold, in_flight, max_detections=None):
         """the common part of evaluate() / evaluate_shapes_stream(): `batches` yields [B,H,W,3] device images and appends each batch's
         (images that count, gt_masks [B,H,W,T] device, gt_ids [B,T], gt_boxes [B,T,4] host or device) to the deque `truth`; a fifth element True
         (_evaluate_segments): a slot whose ground-truth plane is empty is padding whatever its class id."""
@@ -928,7 +939,7 @@ class MaskYOLO(object):
             entry = truth.popleft()
             n, gt_d, gt_ids, gt_boxes = entry[:4]
             drop_empty = len(entry) > 4
-            selection = D.Selection(det_d.cpu().numpy(), n, cs_threshold, self.config.IMAGE_SHAPE)
+            selection = D.Selection.of_batch(self.net, det_d, n, cs_threshold, self.config.IMAGE_SHAPE, max_detections)
             inter, area_pred, area_gt, win = D.overlap_counts(self._stager(), det_d, mask_d, selection, gt_d)
             gt_ids, gt_boxes = [t.cpu().numpy() if torch.is_tensor(t) else t for t in (gt_ids, gt_boxes)]
             if drop_empty:
