@@ -100,6 +100,7 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const float* __restri
         const float a1 = (by2 - by1) * (bx2 - bx1);
         float best = -INFINITY;
         int bi = 0;
+        bool any_nan = false;
         for (int k = 0; k < nkeep; ++k) {
             const int g = keep[k];
             const float x1 = fmaxf(bx1, gtb[g][0]), y1 = fmaxf(by1, gtb[g][1]);
@@ -108,9 +109,12 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const float* __restri
             const float a2 = (gtb[g][3] - gtb[g][1]) * (gtb[g][2] - gtb[g][0]);
             const float uni = a1 + a2 - inter;
             const float iou = inter / uni;
-            if (iou > best) { best = iou; bi = k; }
+            if (iou != iou) any_nan = true;                   // 0 / 0: a zero-area proposal against a zero-area kept box
+            else if (iou > best) { best = iou; bi = k; }      // first maximum among the non-NaN entries (read for positives only)
         }
-        // positive: max IoU >= 0.5 ; negative: < 0.5 ; NaN belongs to neither (2 = dropped)
+        // reduce_max propagates a NaN (the oracle's ov.max(1)): one NaN IoU in the row makes the row's maximum NaN
+        if (any_nan) best = NAN;
+        // positive: max IoU >= 0.5 ; negative: < 0.5 ; NaN belongs to neither (2 = dropped, the tail of the outputs is zero-padded)
         posf[r] = (best >= 0.5f) ? 1 : ((best < 0.5f) ? 0 : 2);
         arg[r] = (short)bi;
     }
