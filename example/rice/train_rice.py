@@ -20,6 +20,7 @@ from myolo.anchors import fit_anchors                # noqa: E402
 from myolo.augment import Augmentation, CopyPaste, Mosaic       # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
+from myolo.optim import Recipe, Schedule             # noqa: E402
 from myolo.via import load_via                       # noqa: E402
 
 
@@ -35,6 +36,14 @@ def main():
                                                                             "per sample, on the device (default: 0, off)")
     ap.add_argument("--copy-paste", type=float, default=0.0, metavar="P", help="paste instances of another sample of the batch into a training "
                                                                                 "sample with probability P, on the device (default: 0, off)")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="C", help="scale the whole gradient down to Euclidean norm C when it is longer "
+                    "(the reference config's GRADIENT_CLIP_NORM is 5.0; default: no clipping)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, metavar="W", help="decoupled (AdamW) weight decay on the convolution kernels "
+                    "(the reference config's WEIGHT_DECAY is 0.0001; default: none)")
+    ap.add_argument("--ema", type=float, default=None, metavar="D", help="keep an exponential moving average of the weights with decay D in (0, 1), "
+                    "saved as saved_model_<stamp>_ema.npz beside every epoch's checkpoint (default: none)")
+    ap.add_argument("--lr-schedule", choices=Schedule.KINDS, default=None, help="learning-rate schedule over the whole run (default: constant)")
+    ap.add_argument("--warmup-steps", type=int, default=0, metavar="N", help="linear warm-up over the first N optimiser steps")
     ap.add_argument("--host-masks", action="store_true", help="fill the outlines on the host (load_mask) instead of on the device")
     ap.add_argument("--fit-anchors", type=int, default=0, metavar="K", help="fit K anchors to the training set first (default: RiceConfig's anchors)")
     a = ap.parse_args()
@@ -50,10 +59,14 @@ def main():
     augmentation = None if a.no_augment else Augmentation(fliplr=.5, scale=(.8, 1.2), translate=(-.1, .1), rotate=(-15, 15),
                                                           brightness=(.8, 1.2))
     model = MaskYOLO(mode="training", config=config, model_dir=a.logs, yolo_pretrain_dir=None, yolo_trainable=True)
+    recipe = None                                   # any of the five flags: the optimiser pass with the recipe on the device
+    if a.clip_norm is not None or a.weight_decay > 0 or a.ema is not None or a.lr_schedule is not None or a.warmup_steps > 0:
+        recipe = Recipe(clip_norm=a.clip_norm, weight_decay=a.weight_decay, ema=a.ema,
+                        schedule=Schedule(a.lr_schedule or "constant", warmup_steps=a.warmup_steps))
     hist = model.train(dataset_train, dataset_val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all',
                        augmentation=augmentation, device_polygons=not a.host_masks,
                        mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None,
-                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None)
+                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None, recipe=recipe)
     print("epoch losses:", ["%.4f" % h for h in hist])
     print("batches rasterised on the device: %d of %d" % (model.host_times["polygon_batches"], model.host_times["steps"]))
     os.makedirs(a.logs, exist_ok=True)

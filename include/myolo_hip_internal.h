@@ -510,6 +510,29 @@ int    myolo_anchor_kmeans(const int32_t* wh /*[n,2] device*/, int64_t n, const 
 int myolo_select_detections(const float* det /*[B,R,6]*/, int B, int R, int n_live, int K, double cs_threshold, double nms_threshold,
                             int shape0, int shape1, int32_t* sel /*[B,K]*/, float* picked /*[B,K,6]*/, int32_t* count /*[B]*/, void* stream);
 
+/* ---- the training recipe's optimiser pass (myolo/optim.py, Net.recipe_step; csrc/optim_kernels.hip; contract: DESIGN.md section 24): global-norm
+ * gradient clipping, AdamW's decoupled weight decay, a freeze mask and an EMA shadow of the weights in ONE read of p, g, m, v, behind a
+ * deterministic gradient-norm reduction; nothing comes back to the host.  They belong beside myolo_adam_step and are declared here only because
+ * the operator API (myolo_hip.h) is held to 70 entries.  All buffers are flat float32 of n elements, n % 4 == 0, 16-byte aligned.
+ *   flags [n/4] uint8, one byte per group of four consecutive elements: bit 0 = trainable, bit 1 = decayed.
+ *   stats: a 24-byte device record { double sumsq; float norm; float scale; int32 skipped; int32 steps; } (zero it once).
+ * myolo_grad_sumsq: sumsq = sum over the trainable groups of (double)x * (double)x, x = g[i] * gs in binary32; per-thread double sums combined in
+ *   a fixed order (workgroup tree, then the partials in one workgroup: a grid that depends on n only, no float atomics), so the bits repeat from
+ *   run to run and agree between ranks that hold the same gradient.  norm = (float)sqrt(sumsq).  scale = 1.0f when clip == 0 (off) or
+ *   sumsq <= (double)clip * clip, else (float)((double)clip / sqrt(sumsq)); a NaN or infinite sumsq gives scale = 0 and skipped += 1 (the step is
+ *   skipped); steps += 1 always.  partials: MYOLO_OPTIM_PARTIALS doubles of scratch.
+ * myolo_adamw_ema_step: reads scale and the skip decision (sumsq not finite) from stats.  Skipped: nothing is written.  A group without bit 0:
+ *   p, m, v, ema are not written.  Otherwise per element, every line one binary32 operation:
+ *     gi = (g*gs)*scale;  mi = b1*m + (1-b1)*gi;  vi = b2*v + ((1-b2)*gi)*gi;  pn = p - (lr_t*mi)/(sqrtf(vi)+eps);
+ *     decayed: pn = pn - lr_wd*p (the old p);  ema (nullable): ema = ema_d*ema + ema_omd*pn.
+ * myolo_swap_f32: exchanges the contents of a and b in one pass.
+ * MYOLO_EINVAL (nothing launched) for a null pointer (ema excepted), n <= 0, n % 4 != 0 and a negative or non-finite clip. */
+#define MYOLO_OPTIM_PARTIALS 1024
+int myolo_grad_sumsq(const float* g, const uint8_t* flags, int64_t n, float gs, float clip, void* stats, double* partials, void* stream);
+int myolo_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema_or_null, const uint8_t* flags, int64_t n, const void* stats,
+                         float lr_t, float b1, float b2, float eps, float gs, float lr_wd, float ema_d, float ema_omd, void* stream);
+int myolo_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

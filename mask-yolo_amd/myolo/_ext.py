@@ -108,6 +108,9 @@ SIGS = {
     "myolo_mask_bce_sel": [P, P, P, F, P, P, I, I, I, I, P, Z, P],
     "myolo_mask_head_out_bwd_sel": [P, P, P, P, P, P, P, L, I, I, I, P, Z, P],
     "myolo_adam_step": [P, P, P, P, L, F, F, F, F, F, P],
+    "myolo_grad_sumsq": [P, P, L, F, F, P, P, P],
+    "myolo_adamw_ema_step": [P, P, P, P, P, P, L, P, F, F, F, F, F, F, F, F, P],
+    "myolo_swap_f32": [P, P, L, P],
     "myolo_matmul_f32": [P, P, P, L, I, I, I, I, P, Z, P],
     "myolo_stream_copy": [P, P, Z, I, I, P],
     "myolo_mfma_probe": [I, I, I, P, P],

@@ -243,6 +243,9 @@ class MaskYOLO(object):
         self._detect_stager = None          # myolo.detect.Stager, made by the first detection call
         self._lr = None
         self._trainable_regex = ".*"
+        self._flags = None                  # (key, uint8 [nparam/4] on the device): the recipe path's trainable / decayed byte per group of four
+        self._resumed = False               # load_checkpoint ran: train(initial_epoch > 0) may continue from it
+        self.global_step = 0                # optimiser steps train() has taken under a recipe (saved by save_checkpoint)
         self.net = self.build(mode=mode, config=self.config)
         self.keras_model = _KerasModelShim(self)
         self.epoch = 0
@@ -302,6 +305,62 @@ class MaskYOLO(object):
     def save_weights(self, filepath):
         np.savez(filepath, **self.net.state_dict())
 
+    # ------------------------------------------------------------------ recipe: statistics, averaged weights, checkpoints
+    def optimizer_stats(self):
+        """-> dict(sumsq, norm, scale, skipped, steps): the record the recipe's optimiser pass keeps on the device -- the last
+        step's squared gradient norm (float64), its norm and clip scale (float32; scale 0 = that step was skipped), and the counts of skipped and
+        of all recipe steps.  Waits for the steps queued so far."""
+        return self.net.optimizer_stats()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with model.ema_weights(): detect / detect_many / evaluate / save_weights / state_dict see the averaged weights a Recipe(ema=...) keeps.
+        The CONTENTS of the live and the averaged buffer are exchanged on the device on entry and again on exit; no tensor is rebound.  BatchNorm
+        moving statistics are shared (they are averages already).  Before any recipe step the average is a copy of the weights.  Do not train
+        inside the context."""
+        self.net.swap_ema()
+        try:
+            yield self
+        finally:
+            self.net.swap_ema()
+
+    def save_checkpoint(self, filepath):
+        """everything a run needs to go on bit for bit in the optimiser: the state_dict ('state/<name>'), both Adam moments, the EMA if one is
+        kept, the optimiser's step count, train()'s global step and the epoch -- one .npz.  See load_checkpoint and train(initial_epoch=...)."""
+        net = self.net
+        arrays = {"state/" + k: v for k, v in net.state_dict().items()}
+        arrays["optim/m"] = net.flat_m.cpu().numpy()
+        arrays["optim/v"] = net.flat_v.cpu().numpy()
+        if net.flat_ema is not None:
+            arrays["optim/ema"] = net.flat_ema.cpu().numpy()
+        arrays["optim/adam_t"] = np.int64(net.adam_t)
+        arrays["optim/global_step"] = np.int64(self.global_step)
+        arrays["optim/epoch"] = np.int64(self.epoch)
+        filepath = str(filepath)
+        np.savez(filepath if filepath.endswith(".npz") else filepath + ".npz", **arrays)
+
+    def load_checkpoint(self, filepath):
+        """restore a save_checkpoint file into this model (same config: the flat layout must match); train(..., initial_epoch=model.epoch)
+        then continues the run."""
+        net = self.net
+        filepath = str(filepath)
+        data = np.load(filepath if filepath.endswith(".npz") else filepath + ".npz")
+        for key in ("optim/m", "optim/v"):
+            if data[key].shape != (net.nparam,):
+                raise ValueError("checkpoint %s holds %d values, this model %d: not the same configuration" % (key, data[key].size, net.nparam))
+        self.load_state_dict({k[len("state/"):]: data[k] for k in data.files if k.startswith("state/")})
+        net.flat_m.copy_(torch.from_numpy(data["optim/m"]))
+        net.flat_v.copy_(torch.from_numpy(data["optim/v"]))
+        if "optim/ema" in data.files:
+            net._ensure_ema().copy_(torch.from_numpy(data["optim/ema"]))
+        else:
+            net.flat_ema = None
+        net.adam_t = int(data["optim/adam_t"])
+        self.global_step = int(data["optim/global_step"])
+        self.epoch = int(data["optim/epoch"])
+        self._weights_cache = None
+        self._resumed = True
+
     # ------------------------------------------------------------------ training
     def set_trainable(self, layer_regex, keras_model=None, indent=0, verbose=1):
         """model.py:1120-1151: layers whose name fully matches the regex are trained; the
@@ -309,14 +368,26 @@ class MaskYOLO(object):
         self._trainable_regex = layer_regex
         mask = torch.zeros_like(self.net.flat_p)
         for k, (off, shp) in self.net.pslots.items():
-            layer = k.split("/")[0]
-            trainable = bool(re.fullmatch(layer_regex, layer))
-            if self.yolo_pretrain_dir is not None and not self.yolo_trainable and not layer.startswith("myolo_mask") \
-                    and layer != "feature_map":
-                trainable = False                      # model.py:867-868
-            if trainable:
+            if self._layer_trainable(k.split("/")[0]):
                 mask[off:off + int(np.prod(shp))] = 1.0
         self._train_mask = None if bool(mask.min() > 0) else mask
+
+    def _layer_trainable(self, layer):
+        trainable = bool(re.fullmatch(self._trainable_regex, layer))
+        if self.yolo_pretrain_dir is not None and not self.yolo_trainable and not layer.startswith("myolo_mask") \
+                and layer != "feature_map":
+            trainable = False                      # model.py:867-868
+        return trainable
+
+    def _recipe_flags(self):
+        """the flags byte of the recipe path (myolo.optim.group_flags) for the current set_trainable regex, on the device; it replaces the mask
+        multiply of the plain path: flat_g is not touched"""
+        key = (self._trainable_regex, self.yolo_pretrain_dir is not None and not self.yolo_trainable)
+        if self._flags is None or self._flags[0] != key:
+            from .optim import group_flags
+            flags = group_flags(self.net.pslots, self.net.nparam, self._layer_trainable)
+            self._flags = (key, torch.from_numpy(flags).to(self.net.dev))
+        return self._flags[1]
 
     def compile(self, learning_rate, momentum):
         """model.py:1062-1118: Adam(lr, 0.9, 0.999, 1e-8); loss = sum of the batch-mean losses
@@ -328,11 +399,16 @@ class MaskYOLO(object):
         self.net.flat_v.zero_()
         self.net.adam_t = 0
 
-    def train_on_batch(self, batch, learning_rate=None):
+    def train_on_batch(self, batch, learning_rate=None, *, recipe=None):
         """One optimisation step on a host batch (the six arrays of model.py:896-897) or an already staged device batch.
         Returns a StepResult -- a read-only Mapping of the reference's training outputs (model.py:899) and the loss scalars: scalars from one
         small asynchronous copy (first read waits for the step), tensors downloaded when indexed.  It keeps the step's output tensors on the
-        device until dropped: see StepResult (release / as_dict) before collecting results over many steps."""
+        device until dropped: see StepResult (release / as_dict) before collecting results over many steps.
+        recipe (keyword only): a myolo.optim.Recipe -- the step's update is Net.recipe_step (clipping, decoupled weight decay, EMA, frozen layers by
+        a flags byte) instead of the mask multiply + Net.adam_step; its Schedule is train()'s business, not this method's."""
+        if recipe is not None:
+            from .optim import check_recipe
+            check_recipe(recipe)
         lr = self._lr if learning_rate is None else learning_rate
         if lr is None:
             lr = self.config.LEARNING_RATE
@@ -340,13 +416,16 @@ class MaskYOLO(object):
         db = batch if isinstance(batch, dict) else net.to_device_batch(batch)
         yolo_only = self.mode == 'yolo' or "gt_masks" not in db
         out = net.forward_backward_yolo(db) if yolo_only else net.forward_backward(db)
-        if getattr(self, "_train_mask", None) is not None:
-            # data-parallel: the bucketed all-reduces run in place on flat_g on the reducer's stream -- join them BEFORE
-            # masking, or RCCL may overwrite zeroed entries / read half-masked data (frozen layers would then move)
-            if net.before_optimizer:
-                net.before_optimizer()
-            net.flat_g.mul_(self._train_mask)          # torch used as a memory op on a flag vector only
-        net.adam_step(lr)
+        if recipe is not None:
+            net.recipe_step(lr, recipe, self._recipe_flags())
+        else:
+            if getattr(self, "_train_mask", None) is not None:
+                # data-parallel: the bucketed all-reduces run in place on flat_g on the reducer's stream -- join them BEFORE
+                # masking, or RCCL may overwrite zeroed entries / read half-masked data (frozen layers would then move)
+                if net.before_optimizer:
+                    net.before_optimizer()
+                net.flat_g.mul_(self._train_mask)          # torch used as a memory op on a flag vector only
+            net.adam_step(lr)
         if yolo_only:
             return StepResult(dict(yolo_output=out["yolo_output"]), out["yolo_terms"], None, out["loss_weights"])
         return self._host_outputs(out)
@@ -385,7 +464,7 @@ class MaskYOLO(object):
 
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers,
               augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0,
-              device_polygons=True, mosaic=None, *, copy_paste=None):
+              device_polygons=True, mosaic=None, *, recipe=None, initial_epoch=0, copy_paste=None):
         """model.py:943-1060.  Returns the list of per-epoch mean training losses; ``self.history`` holds
         {"loss": [...], "val_loss": [...]} like the Keras History the reference's fit_generator produces.
         shuffle_seed: the generators' one-off shuffle (myolo_utils.py:711-712) draws from RandomState(shuffle_seed) -- the
@@ -404,7 +483,23 @@ class MaskYOLO(object):
         validation batches never are.
         copy_paste (keyword only): a myolo.augment.CopyPaste -- every training sample it picks receives instances of another sample of its batch,
         pasted on the device after both have been augmented / mosaicked, on every route, with or without `augmentation`
-        and `mosaic`.  Samples whose source is in no_augmentation_sources neither receive nor donate; validation batches are never pasted."""
+        and `mosaic`.  Samples whose source is in no_augmentation_sources neither receive nor donate; validation batches are never pasted.
+        recipe (keyword only): a myolo.optim.Recipe -- gradient clipping, decoupled weight decay, an EMA of the weights and a learning-rate
+        Schedule, all in the optimiser pass on the device.  Step k of the run (counted over all epochs) is taken at
+        schedule.lr_at(k, epochs * steps per epoch, learning_rate).  The per-epoch logs and self.history gain "lr" (the epoch's last step),
+        "grad_norm" (that step's gradient norm before clipping) and "skipped_steps" (steps the device skipped for a non-finite norm, so far), from
+        one small copy of the device's record at the epoch end; with recipe.ema and a model_dir, saved_model_<stamp>_ema.npz holds the averaged
+        weights beside the epoch's checkpoint.  None: the plain Adam path, as ever.
+        initial_epoch (keyword only): continue a run restored by load_checkpoint at this epoch: the moments, the step count and the EMA are kept
+        and the schedule goes on at step initial_epoch * steps per epoch.  Without a loaded checkpoint it must be 0."""
+        if recipe is not None:
+            from .optim import check_recipe
+            check_recipe(recipe)
+        initial_epoch = int(initial_epoch)
+        if initial_epoch < 0 or initial_epoch > epochs:
+            raise ValueError("initial_epoch must be in [0, epochs], got %r" % (initial_epoch,))
+        if initial_epoch and not self._resumed:
+            raise ValueError("initial_epoch > 0 continues a run restored by load_checkpoint(); none was loaded")
         layer_regex = {"all": ".*"}
         if layers in layer_regex:
             layers = layer_regex[layers]
@@ -449,12 +544,18 @@ class MaskYOLO(object):
         train_gen = mutils.BatchGenerator(train_info, cfg, mode=mode, shuffle=True, jitter=False, norm=True, rng=rng)
         val_gen = mutils.BatchGenerator(val_info, cfg, mode=mode, shuffle=True, jitter=False, norm=True, rng=rng) if val_info else None
         self.set_trainable(layers)
-        self.compile(learning_rate, cfg.LEARNING_MOMENTUM)
+        if initial_epoch:
+            self._lr = float(learning_rate)            # a resumed run keeps its moments and step count
+        else:
+            self.compile(learning_rate, cfg.LEARNING_MOMENTUM)
         from .dist import dp_batch_indices
         schedule = dp_batch_indices(len(train_info), cfg.BATCH_SIZE, rank, world, len(train_gen))   # raises if < one batch
         history = []
         self.history = {"loss": [], "val_loss": []}
+        if recipe is not None:
+            self.history.update(lr=[], grad_norm=[], skipped_steps=[])
         n_steps = len(train_gen)
+        total_steps = epochs * len(schedule)
 
         bytes_ok = bool(train_info) and all(inst[0].dtype == np.uint8 for inst in train_info)
 
@@ -479,18 +580,24 @@ class MaskYOLO(object):
 
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
         # are encoded and uploaded while epoch e finishes
-        prefetch = _Prefetcher([(e, i) for e in range(epochs) for i in schedule], make_item, self.net.dev)
+        prefetch = _Prefetcher([(e, i) for e in range(initial_epoch, epochs) for i in schedule], make_item, self.net.dev)
         stream = iter(prefetch)
         try:
             with _gc_parked():                          # for the whole run: a full collection at every epoch end cost ~50 ms per epoch
-                for ep in range(epochs):
+                for ep in range(initial_epoch, epochs):
                     losses = []
                     pending = None
-                    for _ in schedule:
+                    for k in range(len(schedule)):
                         t0 = time.perf_counter()
                         (_, i), db = next(stream)
                         t1 = time.perf_counter()
-                        out = self.train_on_batch(db)
+                        if recipe is None:
+                            out = self.train_on_batch(db)
+                        else:
+                            self.global_step = ep * len(schedule) + k
+                            lr_now = recipe.lr_at(self.global_step, total_steps, learning_rate)
+                            out = self.train_on_batch(db, lr_now, recipe=recipe)
+                            self.global_step += 1
                         self.host_times["wait_for_batch_s"] += t1 - t0      # the launch thread blocked on the prefetch queue
                         self.host_times["launch_step_s"] += time.perf_counter() - t1
                         self.host_times["steps"] += 1
@@ -502,6 +609,12 @@ class MaskYOLO(object):
                     gc.collect(0)                          # the young generation only (cheap): what this epoch's steps left behind
                     history.append(float(np.mean(losses)))
                     logs = {"loss": history[-1]}
+                    if recipe is not None:                 # one small copy of the device's record; the epoch's last step has been waited for above
+                        st = self.optimizer_stats()
+                        logs.update(lr=lr_now, grad_norm=st["norm"], skipped_steps=st["skipped"])
+                        for key in ("lr", "grad_norm", "skipped_steps"):
+                            self.history[key].append(logs[key])
+                        self.epoch = max(self.epoch, ep + 1)    # what a save_checkpoint from a callback records
                     if val_gen is not None and len(val_info) >= cfg.BATCH_SIZE:
                         # validation_data=val_generator, validation_steps=len(val_generator) (model.py:1053-1054): forward only, BN on
                         # moving statistics, batch-mean of the total loss.  Every rank evaluates the same (small) set.
@@ -515,6 +628,9 @@ class MaskYOLO(object):
                         os.makedirs(self.model_dir, exist_ok=True)
                         stamp = datetime.datetime.now().strftime('%b%d-%H-%M')
                         self.save_weights(os.path.join(self.model_dir, 'saved_model_' + stamp + '.npz'))   # model.py:1026
+                        if recipe is not None and recipe.ema is not None:
+                            with self.ema_weights():
+                                self.save_weights(os.path.join(self.model_dir, 'saved_model_' + stamp + '_ema.npz'))
                     for cb in (custom_callbacks or []):
                         (cb.on_epoch_end if hasattr(cb, "on_epoch_end") else cb)(ep, dict(logs))
             for _ in stream:                               # (drains the prefetch thread: nothing is left when every epoch ran)
