@@ -7,9 +7,13 @@ photograph's overlay -- masks, outlines and boxes drawn over it on the device (D
 --via-json the masks are asked for as polygons (traced on the device) and written as a VIA 2.x annotation file: load it in the
 VGG Image Annotator beside the photographs to correct the predictions, or read it back with myolo.via.load_via.  With --max-detections N up to
 N instances (1 .. 128) are reported per photograph instead of ten, selected on the device; an overlay holds at most 16.
+With --measure-csv every grain's measurements -- area, the area no other grain hides, length and width, orientation, perimeter, Euler number,
+box and centroid, taken on the device -- are written as one CSV row per grain, in pixels or, with --units-per-pixel S,
+in units (lengths times S, areas times S * S); it goes with every other output.
 
   python example/rice/infer_rice.py WEIGHTS.npz IMAGE_DIR [--size 224] [--batch 8] [--threshold 0.35] [--network-frame] [--coco-json PATH]
                                     [--render-dir DIR] [--via-json PATH] [--polygon-tolerance T] [--max-detections N]
+                                    [--measure-csv PATH] [--units-per-pixel S]
 """
 import argparse
 import glob
@@ -22,7 +26,7 @@ sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 import numpy as np                                   # noqa: E402
 from myolo.config import RiceConfig, make_config     # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
-from myolo import render, rle, via                   # noqa: E402
+from myolo import measure, render, rle, via          # noqa: E402
 
 
 def load_rgb(path):
@@ -46,6 +50,9 @@ def main():
                     help="with --via-json: simplify every outline (Douglas-Peucker), dropping vertices within T pixels of it; 0 keeps every corner")
     ap.add_argument("--max-detections", metavar="N", type=int, default=None,
                     help="report up to N instances per photograph (1 .. 128), selected on the device; default: the ten of the host selection")
+    ap.add_argument("--measure-csv", metavar="PATH", help="write one row of measurements per detected grain (myolo.measure.table)")
+    ap.add_argument("--units-per-pixel", metavar="S", type=float, default=1.0,
+                    help="with --measure-csv: the length of a pixel's side in the unit wanted (say mm); lengths are multiplied by S, areas by S * S")
     a = ap.parse_args()
     if a.max_detections is not None and not 1 <= a.max_detections <= 128:
         ap.error("--max-detections must be in 1 .. 128")
@@ -57,6 +64,8 @@ def main():
         ap.error("--via-json outlines the photograph given: it does not go with --network-frame")
     if a.polygon_tolerance < 0:
         ap.error("--polygon-tolerance must be >= 0")
+    if not a.units_per_pixel > 0:
+        ap.error("--units-per-pixel must be > 0")
     mask_format = "polygon" if a.via_json else ("rle" if a.coco_json or a.render_dir else "dense")
 
     paths = sorted(p for ext in ("jpg", "jpeg", "png", "JPG", "JPEG", "PNG") for p in glob.glob(os.path.join(a.images, "*." + ext)))
@@ -65,12 +74,15 @@ def main():
     config = make_config(RiceConfig, IMAGE_SHAPE=[a.size, a.size, 3], BATCH_SIZE=a.batch)
     model = MaskYOLO(mode="inference", config=config)
     model.load_weights(a.weights)
-    total, coco, annotations = 0, [], {}
+    total, coco, annotations, rows = 0, [], {}, []
     for lo in range(0, len(paths), 8 * a.batch):                  # a few batches at a time: the photographs of one call are held in memory
         chunk = paths[lo:lo + 8 * a.batch]
         photos = [load_rgb(p) for p in chunk]
         results = model.detect_many(photos, cs_threshold=a.threshold, mask_frame="network" if a.network_frame else "image",
-                                    mask_format=mask_format, render=bool(a.render_dir), max_detections=a.max_detections)
+                                    mask_format=mask_format, render=bool(a.render_dir), max_detections=a.max_detections,
+                                    measure=bool(a.measure_csv))
+        if a.measure_csv:
+            rows += measure.table(results, names=[os.path.basename(p) for p in chunk], scale=a.units_per_pixel)
         if a.via_json:
             annotations.update(via.via_annotations(results, [os.path.basename(p) for p in chunk], class_names=["BG", "rice"],
                                                    tolerance=a.polygon_tolerance))
@@ -98,6 +110,9 @@ def main():
         with open(a.via_json, "w") as f:
             json.dump(annotations, f)
         print("wrote %s" % a.via_json)
+    if a.measure_csv:
+        measure.write_csv(a.measure_csv, rows)
+        print("wrote %s" % a.measure_csv)
 
 
 if __name__ == "__main__":

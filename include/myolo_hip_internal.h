@@ -346,6 +346,31 @@ int myolo_contour_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /
                         int32_t* vert_off /*[B*K+1]*/, int32_t* verts /*[cap][2]: X, Y*/, int32_t* loop_id /*[cap]*/, int64_t cap,
                         int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- measurements of the detected instances (myolo/measure.py, MaskYOLO.detect(measure=True); the record and the kernel: DESIGN.md section 25):
+ * for the PASTED mask of every selected detection -- the paste of myolo_unmold_masks, the same device function, pixel for pixel -- a record of
+ * MYOLO_MEASURE_WORDS exact integer sums, taken on the device without writing or downloading a full-size mask.  Declared here rather than in the
+ * operator API (myolo_hip.h, held to 70 entries).
+ * masks, det, sel, sel_host, frames, frames_host as myolo_rle_masks takes them, but K is 1 .. 128, taken whole: a slot is ranked against ALL
+ * earlier slots of its image.  A slot value may repeat a row.  With m(x, y) the mask of slot s = b * K + k over image b's h x w frame (x the
+ * column, y the row; 0 outside the frame), out[s] is
+ *   0 area, 1 visible_area = the set pixels that no earlier live slot of the image holds, 2 sx, 3 sy, 4 sxx, 5 syy, 6 sxy = the sums of x, y,
+ *   x*x, y*y, x*y over the set pixels, 7 perimeter = the unit edges between a set pixel and a 4-neighbour that is 0 or outside the frame,
+ *   8 quads = the positions with m(x,y) & m(x+1,y) & m(x,y+1) & m(x+1,y+1), 9 .. 12 x1, y1, x2, y2 = the tight box of the set pixels, far corner
+ *   exclusive, zeros when area is 0;
+ * an empty slot (sel < 0) is 13 zeros.  Every word of out is written (the caller zeroes nothing), nothing behind out or behind ws_bytes, and the
+ * result does not depend on what the workspace held.  h, w <= 32768 keep every word inside int64.  Integer work only behind the paste, 64-bit
+ * integer atomics across workgroups: bit-identical from run to run.
+ * MYOLO_EINVAL (message "measure_masks: ...", nothing launched, out untouched) for a null pointer, B < 1, K outside 1 .. 128, h or w outside
+ * 1 .. 32768, sel >= R, and a workspace under myolo_measure_masks_ws_bytes(B, K).  sel_host and frames_host are read before anything is
+ * launched. */
+#define MYOLO_MEASURE_WORDS 13
+size_t myolo_measure_masks_ws_bytes(int B, int K);
+int myolo_measure_masks(const float* masks /*[B,R,mh,mw,C]*/, const float* det /*[B,R,6]*/,
+                        const int32_t* sel /*[B,K] device, <0 = empty*/, const int32_t* sel_host,
+                        const int32_t* frames /*[B,2] device: h, w*/, const int32_t* frames_host,
+                        int64_t* out /*[B,K,13]*/, int B, int R, int K, int mh, int mw, int C,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ---- overlay of the selected detections (myolo/render.py, MaskYOLO.detect(render=True); the picture and the kernel: DESIGN.md section 16): the
  * three layers of render.render_instances -- every PASTED mask blended into the image, every mask's one-pixel outline, the dashed ring of every
  * paste window, each over the slots in order -- drawn from the uploaded image bytes in one launch.  A mask pixel is the paste of

@@ -1042,6 +1042,186 @@ __global__ __launch_bounds__(256) void render_instances_kernel(const uint8_t* __
 }
 
 // ---------------------------------------------------------------------------------------
+// Measurements of the pasted masks (myolo/measure.py measure_dense is the statement of the record): for every image b (its
+// own frame h x w) and selected detection k, MYOLO_MEASURE_WORDS exact integer sums over the mask: area, the area no earlier slot of the image
+// covers, the first and second raw moments, the perimeter, the 2 x 2 blocks and the tight box.  A pixel is unmold_pixel, so the sums are those of
+// the dense paste by construction; no dense mask is written, and everything behind unmold_pixel is integer work.
+// A wave owns one tile of MS_TW columns x MS_TH rows of one image, a lane per column, and walks the image's slots IN ORDER; a slot whose window,
+// grown by one column to the left and one row upwards, misses the tile is skipped, so the work follows the windows and not K x the frame.  The
+// lane evaluates the window's rows of its column into one 32-bit word (bit i = row ty0 + i) and the pixel above the tile; lanes 0 .. 32 also
+// evaluate the column left of the tile and the corner, which a ballot turns into lane 0's left neighbour.  From there on it is bit work:
+//   area / visible     popc(w), popc(w & ~covered) with `covered` the OR of the words of the earlier slots
+//   moments            with i the bit index and l the lane, the wave sums of popc, sum i, sum i^2, l * popc, l^2 * popc, l * sum i (sums over the
+//                      set bits from popcounts under the masks of the index's binary digits) are shifted to (tx0 + l, ty0 + i) in 64 bits
+//   perimeter          every unit edge between a set pixel and a clear one (or the frame's outside) belongs to the tile of its lower / right
+//                      pixel: the transitions against the word shifted down by one row, and against the left neighbour's word; the frame's
+//                      bottom and right edges belong to the last row / column
+//   quads              a 2 x 2 block belongs to its bottom-right pixel: w & left & both shifted down by one row
+// The partial sums of a slot are reduced over the wave, added into the workgroup's record in LDS (integer atomics), and every workgroup adds its
+// non-trivial words into out with one 64-bit integer atomic each (add, min for x1 / y1, max for x2 / y2): integer sums, the same bits every run.
+// measure_init_kernel writes every word of out first (zeros, the identity of min in x1 / y1); measure_finish_kernel zeroes the box of an empty mask.
+// ---------------------------------------------------------------------------------------
+#define MS_MAXK 128
+#define MS_TW 64
+#define MS_TH 32
+#define MS_NONE 0xFFFFFFFFFFFFFFFFull                             // x1 / y1 before any pixel: the identity of min
+
+__device__ __forceinline__ unsigned ms_wave_sum(unsigned v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ unsigned ms_wave_or(unsigned v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
+
+// sum of i and of i * i over the set bits i of w: i = sum_j d_j 2^j, so sum i = sum_j 2^j popc(w & D_j) and
+// sum i^2 = sum_j 4^j popc(w & D_j) + sum_{j<k} 2^(j+k+1) popc(w & D_j & D_k), D_j = the bit positions whose digit j is 1
+__device__ __forceinline__ void ms_bit_index_sums(unsigned w, unsigned& s1, unsigned& s2)
+{
+    const unsigned D[5] = {0xAAAAAAAAu, 0xCCCCCCCCu, 0xF0F0F0F0u, 0xFF00FF00u, 0xFFFF0000u};
+    s1 = 0, s2 = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const unsigned c = __popc(w & D[j]);
+        s1 += c << j;
+        s2 += c << (2 * j);
+#pragma unroll
+        for (int k = j + 1; k < 5; ++k) s2 += (unsigned)__popc(w & D[j] & D[k]) << (j + k + 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void measure_init_kernel(unsigned long long* __restrict__ out, int nslots)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nslots * MYOLO_MEASURE_WORDS) return;
+    const int word = i % MYOLO_MEASURE_WORDS;
+    out[i] = (word == 9 || word == 10) ? MS_NONE : 0ull;
+}
+
+__global__ __launch_bounds__(256) void measure_finish_kernel(unsigned long long* __restrict__ out, int nslots)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nslots) return;
+    unsigned long long* o = out + (long long)s * MYOLO_MEASURE_WORDS;
+    if (o[0] == 0ull) o[9] = o[10] = 0ull;                         // (x2, y2 are still the zeros of the init)
+}
+
+__global__ __launch_bounds__(256) void measure_masks_kernel(const float* __restrict__ masks, const float* __restrict__ det,
+                                                            const int32_t* __restrict__ sel, const int32_t* __restrict__ allhigh,
+                                                            const int32_t* __restrict__ frames, unsigned long long* __restrict__ out, int R,
+                                                            int K, int mh, int mw, int C)
+{
+    __shared__ int winL[MS_MAXK][4];                               // [x1, y1, x2, y2) of the slot's paste; x2 = 0 for a slot that holds nothing
+    __shared__ unsigned long long accL[MS_MAXK * MYOLO_MEASURE_WORDS];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.y;
+    const int H = frames[2 * b], W = frames[2 * b + 1];
+    const int tiles_x = (W + MS_TW - 1) / MS_TW, tiles_y = (H + MS_TH - 1) / MS_TH;
+    const int ntiles = tiles_x * tiles_y;                          // (h, w <= 32768: at most 2^19)
+    if ((int)blockIdx.x * 4 >= ntiles) return;                     // the grid is the largest image's: uniform over the workgroup
+
+    for (int k = tid; k < K; k += 256) {
+        const int s = sel[b * K + k];
+        int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+        if (s >= 0 && s < R) unmold_window(det + ((long long)b * R + s) * 6, H, W, x1, y1, x2, y2);
+        if (x2 <= x1 || y2 <= y1) x1 = y1 = x2 = y2 = 0;
+        winL[k][0] = x1, winL[k][1] = y1, winL[k][2] = x2, winL[k][3] = y2;
+    }
+    for (int i = tid; i < K * MYOLO_MEASURE_WORDS; i += 256) {
+        const int word = i % MYOLO_MEASURE_WORDS;
+        accL[i] = (word == 9 || word == 10) ? MS_NONE : 0ull;
+    }
+    __syncthreads();
+
+    const int t = blockIdx.x * 4 + wave;
+    if (t < ntiles) {                                              // the same for the whole wave, as is everything that decides a branch below
+        const int tx0 = (t % tiles_x) * MS_TW, ty0 = (t / tiles_x) * MS_TH;
+        const int x = tx0 + lane;
+        const int nrows = min(MS_TH, H - ty0);                     // the tile's rows inside the frame; bits nrows .. 31 of a word stay 0
+        const unsigned rowmask = nrows == 32 ? 0xFFFFFFFFu : ((1u << nrows) - 1u);
+        const bool last_row = ty0 + nrows == H;                    // the frame's bottom edge lies under bit nrows - 1
+        unsigned covered = 0;
+        for (int k = 0; k < K; ++k) {
+            const int x1 = winL[k][0], y1 = winL[k][1], x2 = winL[k][2], y2 = winL[k][3];
+            // an empty slot or window (sel may be -1: nothing below may be read), or no pixel of the window in the tile, its left column or the
+            // row above it
+            if (x2 <= x1 || x2 <= tx0 - 1 || x1 >= tx0 + MS_TW || y2 <= ty0 - 1 || y1 >= ty0 + MS_TH) continue;
+            const long long row = (long long)b * R + sel[b * K + k];
+            const float* d = det + row * 6;
+            const float* m0 = masks + row * mh * mw * C;
+            const int ah = allhigh[b * K + k];
+            unsigned w = 0;
+            const int ya = max(ty0, y1), yb = min(ty0 + MS_TH, y2);
+            for (int y = ya; y < yb; ++y) w |= (unsigned)unmold_pixel(d, m0, ah, x, y, mh, mw, C, H, W) << (y - ty0);
+            const unsigned above = unmold_pixel(d, m0, ah, x, ty0 - 1, mh, mw, C, H, W);
+            int hv = 0;                                            // lanes 0 .. 31: the column left of the tile; lane 32: the corner above it
+            if (lane <= 32) hv = unmold_pixel(d, m0, ah, tx0 - 1, lane < 32 ? ty0 + lane : ty0 - 1, mh, mw, C, H, W);
+            const unsigned long long halo = __ballot(hv);
+            const unsigned long long cols = __ballot(w != 0);      // the tile's columns that hold a pixel
+            if (!(cols | halo | __ballot(above))) continue;
+            unsigned left = __shfl_up(w, 1), labove = __shfl_up(above, 1);
+            if (lane == 0) left = (unsigned)halo, labove = (unsigned)(halo >> 32) & 1u;
+            const unsigned n = __popc(w), vis = __popc(w & ~covered);
+            covered |= w;
+            const unsigned wu = (w << 1) | above, lu = (left << 1) | labove;
+            unsigned per = __popc((w ^ wu) & rowmask) + (last_row ? (w >> (nrows - 1)) & 1u : 0u);
+            if (x < W) per += __popc(w ^ left) + (x == W - 1 ? n : 0u);
+            const unsigned quads = __popc(w & left & wu & lu);
+            unsigned s1, s2;
+            ms_bit_index_sums(w, s1, s2);
+            // wave sums; the small ones share a word: n, vis <= 2048, per <= 97 * 64, quads <= 2048, sum i <= 496 * 64, l * n <= 2016 * 32 < 2^16
+            const unsigned lx = lane;
+            const unsigned p0 = ms_wave_sum(n | (vis << 16)), p1 = ms_wave_sum(per | (quads << 16)), p2 = ms_wave_sum(s1 | ((lx * n) << 16));
+            const long long S2 = ms_wave_sum(s2), LXXN = ms_wave_sum(lx * lx * n), LXS1 = ms_wave_sum(lx * s1);
+            const unsigned rows = ms_wave_or(w);
+            const long long N = p0 & 0xFFFFu, S1 = p2 & 0xFFFFu, LXN = p2 >> 16;
+            const long long X0 = tx0, Y0 = ty0;
+            unsigned long long v = 0;
+            switch (lane) {
+            case 0: v = N; break;
+            case 1: v = p0 >> 16; break;
+            case 2: v = X0 * N + LXN; break;
+            case 3: v = Y0 * N + S1; break;
+            case 4: v = X0 * X0 * N + 2 * X0 * LXN + LXXN; break;
+            case 5: v = Y0 * Y0 * N + 2 * Y0 * S1 + S2; break;
+            case 6: v = X0 * Y0 * N + X0 * S1 + Y0 * LXN + LXS1; break;
+            case 7: v = p1 & 0xFFFFu; break;
+            case 8: v = p1 >> 16; break;
+            case 9: v = cols ? (unsigned long long)(tx0 + __ffsll((long long)cols) - 1) : MS_NONE; break;
+            case 10: v = rows ? (unsigned long long)(ty0 + __ffs((int)rows) - 1) : MS_NONE; break;
+            case 11: v = cols ? (unsigned long long)(tx0 + 64 - __clzll((long long)cols)) : 0ull; break;
+            case 12: v = rows ? (unsigned long long)(ty0 + 32 - __clz((int)rows)) : 0ull; break;
+            default: break;
+            }
+            if (lane < MYOLO_MEASURE_WORDS) {
+                unsigned long long* a = accL + k * MYOLO_MEASURE_WORDS + lane;
+                if (lane == 9 || lane == 10) atomicMin(a, v);
+                else if (lane == 11 || lane == 12) atomicMax(a, v);
+                else if (v) atomicAdd(a, v);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < K * MYOLO_MEASURE_WORDS; i += 256) {
+        const int word = i % MYOLO_MEASURE_WORDS;
+        const unsigned long long v = accL[i];
+        unsigned long long* o = out + (long long)b * K * MYOLO_MEASURE_WORDS + i;
+        if (word == 9 || word == 10) {
+            if (v != MS_NONE) atomicMin(o, v);
+        } else if (v) {
+            if (word == 11 || word == 12) atomicMax(o, v);
+            else atomicAdd(o, v);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // GPU producer of the Shapes input pipeline: rasterise the images and instance masks
 // of a batch from their shape specifications (example/shapes/dataset_shapes.py:80-135: load_image / load_mask /
 // draw_shape incl. the occlusion rule :112-116), drop empty instances and take tight boxes (load_image_gt + extract_bboxes,
@@ -1401,6 +1581,44 @@ int myolo_render_instances(const uint8_t* images, uint8_t* out, size_t nbytes, c
     hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(B * K), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
     hipLaunchKernelGGL(render_instances_kernel, dim3((unsigned)tiles, B), dim3(256), 0, s, images, out, desc, masks, det, sel,
                        (const int32_t*)allhigh, colors, alpha, box_alpha, flags, R, K, mh, mw, C);
+    MYOLO_CHECK_LAUNCH();
+    return MYOLO_OK;
+}
+
+// the B * K all-high flags
+size_t myolo_measure_masks_ws_bytes(int B, int K)
+{
+    if (B <= 0 || K <= 0) return 0;
+    return ((size_t)B * K * sizeof(int32_t) + 255) / 256 * 256;
+}
+
+int myolo_measure_masks(const float* masks, const float* det, const int32_t* sel, const int32_t* sel_host, const int32_t* frames,
+                        const int32_t* frames_host, int64_t* out, int B, int R, int K, int mh, int mw, int C, void* ws, size_t ws_bytes,
+                        void* stream)
+{
+    MYOLO_REQUIRE(masks && det && sel && sel_host && frames && frames_host && out && ws, "measure_masks: null pointer");
+    MYOLO_REQUIRE(B > 0 && B <= 65535 && R > 0 && mh > 0 && mw > 0 && C > 0, "measure_masks: bad sizes");
+    MYOLO_REQUIRE(K > 0 && K <= MS_MAXK, "measure_masks: need 1 <= K <= %d (got K=%d)", MS_MAXK, K);
+    long long tiles = 0;
+    for (int b = 0; b < B; ++b) {
+        const int h = frames_host[2 * b], w = frames_host[2 * b + 1];
+        MYOLO_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "measure_masks: frame %d is %d x %d (1 <= h, w <= 32768 needed)", b, h, w);
+        const long long t = (long long)((w + MS_TW - 1) / MS_TW) * ((h + MS_TH - 1) / MS_TH);
+        tiles = t > tiles ? t : tiles;
+    }
+    for (long long i = 0; i < (long long)B * K; ++i)
+        MYOLO_REQUIRE(sel_host[i] < R, "measure_masks: sel[%lld] = %d is not a row of the %d detections", i, sel_host[i], R);
+    const size_t need = myolo_measure_masks_ws_bytes(B, K);
+    MYOLO_REQUIRE(ws_bytes >= need, "measure_masks: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    int32_t* allhigh = (int32_t*)ws;
+    unsigned long long* o = (unsigned long long*)out;
+    hipStream_t s = (hipStream_t)stream;
+    const int nslots = B * K;
+    hipLaunchKernelGGL(measure_init_kernel, dim3((nslots * MYOLO_MEASURE_WORDS + 255) / 256), dim3(256), 0, s, o, nslots);
+    hipLaunchKernelGGL(unmold_allhigh_kernel, dim3(nslots), dim3(256), 0, s, masks, det, allhigh, mh, mw, C, sel, K, R);
+    hipLaunchKernelGGL(measure_masks_kernel, dim3((unsigned)((tiles + 3) / 4), B), dim3(256), 0, s, masks, det, sel, (const int32_t*)allhigh,
+                       frames, o, R, K, mh, mw, C);
+    hipLaunchKernelGGL(measure_finish_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, o, nslots);
     MYOLO_CHECK_LAUNCH();
     return MYOLO_OK;
 }

@@ -142,6 +142,7 @@ SIGS = {
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
     "myolo_contour_masks": [P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
+    "myolo_measure_masks": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, Z, P],
     "myolo_render_instances": [P, P, Z, P, P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, P, Z, P],
     "myolo_anchor_kmeans": [P, L, P, P, I, I, P, P, P, P, P, P, Z, P],
     "myolo_select_detections": [P, I, I, I, I, D, D, I, I, P, P, P, P],
@@ -236,6 +237,8 @@ def load():
     lib.myolo_rle_masks_ws_bytes.restype = Z
     lib.myolo_contour_masks_ws_bytes.argtypes = [I, I, I, I, L]
     lib.myolo_contour_masks_ws_bytes.restype = Z
+    lib.myolo_measure_masks_ws_bytes.argtypes = [I, I]
+    lib.myolo_measure_masks_ws_bytes.restype = Z
     lib.myolo_anchor_kmeans_ws_bytes.argtypes = [L, I]
     lib.myolo_anchor_kmeans_ws_bytes.restype = Z
     lib.myolo_wprep_refresh.argtypes = [P, I, I, I, P]
@@ -251,7 +254,8 @@ def exported_symbols():
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
                               "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_mosaic_batch_ws_bytes", "myolo_copy_paste_batch_ws_bytes",
                               "myolo_resize_images_ws_bytes",
-                              "myolo_rle_masks_ws_bytes", "myolo_contour_masks_ws_bytes", "myolo_anchor_kmeans_ws_bytes"]
+                              "myolo_rle_masks_ws_bytes", "myolo_contour_masks_ws_bytes", "myolo_measure_masks_ws_bytes",
+                              "myolo_anchor_kmeans_ws_bytes"]
 
 
 def ptr(t):
@@ -478,6 +482,10 @@ def rle_masks_ws_bytes(b, k, max_w):
 
 def contour_masks_ws_bytes(b, k, max_h, max_w, cap):
     return int(load().myolo_contour_masks_ws_bytes(int(b), int(k), int(max_h), int(max_w), int(cap)))
+
+
+def measure_masks_ws_bytes(b, k):
+    return int(load().myolo_measure_masks_ws_bytes(int(b), int(k)))
 
 
 def anchor_kmeans_ws_bytes(n, runs):

@@ -2,7 +2,7 @@
 ``myolo.detect`` -- the one detection pipeline under MaskYOLO.detect / detect_many / evaluate / evaluate_shapes_stream:
 uint8 images are staged to the device (Stager), run through the forward, up to SLOTS rows per image are selected on the host from the one
 detection download of a batch (Selection), and the selection is handed to a mask consumer: dense_masks, rle_masks, polygon_masks, overlap_counts,
-render.  With max_detections=K the same record is filled on the device instead, K <= MAX_SLOTS rows per image (Selection.from_device, DESIGN.md
+measurements, render.  With max_detections=K the same record is filled on the device instead, K <= MAX_SLOTS rows per image (Selection.from_device, DESIGN.md
 section 23); no consumer learns where a selection came from.
 """
 import numpy as np
@@ -34,7 +34,7 @@ def check_max_detections(cfg, max_detections, render=False):
                          % (RENDER_SLOTS, max_detections))
 
 
-def check_args(cfg, images, mask_frame, mask_format, render, max_detections=None):
+def check_args(cfg, images, mask_frame, mask_format, render, max_detections=None, measure=False):
     """detect() / detect_many()'s argument checks, before anything is uploaded"""
     selected_only = bool(getattr(cfg, "DETECT_MASKS_FOR_SELECTED_ONLY", False))
     check_max_detections(cfg, max_detections, render)
@@ -49,6 +49,8 @@ def check_args(cfg, images, mask_frame, mask_format, render, max_detections=None
             "a uint8 [h,w,3] image is expected (got %s %s)" % (im.dtype, tuple(im.shape))
     if render and selected_only:
         raise ValueError("render=True is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
+    if measure and selected_only:
+        raise ValueError("measure=True is not supported with config.DETECT_MASKS_FOR_SELECTED_ONLY")
     if render and mask_frame == "network" and any(list(im.shape) != list(cfg.IMAGE_SHAPE) for im in images):
         raise ValueError("render=True draws on the image given: mask_frame='network' needs every image at config.IMAGE_SHAPE")
 
@@ -228,6 +230,17 @@ def polygon_masks(net, det_d, mask_d, selection, frames):
     return [loops[k * K:k * K + len(selection.rows(k))] for k in range(selection.n)]
 
 
+def measurements(net, det_d, mask_d, selection, frames):
+    """measure.properties of the instances of the live images of a batch, one Net.measure_masks call over all the slots of every image: per
+    image the dict of arrays over its instances, in class_ids order, taken in the frame frames[k] = (h, w, ...) its masks are pasted into"""
+    from .measure import properties
+    fr = np.ones(selection.sel.shape[:1] + (2,), np.int32)                 # (padding: no slot, a 1 x 1 frame)
+    for k, f in enumerate(frames):
+        fr[k] = (int(f[0]), int(f[1]))
+    raw = net.measure_masks(det_d, mask_d, selection.sel, fr)
+    return [properties(raw[k, :len(selection.rows(k))]) for k in range(selection.n)]
+
+
 def overlap_counts(stager, det_d, mask_d, selection, gt_d):
     """(inter [B,K,T], area_pred [B,K], area_gt [B,T], win [B,K,4]) on the host: one Net.overlap_counts call against gt_d [B,H,W,T]"""
     # (the table goes up from a pinned buffer without blocking; free again by the next batch: the downloads here end with a synchronisation)
@@ -248,9 +261,10 @@ def render(net, canvas, det_d, mask_d, selection):
     return net.render_instances(images_d, desc, det_d[:n], mask_d[:n], selection.sel[:n])
 
 
-def batch_results(stager, det_d, mask_d, selection, frames, mask_format="dense", canvas=None, feature=None):
+def batch_results(stager, det_d, mask_d, selection, frames, mask_format="dense", canvas=None, feature=None, measure=False):
     """detect()'s result dicts of the live images of one batch: det_d [B,R,6], mask_d [B,R,mh,mw,C] (None: see dense_masks) device tensors,
-    frames[k] the frame image k reports in; with a canvas the dicts gain "rendered", drawn from the same selection after either mask form."""
+    frames[k] the frame image k reports in; with a canvas the dicts gain "rendered", drawn from the same selection after either mask form, and
+    with measure "measurements" (measure.properties of the image's instances), taken from the same selection in the same frame."""
     out = [selection.result(k, frames[k]) for k in range(selection.n)]
     if mask_format == "rle":
         for r, codes in zip(out, rle_masks(stager.net, det_d, mask_d, selection, frames)):
@@ -261,6 +275,9 @@ def batch_results(stager, det_d, mask_d, selection, frames, mask_format="dense",
     else:
         for k, r in enumerate(out):
             r["full_masks"] = dense_masks(stager, det_d[k], None if mask_d is None else mask_d[k], selection.rows(k), frames[k], feature)
+    if measure:
+        for r, props in zip(out, measurements(stager.net, det_d, mask_d, selection, frames)):
+            r["measurements"] = props
     if canvas is not None:
         for r, pic in zip(out, render(stager.net, canvas, det_d, mask_d, selection)):
             r["rendered"] = pic

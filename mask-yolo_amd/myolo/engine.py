@@ -554,6 +554,7 @@ class Net(object):
         self._contour_verts = None        # contour_masks: [verts cap x 2 | loop_id cap] int32 on the device (grow-only), its workspace, the pinned staging
         self._contour_ws = None
         self._contour_pin = None
+        self._measure_pin = None          # measure_masks: the pinned buffer [records | sel | frames] (grow-only)
         self._render_args = None          # render_instances: the pinned buffer of its arguments and the pinned, grow-only one the overlays come down into
         self._render_pin = None
         self._select_pin = None           # select_detections: the pinned buffer [sel | picked] comes down into (grow-only)
@@ -3079,6 +3080,38 @@ class Net(object):
             cuts = np.flatnonzero(np.diff(loop_id[a:b])) + 1 if b > a else ()
             out.append(np.split(verts[a:b], cuts) if b > a else [])
         return out
+
+    def measure_masks(self, det_d, mask_d, sel, frames):
+        """The measurement records of the pasted masks of selected detections, taken on the device (myolo_measure_masks,
+        include/myolo_hip_internal.h; the record: myolo/measure.py): det_d, mask_d, sel [B,K] and frames [B,2] as
+        rle_masks takes them, K <= 128 in ONE call (visible_area ranks a slot against all earlier slots of its image, so sel is not cut into
+        column blocks).  -> int64 [B,K,13] numpy array (a copy): measure.measure_dense of the dense paste integer for integer, zeros in the
+        empty slots.  One upload (sel and frames together) and one download of B*K*104 bytes, both through one pinned buffer."""
+        expected = "det [B,R,6] f32, masks [B,R,mh,mw,C] f32, sel [B,K] i32, frames [B,2] i32"
+        sel_t, (B, R, K, mh, mw, C) = self._selected_sizes("measure_masks", expected, det_d, mask_d, sel)
+        if not 1 <= K <= SEL_MAX:
+            raise ValueError("measure_masks: 1 .. %d slots per image (got K=%d)" % (SEL_MAX, K))
+        sel_h = sel_t.numpy()
+        frames_h = np.ascontiguousarray(frames.numpy() if torch.is_tensor(frames) else frames)
+        if frames_h.dtype != np.int32 or tuple(frames_h.shape) != (B, 2):
+            raise ValueError("measure_masks: %s expected" % expected)
+        det_d, mask_d = det_d.contiguous(), mask_d.contiguous()
+        nsel, nrec = B * K, B * K * 13
+        nargs = (nsel + 2 * B + 1) // 2                                   # [sel | frames] int32 in 8-byte words
+        # host side: [records | sel | frames] in one pinned buffer (free again when this call returns: it ends with a synchronising download)
+        if self._measure_pin is None or self._measure_pin.numel() < nrec + nargs:
+            self._measure_pin = torch.empty(nrec + nargs, dtype=torch.int64).pin_memory()
+        rec_h, args_h = self._measure_pin[:nrec], self._measure_pin[nrec:nrec + nargs]
+        args_np = args_h.numpy().view(np.int32)
+        args_np[:nsel], args_np[nsel:nsel + 2 * B] = sel_h.reshape(-1), frames_h.reshape(-1)
+        args_d = args_h.to(self.dev, non_blocking=True)
+        ws_bytes = X.measure_masks_ws_bytes(B, K)
+        buf = torch.empty(nrec + ws_bytes // 8, dtype=torch.int64, device=self.dev)            # [records | workspace]
+        X.call("myolo_measure_masks", X.ptr(mask_d), X.ptr(det_d), args_d.data_ptr(), args_np.ctypes.data, args_d.data_ptr() + nsel * 4,
+               args_np.ctypes.data + nsel * 4, buf.data_ptr(), B, R, K, mh, mw, C, buf.data_ptr() + nrec * 8, ws_bytes, X.stream())
+        rec_h.copy_(buf[:nrec], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return rec_h.numpy().reshape(B, K, 13).copy()
 
     def predict_yolo(self, images):
         """'yolo' mode forward (model.py:906-920)."""

@@ -849,7 +849,7 @@ class MaskYOLO(object):
         return [im.shape if mask_frame == "image" else self.config.IMAGE_SHAPE for im in images]
 
     def detect(self, image, weights_dir=None, save_path='./img_results/', cs_threshold=0.35, display=False, mask_frame="image",
-               mask_format="dense", render=False, *, max_detections=None):
+               mask_format="dense", render=False, *, max_detections=None, measure=False):
         """model.py:1238-1328.  Returns [ {bboxes, class_ids, confidence_scores, full_masks} ].  An image of another size than config.IMAGE_SHAPE
         is resized to it on the device (Net.resize_to_frame: myolo_utils.resize_image's result, bit for bit) and reported in
         the frame mask_frame names: "image" -- bboxes in pixels of the image given, full_masks [h,w,n] pasted at that size -- or "network" --
@@ -874,9 +874,15 @@ class MaskYOLO(object):
         (Net.select_detections, DESIGN.md section 23: detect.select with its 10 replaced by K, every decision bit for bit the host's; K = 10 gives
         the results of None wherever no two candidates tie in score -- among equal scores the device takes the higher row first, a stable
         argsort reversed, where the host's default argsort promises no order).  ValueError for any other value, with config.DETECT_MASKS_FOR_SELECTED_ONLY, and with render=True above 16 (the
-        overlay kernel draws all instances of an image in one pass)."""
+        overlay kernel draws all instances of an image in one pass).
+        measure=True (keyword only): the dict gains "measurements", myolo.measure.properties of the image's instances in the order of class_ids:
+        area, visible_area (the part no earlier instance covers), perimeter, euler_number (pieces minus holes), bbox, centroid, major / minor
+        axis length, orientation, eccentricity and the raw records of 13 exact integer sums they come from -- measure.measure_dense of the
+        full_masks planes integer for integer, in the frame mask_frame names.  The sums are taken on the device (Net.measure_masks, DESIGN.md
+        section 25) whatever mask_format is; about 100 bytes per instance come down.  myolo.measure.table / write_csv write them out.  Not
+        supported together with config.DETECT_MASKS_FOR_SELECTED_ONLY (ValueError)."""
         cfg = self.config
-        D.check_args(cfg, [image], mask_frame, mask_format, render, max_detections)
+        D.check_args(cfg, [image], mask_frame, mask_format, render, max_detections, measure)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -888,11 +894,12 @@ class MaskYOLO(object):
             predict = self.net.predict_graphed if getattr(cfg, "INFERENCE_HIP_GRAPH", True) else self.net.predict
             _, det_d, mask_d = predict(x)                                  # device tensors
         selection = D.Selection.of_batch(self.net, det_d, 1, cs_threshold, cfg.IMAGE_SHAPE, max_detections)
-        out = D.batch_results(self._stager(), det_d, mask_d, selection, self._frames([image], mask_frame), mask_format, canvas, feature)
+        out = D.batch_results(self._stager(), det_d, mask_d, selection, self._frames([image], mask_frame), mask_format, canvas, feature,
+                              measure=measure)
         return self._save_rendered(out, save_path) if render else out
 
     def detect_many(self, images, weights_dir=None, cs_threshold=0.35, in_flight=3, mask_frame="image", mask_format="dense", render=False, *,
-                    max_detections=None):
+                    max_detections=None, measure=False):
         """detect() for a sequence of images at the throughput of Net.predict_stream: the images go through the inference graph in batches of
         config.BATCH_SIZE with `in_flight` batches running at once (one stream / hipGraph / scratch per lane: the launch-bound trunk of one
         batch under the matrix-pipe-bound mask head of another), and every image gets detect()'s own selection and unmolding
@@ -906,10 +913,12 @@ class MaskYOLO(object):
         render=True (see detect; nothing is written to disk here): every dict gains "rendered", drawn once per BATCH on the bytes the batch went
         up as -- one Net.render_instances call, one download of the batch's overlays.  With mask_format="rle" no dense mask exists anywhere.
         max_detections=K (see detect): the selection of every batch runs on the device -- one launch, B * K * 7 words down -- and the batch's
-        [B,R,6] detections are not downloaded."""
+        [B,R,6] detections are not downloaded.
+        measure=True (see detect): every dict gains "measurements", taken once per BATCH -- one Net.measure_masks call over all the slots of
+        its images, one download of 104 bytes per slot."""
         cfg = self.config
         images = list(images)
-        D.check_args(cfg, images, mask_frame, mask_format, render, max_detections)
+        D.check_args(cfg, images, mask_frame, mask_format, render, max_detections, measure)
         assert self.mode == 'inference'
         if weights_dir is not None:
             self.load_weights(weights_dir)
@@ -926,7 +935,8 @@ class MaskYOLO(object):
         out = []
         for bi, (_, det_d, mask_d) in enumerate(self.net.predict_stream(batches(), in_flight=in_flight)):
             selection = D.Selection.of_batch(self.net, det_d, len(groups[bi]), cs_threshold, cfg.IMAGE_SHAPE, max_detections)
-            out += D.batch_results(stager, det_d, mask_d, selection, self._frames(groups[bi], mask_frame), mask_format, canvases.pop(bi))
+            out += D.batch_results(stager, det_d, mask_d, selection, self._frames(groups[bi], mask_frame), mask_format, canvases.pop(bi),
+                                   measure=measure)
         return out
 
     def _save_rendered(self, results, save_path):
