@@ -7,6 +7,7 @@ written as a COCO results file, category ids mapped back through the dataset.
   python example/coco/train_coco.py TRAIN_JSON TRAIN_IMAGES [--val-json PATH --val-images DIR] [--categories 1,3,17] [--keep-crowd]
                                     [--epochs 30] [--size 224] [--batch 8] [--no-augment] [--host-masks] [--results PATH]
                                     [--fit-anchors K] [--mosaic P] [--copy-paste P] [--max-detections N]
+                                    [--hue DEG] [--saturation F] [--contrast F] [--blur SIGMA] [--noise F]
 
 --fit-anchors K fits K anchors to the training set's boxes first (myolo.anchors) and trains with them; without it the anchors are
 Config's, which were fitted to UECFOOD100 at 224 x 224.  --max-detections N scores and writes up to N detections per validation image (1 .. 128,
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path[:0] = [os.path.join(ROOT, "mask-yolo_amd")]
 from myolo import rle                                # noqa: E402
 from myolo.anchors import fit_anchors                # noqa: E402
-from myolo.augment import Augmentation, CopyPaste, Mosaic       # noqa: E402
+from myolo.augment import Augmentation, CopyPaste, Mosaic, Photometric       # noqa: E402
 from myolo.coco import load_coco                     # noqa: E402
 from myolo.config import Config, make_config         # noqa: E402
 from myolo.model import MaskYOLO                     # noqa: E402
@@ -45,6 +46,12 @@ def main():
                                                                             "per sample, on the device (default: 0, off)")
     ap.add_argument("--copy-paste", type=float, default=0.0, metavar="P", help="paste instances of another sample of the batch into a training "
                                                                                 "sample with probability P, on the device (default: 0, off)")
+    ap.add_argument("--hue", type=float, default=0.0, metavar="DEG", help="rotate a training sample's colours by up to DEG degrees either way, on "
+                                                                         "the device (photometric augmentation, DESIGN section 26; default: 0, off)")
+    ap.add_argument("--saturation", type=float, default=0.0, metavar="F", help="saturation gain in [1 - F, 1 + F] (default: 0, off)")
+    ap.add_argument("--contrast", type=float, default=0.0, metavar="F", help="contrast gain about mid-grey in [1 - F, 1 + F] (default: 0, off)")
+    ap.add_argument("--blur", type=float, default=0.0, metavar="SIGMA", help="Gaussian blur with a sigma in [0, SIGMA] pixels, at most 5 (default: 0, off)")
+    ap.add_argument("--noise", type=float, default=0.0, metavar="F", help="additive noise with a deviation in [0, F] of full scale (default: 0, off)")
     ap.add_argument("--clip-norm", type=float, default=None, metavar="C", help="scale the whole gradient down to Euclidean norm C when it is longer "
                     "(the reference config's GRADIENT_CLIP_NORM is 5.0; default: no clipping)")
     ap.add_argument("--weight-decay", type=float, default=0.0, metavar="W", help="decoupled (AdamW) weight decay on the convolution kernels "
@@ -80,9 +87,12 @@ def main():
     if a.clip_norm is not None or a.weight_decay > 0 or a.ema is not None or a.lr_schedule is not None or a.warmup_steps > 0:
         recipe = Recipe(clip_norm=a.clip_norm, weight_decay=a.weight_decay, ema=a.ema,
                         schedule=Schedule(a.lr_schedule or "constant", warmup_steps=a.warmup_steps))
+    photometric = None                              # any of the five flags: colour, blur and noise as the augmenter's last stage on the device
+    if a.hue > 0 or a.saturation > 0 or a.contrast > 0 or a.blur > 0 or a.noise > 0:
+        photometric = Photometric.around(hue=a.hue, saturation=a.saturation, contrast=a.contrast, blur=a.blur, noise=a.noise)
     hist = model.train(train, val, learning_rate=config.LEARNING_RATE, epochs=a.epochs, layers='all', augmentation=augmentation,
                        device_polygons=not a.host_masks, mosaic=Mosaic(p=a.mosaic) if a.mosaic > 0 else None,
-                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None, recipe=recipe)
+                       copy_paste=CopyPaste(p=a.copy_paste) if a.copy_paste > 0 else None, recipe=recipe, photometric=photometric)
     print("epoch losses:", ["%.4f" % h for h in hist])
     print("batches decoded on the device: %d of %d" % (model.host_times["segment_batches"], model.host_times["steps"]))
     os.makedirs(a.logs, exist_ok=True)

@@ -458,6 +458,23 @@ int myolo_copy_paste_batch(const float*   src_images,   /* [B,H,W,3] */
                            int B, int H, int W, int T, int G, int A, int C,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ---- photometric augmentation (myolo/augment.py: Photometric; contract: DESIGN.md section 26, csrc/photometric_kernels.hip).  The last stage of
+ * the device augmenter, on the float image of the stage before it.  Row p = rows[b] holds 32 doubles: [0:12] a 3x4 colour transform A, row major;
+ * [12] the noise deviation; [13] the noise key, an integer in [0, 2^32); [14] the blur radius r, an integer in 0..15; [15] 0; [16:32] the blur
+ * weights w_0..w_15.  With r' = min(r, max_radius), s the input as doubles and refl reflect-101 (refl(i,1) = 0):  h = w0*s(x,y), then for k =
+ * 1..r' ascending h = h + w_k*(s(refl(x-k,W),y) + s(refl(x+k,W),y));  v the same over y on h (h stays binary64);  u_c = ((A[c][0]*v_0 +
+ * A[c][1]*v_1) + A[c][2]*v_2) + A[c][3];  u_c = u_c + p[12]*n with n = ((double)S - 131070.0) * (1.7320508075688772 / 65536.0), S the sum of the
+ * four 16-bit fields of splitmix64((key << 32) | ((y*W + x)*3 + c));  images = (float)(u_c > 0 ? (u_c < 1 ? u_c : 1) : 0).  Every operation is one
+ * binary64 operation in this order, none fused.  On the identity row ([I|0], 0, 0, 0, 0, w_0 = 1) the output has the input's bits.
+ * rows is device memory and is NOT read on the host (augment.check_photo_rows).  max_radius, 0..15, is the caller's host-known bound: a row never
+ * widens a loop beyond it; with max_radius = 0 no blur pass is launched and no workspace is needed (ws may be NULL).
+ * MYOLO_EINVAL (message "photometric_batch: ...", nothing launched or written) for a null pointer, B, H, W <= 0 (or H*W*3 >= 2^31 - 256, B > 65535),
+ * max_radius outside 0..15, an output over the input or the rows, and a workspace under myolo_photometric_batch_ws_bytes(B, H, W, max_radius). */
+size_t myolo_photometric_batch_ws_bytes(int B, int H, int W, int max_radius);
+int myolo_photometric_batch(const float* src_images /* [B,H,W,3] */, const double* rows /* [B,32], device */,
+                            float* images /* [B,H,W,3] */, int max_radius, int B, int H, int W,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* ---- inference input of any size (MaskYOLO.detect / detect_many, csrc/resize_kernels.hip; arithmetic contract: DESIGN.md section 14).  Declared here
  * rather than in the operator API (myolo_hip.h, held to 70 entries).  B uint8 [h,w,3] images of mixed sizes, packed back to back in src at ANY byte
  * offset, resized to the network frame: per image and channel myolo_utils.resize(image, (H, W), preserve_range=True).astype(uint8) in binary64 --

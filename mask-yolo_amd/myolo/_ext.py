@@ -138,6 +138,7 @@ SIGS = {
     "myolo_augment_batch": [P, P, P, P, D, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
     "myolo_mosaic_batch": [P, P, P, P, P, P, D, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
     "myolo_copy_paste_batch": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P],
+    "myolo_photometric_batch": [P, P, P, I, I, I, I, P, Z, P],
     "myolo_segment_masks": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "myolo_resize_images_u8": [P, Z, P, P, P, P, I, I, I, P, Z, P],
     "myolo_rle_masks": [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, Z, P],
@@ -231,6 +232,8 @@ def load():
     lib.myolo_mosaic_batch_ws_bytes.restype = Z
     lib.myolo_copy_paste_batch_ws_bytes.argtypes = [I, I]
     lib.myolo_copy_paste_batch_ws_bytes.restype = Z
+    lib.myolo_photometric_batch_ws_bytes.argtypes = [I, I, I, I]
+    lib.myolo_photometric_batch_ws_bytes.restype = Z
     lib.myolo_resize_images_ws_bytes.argtypes = [I]
     lib.myolo_resize_images_ws_bytes.restype = Z
     lib.myolo_rle_masks_ws_bytes.argtypes = [I, I, I]
@@ -253,7 +256,7 @@ def exported_symbols():
                               "myolo_deconv2x2s2_mask_ws_bytes", "myolo_wino_output_transform_bn_ws_bytes", "myolo_mask_head_out_bwd_sel_ws_bytes",
                               "myolo_dwconv3x3_bwd_data_bnsums_rows", "myolo_wprep_create", "myolo_wprep_destroy", "myolo_wprep_activate", "myolo_wprep_invalidate", "myolo_wprep_count", "myolo_wprep_refresh",
                               "myolo_conv7x7s2_c3_ws_bytes", "myolo_augment_batch_ws_bytes", "myolo_mosaic_batch_ws_bytes", "myolo_copy_paste_batch_ws_bytes",
-                              "myolo_resize_images_ws_bytes",
+                              "myolo_photometric_batch_ws_bytes", "myolo_resize_images_ws_bytes",
                               "myolo_rle_masks_ws_bytes", "myolo_contour_masks_ws_bytes", "myolo_measure_masks_ws_bytes",
                               "myolo_anchor_kmeans_ws_bytes"]
 
@@ -470,6 +473,10 @@ def mosaic_ws_bytes(b, t):
 
 def copy_paste_ws_bytes(b, t):
     return int(load().myolo_copy_paste_batch_ws_bytes(int(b), int(t)))
+
+
+def photometric_ws_bytes(b, h, w, max_radius):
+    return int(load().myolo_photometric_batch_ws_bytes(int(b), int(h), int(w), int(max_radius)))
 
 
 def resize_ws_bytes(b):

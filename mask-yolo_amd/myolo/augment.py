@@ -13,6 +13,10 @@ Mosaic (MaskYOLO.train(mosaic=Mosaic(...))) composes every sample from four imag
 Copy-paste (MaskYOLO.train(copy_paste=CopyPaste(...))) pastes instances of one augmented sample of the batch into another: the host plans two
 small tables per batch (CopyPaste.plan) and the augmenter runs myolo_copy_paste_batch behind either entry -- DESIGN.md ("Copy-paste"),
 tests/copy_paste_ref.py.
+
+Photometric (MaskYOLO.train(photometric=Photometric(...))) changes the pixels only -- hue, saturation, contrast, Gaussian blur, noise: the host
+draws one row of 32 doubles per image (Photometric.row) and the augmenter runs myolo_photometric_batch (csrc/photometric_kernels.hip) last of
+all -- DESIGN.md ("Photometric augmentation"), tests/photometric_ref.py.
 """
 import math
 
@@ -281,6 +285,158 @@ def check_paste_tables(donor, select, B, T):
         raise ValueError("copy-paste tables: select names a slot at or above T = %d" % T)
 
 
+PHOTO_ROW = 32           # doubles per image: A [0:12], noise deviation [12], noise key [13], blur radius [14], 0 [15], blur weights [16:32]
+PHOTO_MAX_RADIUS = 15
+_HUE_K = np.array([[0., -1., 1.], [1., 0., -1.], [-1., 1., 0.]])
+_LUMA = np.array([0.299, 0.587, 0.114])
+
+
+def photo_reflect(i, n):
+    """reflect-101 index of the blur: ... 2 1 | 0 1 .. n-1 | n-2 ...; valid however far i lies outside [0, n)"""
+    if n == 1:
+        return 0
+    P = 2 * (n - 1)
+    m = ((i % P) + P) % P
+    return m if m < n else P - m
+
+
+class Photometric(object):
+    """What MaskYOLO.train(photometric=...) takes: colour, blur and noise applied to a training image on the device, after every geometric stage
+    (DESIGN.md, "Photometric augmentation").
+
+    p           probability that a sample is touched at all
+    hue         (low, high) rotation of the colour about the grey axis in degrees, within [-180, 180]
+    saturation  (low, high) gain, >= 0
+    contrast    (low, high) gain about mid-grey, >= 0
+    blur        (low, high) Gaussian sigma in pixels, within [0, 5]
+    noise       (low, high) standard deviation of additive noise as a fraction of full scale, within [0, 1]
+    seed        row() is a pure function of (seed, epoch, image_id)"""
+
+    DRAWS = 7            # per sample: touched?, hue, saturation, contrast, sigma, noise deviation, noise key
+
+    def __init__(self, p=1.0, hue=(0., 0.), saturation=(1., 1.), contrast=(1., 1.), blur=(0., 0.), noise=(0., 0.), seed=0):
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p is a probability in [0, 1], got %r" % (p,))
+        self.p = p
+        self.hue = _pair("hue", hue, lo=-180.0, hi=180.0)
+        self.saturation = _pair("saturation", saturation, lo=0.0)
+        self.contrast = _pair("contrast", contrast, lo=0.0)
+        self.blur = _pair("blur", blur, lo=0.0, hi=5.0)
+        self.noise = _pair("noise", noise, lo=0.0, hi=1.0)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError("seed must be in [0, 2**32), got %r" % (seed,))
+        self.seed = seed
+
+    @classmethod
+    def around(cls, hue=0.0, saturation=0.0, contrast=0.0, blur=0.0, noise=0.0, p=1.0, seed=0):
+        """the ranges the example scripts' flags name: symmetric about the neutral value -- hue (-hue, hue) degrees, saturation and contrast
+        (max(0, 1 - f), 1 + f) -- and from zero for blur (0, sigma) and noise (0, deviation)"""
+        return cls(p=p, hue=(-hue, hue), saturation=(max(0.0, 1.0 - saturation), 1.0 + saturation), contrast=(max(0.0, 1.0 - contrast), 1.0 + contrast),
+                   blur=(0.0, blur), noise=(0.0, noise), seed=seed)
+
+    @property
+    def max_radius(self):
+        """the largest blur radius a row of this object can hold: what myolo_photometric_batch takes as its bound"""
+        return self.kernel(self.blur[1])[0]
+
+    def draw(self, epoch, image_id, rs=None):
+        """-> dict(on, hue, saturation, contrast, sigma, std, key): the raw draws.  Always the same seven draws in the same order from
+        RandomState([seed, epoch, image_id, 1]), whatever the ranges -- the fourth element keeps the stream apart from Augmentation's.
+        rs: a RandomState of the caller's to re-seed instead (its state is lost): the same draws at a fraction of a fresh generator's cost, as
+        in Mosaic.plan."""
+        key = [self.seed, int(epoch), int(image_id), 1]
+        if rs is None:
+            rs = np.random.RandomState(key)
+        else:
+            rs.seed(key)
+        u = rs.random_sample(self.DRAWS)
+
+        def between(r, x):
+            return r[0] + (r[1] - r[0]) * x if r[1] > r[0] else r[0]
+        return dict(on=bool(u[0] < self.p), hue=between(self.hue, u[1]), saturation=between(self.saturation, u[2]),
+                    contrast=between(self.contrast, u[3]), sigma=between(self.blur, u[4]), std=between(self.noise, u[5]),
+                    key=min(int(u[6] * 4294967296.0), 2 ** 32 - 1))
+
+    @staticmethod
+    def matrix(hue, saturation, contrast):
+        """-> float64 [3,4], the colour transform [c * S * R | 0.5 * (1 - c)] of a hue rotation in degrees, a saturation and a contrast gain:
+        R = cos h * I + (1 - cos h)/3 * J + (sin h / sqrt 3) * K, S = s * I + (1 - s) * 1 L^T.  h = 0, s = 1 and c = 1 are taken without arithmetic."""
+        h, s, c = float(hue), float(saturation), float(contrast)
+        eye = np.eye(3)
+        if h == 0.0:
+            R = eye
+        else:
+            co, si = math.cos(math.radians(h)), math.sin(math.radians(h))
+            R = co * eye + (1.0 - co) / 3.0 * np.ones((3, 3)) + (si / math.sqrt(3.0)) * _HUE_K
+        S = eye if s == 1.0 else s * eye + (1.0 - s) * np.tile(_LUMA, (3, 1))
+        M = R if s == 1.0 else (S if h == 0.0 else S.dot(R))
+        A = np.zeros((3, 4))
+        A[:, :3] = M if c == 1.0 else c * M
+        A[:, 3] = 0.0 if c == 1.0 else 0.5 * (1.0 - c)
+        return A + 0.0                                             # (-0.0 -> 0.0)
+
+    @staticmethod
+    def kernel(sigma):
+        """-> (r, w float64 [16]): r = min(15, ceil(3 sigma)); w_k proportional to exp(-k^2 / (2 sigma^2)) for k <= r and 0 beyond, normalised to
+        w_0 + 2 * sum_{k>=1} w_k = 1.  sigma = 0 gives r = 0, and r = 0 gives exactly w_0 = 1."""
+        sigma = float(sigma)
+        w = np.zeros(PHOTO_MAX_RADIUS + 1)
+        r = min(PHOTO_MAX_RADIUS, int(math.ceil(3.0 * sigma))) if sigma > 0.0 else 0
+        if r == 0:
+            w[0] = 1.0
+            return 0, w
+        k = np.arange(r + 1, dtype=np.float64)
+        with np.errstate(all="ignore"):                            # (a sigma whose square underflows: every w_k beyond w_0 is 0)
+            g = np.exp(-(k * k) / (2.0 * sigma * sigma))
+        g[0] = 1.0
+        w[:r + 1] = g / (g[0] + 2.0 * g[1:].sum())
+        return r, w
+
+    def row(self, epoch, image_id, rs=None):
+        """-> float64[32], the row myolo_photometric_batch reads (layout: PHOTO_ROW); identity() for a sample that is not picked.  rs: as draw."""
+        d = self.draw(epoch, image_id, rs)
+        if not d["on"]:
+            return self.identity()
+        row = np.zeros(PHOTO_ROW)
+        row[0:12] = self.matrix(d["hue"], d["saturation"], d["contrast"]).reshape(-1)
+        row[12], row[13] = d["std"], (float(d["key"]) if d["std"] > 0.0 else 0.0)      # (no noise: the key is not used, and the defaults give identity())
+        r, w = self.kernel(d["sigma"])
+        row[14], row[16:32] = float(r), w
+        return row
+
+    @staticmethod
+    def identity():
+        row = np.zeros(PHOTO_ROW)
+        row[0] = row[5] = row[10] = row[16] = 1.0
+        return row
+
+    def __repr__(self):
+        return ("Photometric(p=%r, hue=%r, saturation=%r, contrast=%r, blur=%r, noise=%r, seed=%r)" %
+                (self.p, self.hue, self.saturation, self.contrast, self.blur, self.noise, self.seed))
+
+
+def check_photo_rows(rows, B):
+    """myolo_photometric_batch does not read its rows on the host, so they are checked here, on the host array, before they are uploaded: finite
+    entries, a radius that is an integer in 0..15, weights >= 0, a deviation >= 0, a key that is an integer in [0, 2**32)."""
+    rows = np.asarray(rows)
+    if rows.shape != (B, PHOTO_ROW) or rows.dtype != np.float64:
+        raise ValueError("photometric rows: expected float64 [%d,%d], got %s %s" % (B, PHOTO_ROW, rows.dtype, rows.shape))
+    if not np.isfinite(rows).all():
+        raise ValueError("photometric rows: every entry is finite")
+    r = rows[:, 14]
+    if ((r != np.floor(r)) | (r < 0) | (r > PHOTO_MAX_RADIUS)).any():
+        raise ValueError("photometric rows: the blur radius is an integer in 0..%d" % PHOTO_MAX_RADIUS)
+    if (rows[:, 16:32] < 0).any():
+        raise ValueError("photometric rows: a blur weight is >= 0")
+    if (rows[:, 12] < 0).any():
+        raise ValueError("photometric rows: the noise deviation is >= 0")
+    k = rows[:, 13]
+    if ((k != np.floor(k)) | (k < 0) | (k >= 4294967296.0)).any():
+        raise ValueError("photometric rows: the noise key is an integer in [0, 2**32)")
+
+
 class DeviceAugmenter(object):
     """Runs myolo_augment_batch: raw bytes, un-augmented instance masks and class ids, one parameter row per image -> the device batch dict
     Net.forward_backward consumes.  T = cfg.TRUE_BOX_BUFFER (= cfg.MAX_GT_INSTANCES) slots per image; a class id of 0 marks an empty slot."""
@@ -306,7 +462,7 @@ class DeviceAugmenter(object):
             raise ValueError("DeviceAugmenter: expected shape %s, got %s" % (tuple(shape), tuple(a.shape)))
         return a.to(self.dev).contiguous()
 
-    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None, mosaic=None, copy_paste=None):
+    def apply(self, raw_images, gt_masks, gt_ids, params, yolo=False, stream=None, consumer=None, mosaic=None, copy_paste=None, photometric=None):
         """raw_images [B,H,W,3] uint8, gt_masks [B,H,W,T] uint8 / bool 0-1, gt_ids [B,T] int32 (0 = empty slot), params [B,8] float64 --
         numpy arrays (uploaded here) or device tensors.  -> dict(images, true_boxes, y_true, gt_ids, gt_boxes, gt_masks), the first three
         with yolo=True.  stream / consumer: as ShapesProducer.batch -- produce on `stream`, the dict carries the event `_ready` and its
@@ -317,12 +473,16 @@ class DeviceAugmenter(object):
         MaskYOLO.train() does.
         copy_paste = (donor int32 [B], select int32 [B]) (CopyPaste.plan): myolo_copy_paste_batch runs behind either entry on the same stream, on
         that entry's images, masks and class ids (its targets are not encoded), and its outputs are the dict's, which gains "paste_dropped" int32
-        [B], the selected instances that found no free slot.  Numpy tables are checked here (check_paste_tables); device tensors as above."""
+        [B], the selected instances that found no free slot.  Numpy tables are checked here (check_paste_tables); device tensors as above.
+        photometric = rows float64 [B,32] (Photometric.row), or (rows, max_radius): myolo_photometric_batch runs last of all on the same stream, on
+        the image of the stage before it, into the dict's images; masks, boxes, ids and targets are that stage's.  max_radius is the host-known
+        bound on the rows' blur radius (default: the largest radius of numpy rows, 15 for a device tensor).  Numpy rows are checked here
+        (check_photo_rows); a device tensor as above."""
         import torch
         from . import _ext as X
         if stream is not None:
             with torch.cuda.stream(stream):
-                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo, mosaic=mosaic, copy_paste=copy_paste)
+                d = self.apply(raw_images, gt_masks, gt_ids, params, yolo=yolo, mosaic=mosaic, copy_paste=copy_paste, photometric=photometric)
                 ev = torch.cuda.Event()
                 ev.record(stream)
             if consumer is not None:
@@ -345,6 +505,16 @@ class DeviceAugmenter(object):
             check_mosaic_tables(mosaic[0], mosaic[2], B, H, W)
         if copy_paste is not None and not (isinstance(copy_paste[0], torch.Tensor) and isinstance(copy_paste[1], torch.Tensor)):
             check_paste_tables(copy_paste[0], copy_paste[1], B, T)
+        if photometric is not None:
+            photo_rows, photo_radius = photometric if isinstance(photometric, tuple) else (photometric, None)
+            if not isinstance(photo_rows, torch.Tensor):
+                photo_rows = np.ascontiguousarray(photo_rows, dtype=np.float64)
+                check_photo_rows(photo_rows, B)
+                if photo_radius is None:
+                    photo_radius = int(photo_rows[:, 14].max())
+            photo_radius = PHOTO_MAX_RADIUS if photo_radius is None else int(photo_radius)
+            if not 0 <= photo_radius <= PHOTO_MAX_RADIUS:
+                raise ValueError("photometric: max_radius is in 0..%d, got %r" % (PHOTO_MAX_RADIUS, photo_radius))
         src = (self._dev(raw_images, torch.uint8, (B, H, W, 3)), self._dev(gt_masks, torch.uint8, (B, H, W, T)),
                self._dev(gt_ids, torch.int32, (B, T)), self._dev(params, torch.float64, (B, 8)))
         if mosaic is not None:
@@ -353,6 +523,8 @@ class DeviceAugmenter(object):
         need = X.augment_ws_bytes(B, T) if mosaic is None else X.mosaic_ws_bytes(B, T)
         if copy_paste is not None:
             need = max(need, X.copy_paste_ws_bytes(B, T))      # (one workspace: the second stage runs behind the first on the same stream)
+        if photometric is not None:
+            need = max(need, X.photometric_ws_bytes(B, H, W, photo_radius))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.dev)
         d = dict(images=torch.empty(B, H, W, 3, device=self.dev),
@@ -362,6 +534,10 @@ class DeviceAugmenter(object):
                  gt_boxes=torch.empty(B, T, 4, dtype=torch.int32, device=self.dev),
                  gt_masks=torch.empty(B, H, W, T, dtype=torch.uint8, device=self.dev))
         outs = (X.ptr(d["images"]), X.ptr(d["gt_masks"]), X.ptr(d["gt_boxes"]), X.ptr(d["gt_ids"]), X.ptr(d["y_true"]), X.ptr(d["true_boxes"]))
+        if photometric is not None:
+            # the stage before the last writes its image to an intermediate tensor; the photometric stage writes the dict's
+            photo_src = torch.empty_like(d["images"])
+            outs = (X.ptr(photo_src),) + outs[1:]
         if copy_paste is not None:
             # the first stage writes four intermediate arrays and encodes no target; the second stage writes the dict's six
             final = outs
@@ -379,6 +555,10 @@ class DeviceAugmenter(object):
             paste_dropped = torch.empty(B, dtype=torch.int32, device=self.dev)
             X.call("myolo_copy_paste_batch", X.ptr(mid[0]), X.ptr(mid[1]), X.ptr(mid[3]), X.ptr(tables[0]), X.ptr(tables[1]), X.ptr(self.anchors),
                    *final, X.ptr(paste_dropped), B, H, W, T, G, A, C, self._ws.data_ptr(), self._ws.numel(), X.stream())
+        if photometric is not None:
+            photo_rows = self._dev(photo_rows, torch.float64, (B, PHOTO_ROW))
+            X.call("myolo_photometric_batch", X.ptr(photo_src), X.ptr(photo_rows), X.ptr(d["images"]), photo_radius, B, H, W,
+                   self._ws.data_ptr(), self._ws.numel(), X.stream())
         if yolo:
             # the step reads three arrays; the other three stay on the dict's side until the kernels that wrote them have run
             d = dict(images=d["images"], true_boxes=d["true_boxes"], y_true=d["y_true"], _gt=(d["gt_ids"], d["gt_boxes"], d["gt_masks"]))
@@ -387,5 +567,7 @@ class DeviceAugmenter(object):
         if copy_paste is not None:
             d["paste_dropped"] = paste_dropped
             d["_paste_src"] = mid + tables      # the first stage's images, masks, boxes and ids, then donor and select: read asynchronously too
+        if photometric is not None:
+            d["_photo_src"] = (photo_src, photo_rows)      # the image of the stage before and the rows: read asynchronously too
         d["_src"] = src            # the kernels read them asynchronously
         return d

@@ -2066,7 +2066,16 @@ class Net(object):
     def _paste_of(out, copy_paste):
         return (out["paste_donor"], out["paste_select"]) if copy_paste else None
 
-    def stage_augmented(self, fill, n, augmenter, yolo=False, mosaic=False, copy_paste=False):
+    @staticmethod
+    def _photo_spec(n):
+        """the photometric rows (Photometric.row), staged last of all"""
+        return [("photo_rows", (n, 32), torch.float64)]
+
+    @staticmethod
+    def _photo_of(out, photometric, photo_radius):
+        return (out["photo_rows"], photo_radius) if photometric else None
+
+    def stage_augmented(self, fill, n, augmenter, yolo=False, mosaic=False, copy_paste=False, photometric=False, photo_radius=15):
         """The augmented form of stage_batch: fill(arrays) writes [raw images uint8 [n,H,W,3], un-augmented masks uint8 [n,H,W,T], class ids
         int32 [n,T] (0 = empty slot), parameter rows float64 [n,8]] (BatchGenerator.fill_raw) into the same ring of pinned staging sets; behind
         the copies, on the copy stream, `augmenter` (myolo.augment.DeviceAugmenter) produces the step's inputs from them.  No target is encoded
@@ -2074,15 +2083,18 @@ class Net(object):
         mosaic: fill also writes [sources int32 [n,4], tile rows float64 [n,4,8], centres int32 [n,2]] behind the rows -- checked by the caller
         (augment.check_mosaic_tables) -- and the augmenter runs myolo_mosaic_batch on them.
         copy_paste: fill writes, last of all, [donors int32 [n], selections int32 [n]] -- checked by the caller (augment.check_paste_tables) -- and
-        the augmenter runs myolo_copy_paste_batch behind its first stage."""
+        the augmenter runs myolo_copy_paste_batch behind its first stage.
+        photometric: fill writes, behind everything else, [rows float64 [n,32]] -- checked by the caller (augment.check_photo_rows) -- and the
+        augmenter runs myolo_photometric_batch as its last stage; photo_radius is the caller's bound on the rows' blur radius (0..15)."""
         cfg = self.cfg
         H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
         spec = [("raw_images", (n, H, W, 3), torch.uint8), ("src_masks", (n, H, W, T), torch.uint8), ("src_ids", (n, T), torch.int32),
-                ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else []) + (self._paste_spec(n) if copy_paste else [])
+                ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else []) + (self._paste_spec(n) if copy_paste else []) + \
+            (self._photo_spec(n) if photometric else [])
 
         def finish(out):
             return augmenter.apply(out["raw_images"], out["src_masks"], out["src_ids"], out["aug_params"], yolo=yolo, mosaic=self._mosaic_of(out, mosaic),
-                                   copy_paste=self._paste_of(out, copy_paste))
+                                   copy_paste=self._paste_of(out, copy_paste), photometric=self._photo_of(out, photometric, photo_radius))
         return self._stage_upload(spec, fill, finish)
 
     @staticmethod
@@ -2093,7 +2105,8 @@ class Net(object):
         B, H, W, T = masks.shape
         X.call("myolo_segment_masks", *[X.ptr(t) for t in tables], X.ptr(masks), X.ptr(boxes), B, H, W, T, X.stream())
 
-    def stage_segments(self, fill, n, augmenter, yolo=False, n_verts=0, n_parts=0, n_bounds=0, mosaic=False, copy_paste=False):
+    def stage_segments(self, fill, n, augmenter, yolo=False, n_verts=0, n_parts=0, n_bounds=0, mosaic=False, copy_paste=False, photometric=False,
+                       photo_radius=15):
         """stage_augmented for segments instead of masks (myolo.coco datasets, and myolo.via datasets with every outline a one-part segment):
         fill(arrays) writes [raw images uint8 [n,H,W,3], vertices float64 [cap,2] (row, col) in source-image pixels, part offsets int32 [cap+1],
         slot -> part offsets int32 [n*T+1], boundaries int32 [cap], slot -> boundary offsets int32 [n*T+1], source heights int32 [n], class ids
@@ -2102,8 +2115,8 @@ class Net(object):
         device [n,H,W,T] buffer (no boxes: the augmenter derives them from the warped masks) and `augmenter` takes it from there: no mask exists
         on the host or crosses PCIe.
         n_verts, n_parts, n_bounds: what fill will write; each pinned buffer holds the next power of two (at least 1024, 64, 1024), so that
-        batches of different segments share a few staging shapes; with n_bounds = 0 no boundary buffer is staged at all.  mosaic, copy_paste: as
-        stage_augmented."""
+        batches of different segments share a few staging shapes; with n_bounds = 0 no boundary buffer is staged at all.  mosaic, copy_paste,
+        photometric, photo_radius: as stage_augmented."""
         cfg, dev = self.cfg, self.dev
         H, W, T = cfg.IMAGE_SHAPE[0], cfg.IMAGE_SHAPE[1], cfg.TRUE_BOX_BUFFER
 
@@ -2115,7 +2128,8 @@ class Net(object):
                 ("seg_part_off", (cap(n_parts, 64) + 1,), torch.int32), ("seg_slot_part", (n * T + 1,), torch.int32),
                 ("seg_bounds", (cap(n_bounds, 1024),), torch.int32), ("seg_slot_bound", (n * T + 1,), torch.int32), ("seg_src_h", (n,), torch.int32),
                 ("src_ids", (n, T), torch.int32), ("src_row", (n, H), torch.int32), ("src_col", (n, W), torch.int32),
-                ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else []) + (self._paste_spec(n) if copy_paste else [])
+                ("aug_params", (n, 8), torch.float64)] + (self._mosaic_spec(n) if mosaic else []) + (self._paste_spec(n) if copy_paste else []) + \
+            (self._photo_spec(n) if photometric else [])
         fill_all = fill
         if n_bounds == 0:
             # no code in the batch (always so for outlines): nothing is staged for the boundaries -- fill gets an empty array in their place and
@@ -2129,7 +2143,7 @@ class Net(object):
                                                 "src_col"))
             self.segment_masks(tables, masks)
             d = augmenter.apply(out["raw_images"], masks, out["src_ids"], out["aug_params"], yolo=yolo, mosaic=self._mosaic_of(out, mosaic),
-                                copy_paste=self._paste_of(out, copy_paste))
+                                copy_paste=self._paste_of(out, copy_paste), photometric=self._photo_of(out, photometric, photo_radius))
             d["_seg_src"] = tables                          # read asynchronously, like _src
             return d
         return self._stage_upload(spec, fill_all, finish)

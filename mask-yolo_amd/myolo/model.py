@@ -464,7 +464,7 @@ class MaskYOLO(object):
 
     def train(self, train_dataset, val_dataset, learning_rate, epochs, layers,
               augmentation=None, custom_callbacks=None, no_augmentation_sources=None, max_samples=None, verbose=1, shuffle_seed=0,
-              device_polygons=True, mosaic=None, *, recipe=None, initial_epoch=0, copy_paste=None):
+              device_polygons=True, mosaic=None, *, recipe=None, initial_epoch=0, photometric=None, copy_paste=None):
         """model.py:943-1060.  Returns the list of per-epoch mean training losses; ``self.history`` holds
         {"loss": [...], "val_loss": [...]} like the Keras History the reference's fit_generator produces.
         shuffle_seed: the generators' one-off shuffle (myolo_utils.py:711-712) draws from RandomState(shuffle_seed) -- the
@@ -484,6 +484,10 @@ class MaskYOLO(object):
         copy_paste (keyword only): a myolo.augment.CopyPaste -- every training sample it picks receives instances of another sample of its batch,
         pasted on the device after both have been augmented / mosaicked, on every route, with or without `augmentation`
         and `mosaic`.  Samples whose source is in no_augmentation_sources neither receive nor donate; validation batches are never pasted.
+        photometric (keyword only): a myolo.augment.Photometric -- hue, saturation, contrast, Gaussian blur and noise on the pixels of every
+        training sample it picks, on the device, after every other stage, on every route, with or without `augmentation`,
+        `mosaic` and `copy_paste`; masks, boxes and targets are untouched.  Samples whose source is in no_augmentation_sources and validation
+        batches are left as they are.
         recipe (keyword only): a myolo.optim.Recipe -- gradient clipping, decoupled weight decay, an EMA of the weights and a learning-rate
         Schedule, all in the optimiser pass on the device.  Step k of the run (counted over all epochs) is taken at
         schedule.lr_at(k, epochs * steps per epoch, learning_rate).  The per-epoch logs and self.history gain "lr" (the epoch's last step),
@@ -517,7 +521,11 @@ class MaskYOLO(object):
             from .augment import CopyPaste
             if not isinstance(copy_paste, CopyPaste):
                 raise TypeError("copy_paste must be a myolo.augment.CopyPaste, got %r" % type(copy_paste).__name__)
-        device_augmenter = augmentation is not None or mosaic is not None or copy_paste is not None
+        if photometric is not None:
+            from .augment import Photometric
+            if not isinstance(photometric, Photometric):
+                raise TypeError("photometric must be a myolo.augment.Photometric, got %r" % type(photometric).__name__)
+        device_augmenter = augmentation is not None or mosaic is not None or copy_paste is not None or photometric is not None
 
         def collect(ds, tag=False):
             ids = list(ds.image_ids)
@@ -574,9 +582,11 @@ class MaskYOLO(object):
         make_item = lambda it: make(it[1])             # noqa: E731
         if polygon_route or segment_route:
             make_item = self._segment_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic,
-                                              counter="polygon_batches" if polygon_route else "segment_batches", copy_paste=copy_paste)
+                                              counter="polygon_batches" if polygon_route else "segment_batches", copy_paste=copy_paste,
+                                              photometric=photometric)
         elif device_augmenter:
-            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic, copy_paste=copy_paste)
+            make_item = self._augmented_batches(augmentation, no_augmentation_sources, train_dataset, train_gen, mode, mosaic, copy_paste=copy_paste,
+                                                photometric=photometric)
 
         # ONE prefetcher for the whole run (Keras' generator queue also keeps running across epoch ends): the first batches of epoch e+1
         # are encoded and uploaded while epoch e finishes
@@ -706,7 +716,34 @@ class MaskYOLO(object):
             return arrays
         return both
 
-    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, copy_paste=None):
+    def photometric_rows(self, photometric, no_augmentation_sources, dataset, epoch, image_ids):
+        """-> float64 [n,32]: the rows train() hands the device augmenter's last stage for these dataset image ids in this epoch (Photometric.row),
+        keyed by image id and epoch, the identity for a sample whose source is in no_augmentation_sources."""
+        skip = set(no_augmentation_sources or [])
+        rows = np.empty((len(image_ids), 32), np.float64)
+        rs = np.random.RandomState(0)          # re-seeded per sample, as in Mosaic.plan
+        for k, i in enumerate(image_ids):
+            plain = bool(skip) and dataset.image_info[i]['source'] in skip
+            rows[k] = photometric.identity() if plain else photometric.row(epoch, i, rs)
+        return rows
+
+    def _with_photo(self, photometric, no_augmentation_sources, dataset, gen, epoch, i, fill):
+        """fill(arrays) -> a fill for the same batch with the photometric rows staged last of all (Net._photo_spec): the rows of the batch's image
+        ids, checked before the upload is queued.  photometric=None: `fill` itself."""
+        if photometric is None:
+            return fill
+        from .augment import check_photo_rows
+        lo, hi = gen.batch_bounds(i)
+        rows = self.photometric_rows(photometric, no_augmentation_sources, dataset, epoch, [inst[4] for inst in gen.all_info[lo:hi]])
+        check_photo_rows(rows, hi - lo)
+
+        def both(arrays):
+            fill(arrays[:-1])
+            arrays[-1][...] = rows
+            return arrays
+        return both
+
+    def _augmented_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, copy_paste=None, photometric=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread: raw bytes, un-augmented masks, class ids and parameter rows go up through the
         engine's staging ring, and the device augmenter runs behind the copies on the copy stream, under the previous step."""
         from .augment import DeviceAugmenter
@@ -720,7 +757,9 @@ class MaskYOLO(object):
             row_of = self._row_of(augmentation, no_augmentation_sources, dataset, epoch)
             fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, lambda arrays: gen.fill_raw(i, arrays, row_of))
             fill = self._with_paste(copy_paste, no_augmentation_sources, dataset, gen, epoch, i, fill)
-            return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None, copy_paste=copy_paste is not None)
+            fill = self._with_photo(photometric, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            return self.net.stage_augmented(fill, hi - lo, aug, yolo=(mode == 'yolo'), mosaic=mosaic is not None, copy_paste=copy_paste is not None,
+                                            photometric=photometric is not None, photo_radius=photometric.max_radius if photometric else 0)
         return make
 
     def _collect_segments(self, dataset, max_samples=None, first=None, load="load_segments"):
@@ -768,7 +807,8 @@ class MaskYOLO(object):
             info.append([image, class_ids, list(segs), (rows.astype(np.int32), cols.astype(np.int32)), int(i), int(h)])
         return info
 
-    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, counter="segment_batches", copy_paste=None):
+    def _segment_batches(self, augmentation, no_augmentation_sources, dataset, gen, mode, mosaic=None, counter="segment_batches", copy_paste=None,
+                         photometric=None):
         """-> make((epoch, batch index)) for train()'s prefetch thread on the device route: image bytes, segments, class ids, index tables and
         parameter rows go up through the engine's staging ring; Net.stage_segments decodes the segments behind the copies on the copy stream, then
         the device augmenter runs.  counter: the key of host_times that counts the batches ("polygon_batches" for a dataset with load_polygons)."""
@@ -783,8 +823,10 @@ class MaskYOLO(object):
             fill, n_verts, n_parts, n_bounds = gen.segment_batch(i, self._row_of(augmentation, no_augmentation_sources, dataset, epoch))
             fill = self._with_mosaic(mosaic, no_augmentation_sources, dataset, gen, epoch, i, fill)
             fill = self._with_paste(copy_paste, no_augmentation_sources, dataset, gen, epoch, i, fill)
+            fill = self._with_photo(photometric, no_augmentation_sources, dataset, gen, epoch, i, fill)
             db = self.net.stage_segments(fill, hi - lo, aug, yolo=(mode == 'yolo'), n_verts=n_verts, n_parts=n_parts, n_bounds=n_bounds,
-                                         mosaic=mosaic is not None, copy_paste=copy_paste is not None)
+                                         mosaic=mosaic is not None, copy_paste=copy_paste is not None, photometric=photometric is not None,
+                                         photo_radius=photometric.max_radius if photometric else 0)
             self.host_times[counter] += 1
             return db
         return make
